@@ -633,7 +633,7 @@ class TimedRun:
                                 timestamps=True, want_alignment=True)
         t_b = time.perf_counter()
         L = out["length"]
-        e.token_timestamps(nb, self.n_prompt, L, [2 * self.T] * nb)
+        ts = e.token_timestamps(nb, self.n_prompt, L, [2 * self.T] * nb)
         t_c = time.perf_counter()
         tm = e.last_timings()
         t_d = time.perf_counter()
@@ -641,7 +641,7 @@ class TimedRun:
         host["timestamps_call_ms"] += (t_c - t_b) * 1e3
         host["timings_call_ms"] += (t_d - t_c) * 1e3
         host["calls"] += 1
-        return (L - self.n_prompt) * nb, tm
+        return (L - self.n_prompt) * nb, tm, {"sequences": out["sequences"], "token_timestamps": ts}
 
     def run_steps(self, n):
         """n steps = n x `passes` engine passes; with the overlap the encoder stage of pass i+1 runs on its own CUs while pass i
@@ -665,14 +665,18 @@ class TimedRun:
         stage = {"logmel_ms": 0.0, "encode_ms": 0.0, "cross_kv_ms": 0.0, "greedy_ms": 0.0, "token_timestamps_ms": 0.0}
         dec_steps = new_tok = 0
         t0 = time.perf_counter()
-        for ntok, tm in self.run_steps(args.steps):
+        res = self.run_steps(args.steps)
+        for ntok, tm, _ in res:
             new_tok += ntok
             for k in stage:
                 stage[k] += tm[k]
             dec_steps += tm["decode_steps"]
         rep.barrier()
         dt_local = time.perf_counter() - t0
-        return {"dt_local": dt_local, "new_tok": new_tok, "stage": stage, "dec_steps": dec_steps, "host": dict(self.host)}
+        # what the last timed step handed back: one entry per pass of that step (host arrays, already returned by the calls)
+        last = [o for _, _, o in res[-len(self.batches):]]
+        return {"dt_local": dt_local, "new_tok": new_tok, "stage": stage, "dec_steps": dec_steps, "host": dict(self.host),
+                "last_step_outputs": last}
 
     def roofline(self, r, dt):
         """Decode step: SURVEY 8d's algorithmic bytes over the HIP-event time of the loop (per engine pass of B streams)."""
@@ -733,6 +737,26 @@ def full_depth_parity(dtype):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, passes, rank, world):
+    """--dump-outputs: the arrays the last timed step's calls returned, all passes of this GPU's share stacked stream by stream -
+    `sequences` (generate_greedy's token ids, prompt included, as float64: exact for ids) and `token_timestamps` (float32, seconds).
+    Above 64 MB in all, a fixed seeded sample of streams is written instead.  Ranks other than 0 add `_rank<r>` to the names."""
+    arrays = {"sequences": np.concatenate([p["sequences"] for p in passes]).astype(np.float64),
+              "token_timestamps": np.concatenate([p["token_timestamps"] for p in passes]).astype(np.float32)}
+    n = arrays["sequences"].shape[0]
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 and rank > 0 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
@@ -774,7 +798,12 @@ def main(argv=None):
                     help="skip the compact 32 / 64 / 2 x 64 streams-per-GPU legs (the single-GPU points of the strong-scaling curve)")
     ap.add_argument("--hub-short-tokens", type=int, default=24,
                     help="max_new_tokens of the second hub measurement (the <= 2 passes per buffer regime; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (token ids as float64, token timestamps as "
+                         "float32; every stream of this GPU's share) to DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, argv))
@@ -810,6 +839,8 @@ def main(argv=None):
     run.set_share(share)
     eng, heads, prompt, n_prompt = run.eng, run.heads, run.prompt, run.n_prompt
     r = run.timed()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["last_step_outputs"], rank, world)
     dt_local = r["dt_local"]
     dt = rep.max_float(dt_local)           # max over ranks
     per_rank = rep.gather_floats(r["new_tok"] / dt_local)   # tokens/s of every rank on its own clock

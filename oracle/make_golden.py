@@ -45,9 +45,11 @@ WEIGHT_KW = {
 
 
 def _import_reference():
+    """The reference's ASRPipeline and streaming_pipeline module: from the checkout, or from the oracle/_ref bundle that
+    __graft_entry__.build() packs from it (oracle/ref_bundle.reference_dir)."""
     from .ref_bundle import import_reference
 
-    ASRPipeline, sp, _streams = import_reference(REF)
+    ASRPipeline, sp, _streams = import_reference()
     return ASRPipeline, sp
 
 

@@ -36,6 +36,23 @@ def test_bench_self_spawns_ranks_and_prints_one_json_line():
     assert d["roofline"]["weight_bytes_per_step"] == 2 * (32 * 14 * 1280 * 1280 + 51866 * 1280)
 
 
+@pytest.mark.timeout(300)
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step returned (ids as float64, token timestamps as float32), every stream of
+    the share; --steps sets the timed step count and ms_per_step is one step's time."""
+    r = _run(["--gpus", "1", "--steps", "3", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 * d["steps"] - 3 * 16 * 128) < 1.0
+    import numpy as np
+
+    seq, ts = np.load(tmp_path / "sequences.npy"), np.load(tmp_path / "token_timestamps.npy")
+    assert seq.dtype == np.float64 and ts.dtype == np.float32
+    assert seq.shape == ts.shape == (16, 3 + 128)
+    assert sorted(os.listdir(tmp_path)) == ["sequences.npy", "token_timestamps.npy"]
+
+
 @pytest.mark.timeout(120)
 def test_bench_refuses_a_rank_count_mismatch():
     r = _run(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0"})     # a launcher gave one rank, the command line says two

@@ -47,12 +47,14 @@ def test_metronome_backend_is_consistent_across_overlapping_buffers():
     assert all(w["end"] <= 9.0 - c3.TAIL_GUARD_S + 1e-9 for w in a)
 
 
-@pytest.mark.skipif(not os.path.isdir(rb.REF), reason="the bundle is packed from /root/reference (build container only)")
+@pytest.mark.skipif(rb.reference_dir() is None, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_bundle_round_trip_without_the_checkout(tmp_path):
-    """What the GPU box does: no /root/reference, only the archive -> the reference's classes import from a temporary directory."""
-    out = rb.make_bundle(out=str(tmp_path / "pkg.tar.gz"))
+    """What the GPU box does: no /root/reference, only the archive -> the reference's classes import from a temporary directory.
+    The archive is packed from wherever the reference package is here (the checkout, or a bundle build() left unpacked)."""
+    src = rb.reference_dir()
+    out = rb.make_bundle(ref=src, out=str(tmp_path / "pkg.tar.gz"))
     assert out and os.path.getsize(out) > 10000
-    assert open(out, "rb").read() == open(rb.make_bundle(out=str(tmp_path / "again.tar.gz")), "rb").read()   # deterministic bytes
+    assert open(out, "rb").read() == open(rb.make_bundle(ref=src, out=str(tmp_path / "again.tar.gz")), "rb").read()   # deterministic bytes
     code = (
         "import sys, json\n"
         "from oracle import ref_bundle as rb\n"

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import ref_bundle
 from oracle import whisper_oracle as wo
 from tests.test_pipeline_glue import build_amd_pipeline, normalise
 
@@ -115,7 +116,7 @@ def test_concurrent_requests_share_batches(served):
     assert max(list(hub.batches)[before:]) > 1            # different HTTP requests were decoded in one batched pass
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
+@pytest.mark.skipif(ref_bundle.reference_dir() is None, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_reference_remote_backend_against_the_gateway(served, monkeypatch):
     """The reference's own client class, unmodified, talking to the gateway (httpx.post routed to the test client)."""
     from oracle.make_golden import _import_reference
@@ -137,7 +138,7 @@ def test_reference_remote_backend_against_the_gateway(served, monkeypatch):
     assert normalise(got) == normalise(want)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
+@pytest.mark.skipif(ref_bundle.reference_dir() is None, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_session_routes_mirror_the_reference_server(served):
     """R:examples/server.py:118-163: create / add_chunk (base64 float32 as a query parameter) / process / clear / end.  Two
     sessions stream the golden clip in lock step through their own scheduler state and the shared hub; the words each one

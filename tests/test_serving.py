@@ -1,13 +1,13 @@
 """Cross-stream batching hub (thewhisper_amd/serving.py) on CPU with the oracle-backed engine: concurrent sessions get
 exactly the per-stream results, and their requests are really executed as shared batches."""
 import json
-import os
 import threading
 
 import numpy as np
 import pytest
 import torch
 
+from oracle import ref_bundle
 from oracle import whisper_oracle as wo
 from tests.test_pipeline_glue import build_amd_pipeline, golden, normalise
 
@@ -59,7 +59,7 @@ def test_hub_batches_concurrent_sessions_and_replays_reference_stream():
     assert max(hub.batches) > 1                                  # requests of different sessions shared a batch
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
+@pytest.mark.skipif(ref_bundle.reference_dir() is None, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_hub_under_the_reference_scheduler():
     """Two unmodified reference StreamingPipeline instances (own scheduler state each) sharing one hub reproduce the
     committed/uncommitted words of the reference's single-stream run."""

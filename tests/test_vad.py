@@ -2,7 +2,6 @@
 reference's unmodified StreamingPipeline, gates which audio reaches the backend.  GPU (-m gpu): tw_vad_energy == the
 restatement (probabilities within 2e-5, decisions at the reference's threshold 0.1 identical away from the threshold), batched
 == per stream, silero's calling contract."""
-import os
 import sys
 import types
 
@@ -10,9 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import ref_bundle
 from oracle import whisper_oracle as wo
 
-REF = "/root/reference"
+# the reference checkout, or the package build() packed from it into oracle/_ref (oracle/ref_bundle.py)
+HAVE_REF = ref_bundle.reference_dir() is not None
 
 
 def _talk_silence(seed=0, secs=(1.0, 2.0, 1.5, 2.0, 1.0)):
@@ -57,7 +58,7 @@ class _OracleVad:
         return torch.tensor(p[0, 0])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+@pytest.mark.skipif(not HAVE_REF, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_gate_under_the_reference_scheduler():
     """The reference's StreamingPipeline with its VAD state machine switched on (R:...:640-721): only audio around speech
     reaches the backend, and nothing is sent during the long trailing silence."""
@@ -169,7 +170,7 @@ def test_vad_service_batches_sessions_and_equals_sequential_detectors():
     svc.close()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+@pytest.mark.skipif(not HAVE_REF, reason="neither the reference checkout nor its oracle/_ref bundle is present")
 def test_gateway_sessions_are_gated_by_the_shared_vad_service():
     """SessionHost + VadService under the reference's unmodified StreamingPipeline: the add_chunk route asks for all frames of a
     chunk at once (one service request per chunk), the scheduler's state machine sees exactly the per-frame decisions of a

@@ -42,11 +42,11 @@ struct tw_ctx {
   tw_config cfg{};
   int dtype = 1;
   bool w8 = false;   // decoder projection weights in MXFP8 (TW_BF16_MXFP8 / TW_BF16_W8A16 contexts)
-  int a16 = 0;       // ... contracted as bf16 after widening in registers (TW_BF16_W8A16; TW_FP8_ACT=bf16|fp8 overrides at run time for A/B)
+  int a16 = 0;       // ... contracted as bf16 after widening in registers (TW_BF16_W8A16)
   // "cross query ahead" (decode_core): the decoder's cross-attention query projection is folded into the two launches before
   // it, which saves one dependent launch per layer and step.  du = float32 [Bmax][d] pre-activation of that projection.
   bool fuse_cq = false;
-  bool enc_fold = true;   // encoder pre-LayerNorms folded into the QKV / fc1 GEMMs (GemmEpilogue::stats_*); TW_ENC_FOLD_LN=0: two LayerNorm launches per layer
+  bool enc_fold = true;   // encoder pre-LayerNorms folded into the QKV / fc1 GEMMs (GemmEpilogue::stats_*); false: two LayerNorm launches per layer
   float *ln_stats_a = nullptr, *ln_stats_b = nullptr;   // [rows][d / 32][2] partial row statistics of xa / xb
   float* du = nullptr;
   float* dstats = nullptr;   // [Bmax][d / tile rows][2] partial LayerNorm statistics of the residual stream (see GemvArgs::stats)
@@ -299,26 +299,17 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   c->cfg = *cfg;
   c->w8 = cfg_w8;
   c->a16 = cfg->dtype == TW_BF16_W8A16;
-  if (cfg->dtype == TW_BF16_MXFP8) {   // same weights and layouts: the activation flavour can be switched for A/B measurements
-    const char* fa = getenv("TW_FP8_ACT");
-    if (fa && !strcmp(fa, "bf16")) c->a16 = 1;
-  }
   c->dtype = c->w8 ? (int)TW_BF16 : cfg->dtype;
   c->esz = c->dtype == TW_F32 ? 4 : 2;
   c->d = cfg->d_model; c->H = cfg->heads; c->ffn = cfg->ffn; c->V = cfg->vocab;
   c->T = cfg->source_positions; c->Tp = (c->T + 63) / 64 * 64; c->P = cfg->target_positions;
   c->n_mels = cfg->n_mels; c->C = (cfg->n_mels + 63) / 64 * 64;
   c->Bmax = cfg->max_batch; c->Le = cfg->enc_layers; c->Ld = cfg->dec_layers; c->Ha = cfg->n_align_heads;
-  {
-    const char* fe = getenv("TW_FUSE_CQ_LAYOUT");   // 0: do not even lay the weights out for the fused sequence
-    c->fuse_cq = c->d == c->H * 64 && !(fe && atoi(fe) == 0);
-    const char* ef = getenv("TW_ENC_FOLD_LN");
-    c->enc_fold = c->d % 64 == 0 && c->d <= 1280 && !(ef && atoi(ef) == 0);   // (k_gemm.hip: TW_LN_HALF partial statistics per thread)
-  }
+  c->fuse_cq = c->d == c->H * 64;
+  c->enc_fold = c->d % 64 == 0 && c->d <= 1280;   // (k_gemm.hip: TW_LN_HALF partial statistics per thread)
   auto bail = [&](int r) { g_create_error = c->err; tw_destroy(c); return r; };
 #define CALLOC(ptr, bytes, zero) do { int _r = dalloc(c, &(ptr), (bytes), (zero)); if (_r != TW_OK) return bail(_r); } while (0)
 #define CHIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fail(c, TW_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); return bail(TW_EHIP); } } while (0)
-  CHIP(init_decode_kernels());
   CHIP(hipStreamCreate(&c->own_stream));
   for (int i = 0; i < 5; ++i) { CHIP(hipEventCreate(&c->ev0[i])); CHIP(hipEventCreate(&c->ev1[i])); }
   for (int i = 0; i < 8; ++i) CHIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
@@ -641,13 +632,10 @@ int tw_finalize_weights(tw_ctx* c, void* stream) {
     void* scratch = nullptr;
     HIPCHK(c, hipMalloc(&scratch, mx * e));
     // narrow projections (N <= 2048: the three d x d matrices and fc2) are laid out for 8-row tiles so that their launches
-    // cover 160 instead of 80 compute units (k_decode.hip); TW_SK_TR overrides (16 / 8 / 4) for experiments
-    const char* tr_env = getenv("TW_SK_TR");
-    const int tr_narrow = tr_env ? atoi(tr_env) : 8;
-    auto retile = [&](void* w, int N, int K, unsigned char** scales, int* tr_out, bool narrow = false) -> int {
+    // cover 160 instead of 80 compute units (k_decode.hip)
+    auto retile = [&](void* w, int N, int K, unsigned char** scales, int* tr_out) -> int {
       const size_t Np = (size_t)(N + 15) / 16 * 16;
-      int tr = 16;
-      if (tr_out && (N <= 2048 || narrow) && (tr_narrow == 8 || (tr_narrow == 4 && !c->w8)) && N % 16 == 0) tr = tr_narrow;
+      const int tr = tr_out && N <= 2048 && N % 16 == 0 ? 8 : 16;
       if (tr_out) *tr_out = tr;
       if (c->w8) {  // MXFP8 fragments + block scales replace the bf16 rows in the same buffer (half the bytes + 1/32)
         unsigned char* sc = reinterpret_cast<unsigned char*>(scratch);
@@ -668,7 +656,7 @@ int tw_finalize_weights(tw_ctx* c, void* stream) {
       if ((r = retile(L.wqkv, (c->fuse_cq ? 4 : 3) * c->d, c->d, &L.s_qkv, nullptr)) != TW_OK) break;   // K/V scatter epilogue: 16-row tiles
       // (the fused out-projection of large-v3 has 2560 rows: 16-row tiles = 160 workgroups, measured 1.487 vs 1.510 ms per step
       //  with 320 workgroups of 8 rows, each of which re-reads the whole activation block)
-      if ((r = retile(L.wo, (c->fuse_cq ? 2 : 1) * c->d, c->d, &L.s_o, &L.tr_o, getenv("TW_SK_TR_O8") != nullptr)) != TW_OK) break;
+      if ((r = retile(L.wo, (c->fuse_cq ? 2 : 1) * c->d, c->d, &L.s_o, &L.tr_o)) != TW_OK) break;
       if ((r = retile(L.wq_c, c->d, c->d, &L.s_qc, &L.tr_qc)) != TW_OK) break;
       if ((r = retile(L.wo_c, c->d, c->d, &L.s_oc, &L.tr_oc)) != TW_OK) break;
       if ((r = retile(L.w1, c->ffn, c->d, &L.s_1, &L.tr_1)) != TW_OK) break;
@@ -771,7 +759,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
   for (int l = 0; l < c->Le; ++l) {
     const LayerW& L = c->enc[l];
     // pre-LayerNorms: folded into the consuming GEMM (weights carry the gain, the epilogue applies mean / rstd from the partial row
-    // statistics the producing GEMM left), or - TW_ENC_FOLD_LN=0 - a launch that writes a normalised copy
+    // statistics the producing GEMM left), or - without enc_fold - a launch that writes a normalised copy
     if (!fold) HIPCHK(c, launch_layernorm(dt, c->xa, L.ln1_g, L.ln1_b, c->lnbuf, M, d, st));
     {
       GemmEpilogue ep{};
@@ -1206,8 +1194,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   sa.begin_suppress = c->begin_suppress_dev; sa.n_begin_suppress = o->n_begin_suppress;
   sa.suppress_bits = c->suppress_bits; sa.partials = c->sampler_partials;
   // the embedding of the token a step has chosen is written by the sampler's last launch (k_decode.hip: embed_row), so a step is
-  // layers + logits + sampler; only the FIRST step of the call needs its input row from a launch of its own (TW_FUSE_EMBED=0: A/B)
-  static const bool fuse_embed = []() { const char* e = getenv("TW_FUSE_EMBED"); return !(e && atoi(e) == 0); }();
+  // layers + logits + sampler; only the FIRST step of the call needs its input row from a launch of its own
   c->last_draft[0] = n_draft * B; c->last_draft[1] = c->last_draft[2] = c->last_draft[3] = 0;
   bool draft_all_done = false;
   if (n_draft > 0) {
@@ -1216,9 +1203,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
     //      after a rejection the REST of the draft is offered again at the same positions (a changed timestamp or word usually leaves
     //      the text behind it as it was), in launches of one group of rows - such a launch costs about what one step costs and
     //      yields at least the one token a step yields - until a round confirms nothing or the draft is used up. ----
-    static const int retry_rows = []() { const char* e = getenv("TW_DRAFT_RETRY_ROWS"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
-    static const int max_rounds = []() { const char* e = getenv("TW_DRAFT_MAX_ROUNDS"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : v; }();
-    static const int first_rows = []() { const char* e = getenv("TW_DRAFT_FIRST_ROWS"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
+    constexpr int first_rows = 64, retry_rows = 16, max_rounds = 16;   // rows of round 1 / of a retry launch, rounds per call
     const int cap = std::min((c->w8 && !c->a16) ? 16 : 64, c->row_cap);   // W8A8 quantises activations per group of 16 rows: one group per launch
     if (B > cap) return fail(c, TW_EINVAL, "n_draft: %d streams exceed the %d rows of a launch", B, cap);
     const int ts_begin = o->timestamps ? o->no_timestamps_id + 1 : c->V;
@@ -1245,15 +1230,13 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
     c->last_draft[3] = rounds;
     s_start = pos;
   }
-  if (fuse_embed) {
-    sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = c->dx0; sa.d = c->d; sa.dtype = c->dtype;
-    HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
-  }
+  sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = c->dx0; sa.d = c->d; sa.dtype = c->dtype;
+  HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%d", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, (int)fuse_embed);
+  snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress);
   const bool use_graph = c->cfg.use_graph != 0;
   if (use_graph && c->step_graph_key != keybuf) {   // other options: the captured sampler arguments are stale
     for (auto& kv : c->step_graphs) (void)hipGraphExecDestroy(kv.second);
@@ -1272,7 +1255,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
     int r = TW_OK;
     hipError_t es = hipSuccess;
     for (int i = 0; i < n && r == TW_OK && es == hipSuccess; ++i) {
-      r = decode_core(c, B, st, 0, nullptr, !fuse_embed);
+      r = decode_core(c, B, st, 0, nullptr, false);
       if (r == TW_OK) es = launch_sampler(sa, st);
     }
     hipError_t ee = hipStreamEndCapture(st, &g);
@@ -1298,11 +1281,11 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   if (n_draft == 0) tic(c, 3, st);
   // two steps per graph launch: measured +2 % at one turbo stream, +0.3 % at 16 large-v3 streams (4 per launch: +3 % / +0.8 %, but
   // up to 7 steps past the last <eos> instead of 5); the finished flags are read LAG launches behind so the host never waits
-  static const int group = []() { const char* e = getenv("TW_GRAPH_STEPS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
+  constexpr int group = 2;
   // while <eos> is still masked (min_new_tokens not reached) no stream can finish, so nothing is wasted by replaying more steps per
   // launch: 8 at a time there (forced-length decoding, e.g. RTFx runs with a fixed token budget); the reference backend's calls
   // set no minimum and always take the small group
-  static const int group_forced = []() { const char* e = getenv("TW_GRAPH_STEPS_FORCED"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
+  constexpr int group_forced = 8;
   const int LAG = std::max(1, 4 / group);
   int steps = 0, launches = 0;
   bool all_done = draft_all_done;
@@ -1322,7 +1305,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
       HIPCHK(c, hipGraphLaunch(ex, st));
     } else {
       c->dec_key_bound = kb;
-      int r = decode_core(c, B, st, 0, nullptr, !fuse_embed);
+      int r = decode_core(c, B, st, 0, nullptr, false);
       if (r != TW_OK) return r;
       HIPCHK(c, launch_sampler(sa, st));
     }
@@ -1381,18 +1364,6 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   c->last_seq_len = L;
   c->last_n_prompt = n_prompt;
   return TW_OK;
-}
-
-// Diagnostics only (NOT part of include/thewhisper.h): copy an internal decoder buffer to the host - tools/dbg/rows_vs_steps.py.
-int tw_dbg_copy(tw_ctx* c, const char* what, void* host, size_t bytes) {
-  if (!c || !what || !host) return TW_EINVAL;
-  TW_ON_DEVICE(c);
-  const std::string w(what);
-  const void* src = w == "dq" ? c->dq : w == "du" ? (void*)c->du : w == "dstats" ? (void*)c->dstats : w == "datt" ? c->datt : w == "dx0" ? c->dx0 :
-                    w == "dx1" ? c->dx1 : w == "dh" ? c->dh : w == "self_k" ? c->self_k : w == "self_v" ? c->self_v : w == "logits" ? (void*)c->logits : nullptr;
-  if (!src) return TW_EINVAL;
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? TW_OK : TW_EHIP;
 }
 
 int tw_last_draft(tw_ctx* c, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds) {

@@ -15,48 +15,14 @@
 //    per stream (HF:generation/logits_process.py:1816-2047, HF:generation/utils.py:2925).
 #include "tw_common.h"
 
-#include <cstdlib>
-
 namespace {
 
-// Probe builds (tools/dbg/probe_gemv.hip -DTW_PROBE_TS) stamp s_memrealtime at a few points of the projection kernels.
-#ifdef TW_PROBE_TS
-__device__ unsigned long long* g_probe_ts;
-// (stamp 0 is taken before the launch's position is known: it is kept in a register and stored with stamp 1)
-#define TW_TS(k) do { if ((k) == 0) probe_t0 = wall_clock64(); else if (threadIdx.x == 0) { unsigned long long* q_ = g_probe_ts + ((size_t)cur_pos * 1024 + blockIdx.x) * 8; \
-                                                                                         if ((k) == 1) q_[0] = probe_t0; q_[k] = wall_clock64(); } } while (0)
-#else
-#define TW_TS(k) do { } while (0)
-#endif
-
-// Compile-time switches of the projection kernel (defaults = what ships; tools/dbg/probe_gemv.hip builds the other settings for A/B runs):
-//  TW_RED_STRIDE   row stride (floats) of the partial tiles in LDS.  A partial tile is written [weight row][stream] by the MFMA lanes and
-//                  read [stream][weight row] by the epilogue threads (16 consecutive rows of one stream per 16 threads, for the stores):
-//                  with 16 floats per row a 32-lane group of a ds_read_b32 hit 4 banks, 8 addresses each (8-way conflict on every read
-//                  of the reduction); 17 spreads it over all 32 banks, the writers stay at <= 2 addresses per bank (free for stores).
-//  TW_CG_ORDER     several groups of 16 streams per launch: the HBM weight requests leave FIRST and the (L2) activation requests follow in
-//                  consumption order (step-major); 0 = the order of the one-group kernel (activations first, group-major), which puts
-//                  20 KiB of L2 traffic per wavefront in front of the first HBM request.
-//  TW_CG_EPI_ALL   ... the epilogue of the groups is spread over all 512 threads (two halves of the workgroup take alternate groups).
-//  TW_CG_RING     several groups, 16-bit or f32 weights, one tile per workgroup: the template parameter SK_MAXS is then the wavefront's
-//                  WHOLE step count and the operands go through two register RINGS (weights: 5 steps deep, activations: 3 steps x
-//                  CG groups) refilled as soon as a step has been contracted - straight-line code, the compiler's vmcnt counts are
-//                  exact.  The point is registers: the one-round scheme holds CG x 5 activation fragments at once (80 registers at 64
-//                  streams, 134-158 in total: ONE 512-thread workgroup per CU, so the 320-workgroup launches ran as two rounds on
-//                  the decode loop's 160 CUs); the rings need 48 and two workgroups fit.
-#ifndef TW_RED_STRIDE
-#define TW_RED_STRIDE 17
-#endif
-#ifndef TW_CG_RING
-#define TW_CG_RING 1
-#endif
-#ifndef TW_CG_ORDER
-#define TW_CG_ORDER 1
-#endif
-#ifndef TW_CG_EPI_ALL
-#define TW_CG_EPI_ALL 1
-#endif
-constexpr int kRedTile = 16 * TW_RED_STRIDE;   // floats per partial tile in LDS
+// Row stride (floats) of the projection kernel's partial tiles in LDS.  A partial tile is written [weight row][stream] by the MFMA
+// lanes and read [stream][weight row] by the epilogue threads (16 consecutive rows of one stream per 16 threads, for the stores):
+// with 16 floats per row a 32-lane group of a ds_read_b32 hit 4 banks, 8 addresses each (8-way conflict on every read of the
+// reduction); 17 spreads it over all 32 banks, the writers stay at <= 2 addresses per bank (free for stores).
+constexpr int kRedStride = 17;
+constexpr int kRedTile = 16 * kRedStride;   // floats per partial tile in LDS
 
 __device__ __forceinline__ float wave_sum(float v) { return tw_wave_sum(v); }
 // erf-GELU (activation_function = "gelu").  Strict-f32 contexts use the library erff; bf16 contexts, whose outputs are
@@ -268,7 +234,7 @@ template <> __device__ __forceinline__ void sk_stats<float>(const u32x4_t& v, fl
 // statistics come from the activation fragments the wavefront holds anyway (per-lane sum / sum of squares with
 // v_dot2, folded over the 4 k-groups by two lane swaps, over the wavefronts in the epilogue through LDS): no extra
 // loads and ~60 instead of ~500 VALU instructions on the critical path (at 4 cycles per wave64 VALU op that was 1 us).
-// Ordering rules this kernel follows (measured with tools/dbg/probe_gemv.hip, stamps of s_memrealtime):
+// Ordering rules this kernel follows (measured with s_memrealtime stamps inside the kernel, profiles/r05_projection_probe.txt):
 //  * all kernel arguments are pinned in SGPRs by one asm statement: one batch of scalar loads, one wait;
 //  * vmcnt retires loads IN ORDER, so operands are requested in the order they are consumed: the (L2-resident)
 //    activation fragments, then the HBM weight fragments; sched_barriers keep hipcc from reordering the groups or
@@ -308,7 +274,7 @@ template <> __device__ __forceinline__ void sk_stats<float>(const u32x4_t& v, fl
 // in pairs, the 8-wavefront kernel (SPLIT2) keeps two accumulators per group - the two halves of its slice - and adds them in
 // registers before the tile goes to LDS.  Bit-identical by construction; tests/test_gpu_parity.py::test_rows_of_a_launch_do_not_matter.
 template <typename T, int NW, int SK_MAXS, bool LN, int EPI, bool MULTI, bool W8, int CG, int TR, bool A16 = false, int MODE = 0, bool SPLIT2 = false>
-__global__ __launch_bounds__(NW * 64, (CG > 1 ? ((NW >= 16 || (TW_CG_RING && !MULTI && !W8 && MODE == 2)) ? 4 : 2) : (NW >= 16 ? 4 : (W8 ? (SK_MAXS <= 2 ? 4 : 2) : (SK_MAXS <= 5 ? 4 : 2)))))
+__global__ __launch_bounds__(NW * 64, (CG > 1 ? ((NW >= 16 || (!MULTI && !W8 && MODE == 2)) ? 4 : 2) : (NW >= 16 ? 4 : (W8 ? (SK_MAXS <= 2 ? 4 : 2) : (SK_MAXS <= 5 ? 4 : 2)))))
 void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_arg, int n_arg, int rg_arg,
                         const unsigned char* wscale_arg, const void* bias_arg, const void* res_arg, const float* gw_arg, GemvArgs a) {
   // The first arguments repeat what the request addresses are formed from (operands, K, B, N, tiles per workgroup): gfx950
@@ -347,10 +313,6 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   // (1) what the activation / weight requests need: delivered with the wave (leading arguments), nothing to wait for
   asm volatile("" ::"s"(x), "s"(W), "s"(K), "s"(N), "s"(B), "s"(RG), "s"(wscale));
   int cur_pos = 0;
-#ifdef TW_PROBE_TS
-  unsigned long long probe_t0 = 0;
-#endif
-  TW_TS(0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -363,9 +325,13 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   const int ej = (tid >> 4) & 15, ei = tid & 15;  // epilogue role of threads 0..255: stream ej, tile row ei (rows >= TR idle)
 
   // MODE (several groups of streams only; picked by the launcher): 0 = rounds of SK_MAXS fragments, 2 = operand rings over the
-  // wavefront's whole K slice (TW_CG_RING above; SK_MAXS = the slice's step count).  (1 - rounds with the next round's weights
+  // wavefront's whole K slice (SK_MAXS = the slice's step count; 16-bit or f32 weights only).  (1 - rounds with the next round's weights
   // requested a round ahead - was measured in round 5 and dropped: fc2 at 64 streams 12.1 -> 12.6 us, profiles/r05_projection_probe.txt)
-  constexpr bool RING = CG > 1 && TW_CG_RING && !W8 && MODE == 2;
+  // The rings: weights 5 steps deep, activations 3 steps x CG groups, refilled as soon as a step has been contracted - straight-line
+  // code, the compiler's vmcnt counts are exact.  The point is registers: the one-round scheme holds CG x 5 activation fragments at
+  // once (80 registers at 64 streams, 134-158 in total: ONE 512-thread workgroup per CU, so the 320-workgroup launches ran as two
+  // rounds on the decode loop's 160 CUs); the rings need 48 and two workgroups fit.
+  constexpr bool RING = CG > 1 && !W8 && MODE == 2;
   // RING with MULTI = DUAL (round 5's "two tiles per workgroup", back in round 6): the workgroup contracts TWO weight tiles (tile0,
   // tile0 + 1; the launcher sets RG = 2) against ONE sweep of the activation rings - half the activation (L2) traffic of two workgroups,
   // 160 instead of 320 workgroups for the 5120-row launches (QKV, fc1).  Round 5 removed it because stream 63 of 64 decoded other ids
@@ -376,8 +342,8 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   constexpr int DX = RING ? (SK_MAXS < 3 ? SK_MAXS : 3) : 1;
   u32x4_t rw[DW], rx[DX][CG];
   u32x4_t rw2[DUAL ? DW : 1];
-  // several groups: the two 256-thread halves of the workgroup take alternate groups in the epilogue (TW_CG_EPI_ALL)
-  constexpr bool EALL = CG > 1 && TW_CG_EPI_ALL && NW >= 8;
+  // several groups: the two 256-thread halves of the workgroup take alternate groups in the epilogue
+  constexpr bool EALL = CG > 1 && NW >= 8;
   constexpr int GPT = EALL ? CG / 2 : CG;     // groups per epilogue thread
   u32x4_t wq[SK_MAXS * WPS], xq[CG][SK_MAXS * XPS];
   int wsc[SK_MAXS];  // MXFP8: scale byte of the weight block this lane feeds to the scaled MFMA (A16: of its own first block)
@@ -479,7 +445,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   for (int g = 0; g < CG; ++g)
     xoff[g] = (g * 16 + fr < B) ? (unsigned)((g * 16 * K + lane * E) * (int)sizeof(T)) : 0x80000000u;
   auto load_x = [&](int s0) {
-    if constexpr (CG > 1 && TW_CG_ORDER) {   // step-major: the order mfma_round consumes them in
+    if constexpr (CG > 1) {   // several groups: step-major, the order mfma_round consumes them in
 #pragma unroll
       for (int i = 0; i < SK_MAXS; ++i)
 #pragma unroll
@@ -528,7 +494,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
 #pragma unroll
       for (int g = 0; g < CG; ++g) rx[i][g] = ring_x(g, s_lo + i);
     __builtin_amdgcn_sched_barrier(0);
-  } else if constexpr (CG > 1 && TW_CG_ORDER) {
+  } else if constexpr (CG > 1) {
     // several groups of streams: a wavefront asks for up to 20 KiB of activations per round.  The HBM requests go first (their
     // latency is the long one; vmcnt retires in order, so by the time an activation fragment has arrived its weights have too)
     load_w(tile0, s_lo);
@@ -545,14 +511,9 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   // here, behind the operand requests that are already on their way
   asm volatile("" ::"s"(bias), "s"(res), "s"(gw_p), "s"(cb_p), "s"(a.gelu), "s"(ldy), "s"(d_model), "s"(cache_bstride), "s"(cache_hstride), "s"(y),
                "s"(y_f32), "s"(kcache), "s"(vcache), "s"(stt), "s"(u_p), "s"(nsplit), "s"(stats_p), "s"(rows_streams));
-#ifdef TW_PROBE_TS
-  cur_pos = stt->pos;
-#else
   if (EPI == SK_KV) cur_pos = stt->pos;
-#endif
   load_epi(tile0, e_c, e_gw, e_res);
   __builtin_amdgcn_sched_barrier(0);  // ... nor hoist arithmetic between the requests
-  TW_TS(1);
 
   float mean[GPT], rstd[GPT];
 #pragma unroll
@@ -662,7 +623,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
     } else {
     mfma_round(s_lo);  // operands already in flight
     for (int s0 = s_lo + SK_MAXS; s0 < s_hi; s0 += SK_MAXS) {  // K longer than one round of fragments
-      if constexpr (CG > 1 && TW_CG_ORDER) {
+      if constexpr (CG > 1) {
         load_w(tile, s0);
         __builtin_amdgcn_sched_barrier(0);
         load_x(s0);
@@ -683,7 +644,6 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
       if constexpr (!RING) load_w(nt, s_lo);
       load_epi(nt, n_c, n_gw, n_res);
     }
-    TW_TS(2);
     // D[i = weight row (lane>>4)*4 + reg][j = stream lane&15]
     if (MULTI && grp > 0) __syncthreads();  // previous tile's readers are done with `red`
     if constexpr (SPLIT2) {   // P_2w + P_2w+1: the addition the 16-wavefront kernel performs on its LDS tiles
@@ -693,7 +653,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
 #pragma unroll
     for (int g = 0; g < CG; ++g)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) red[(wave * CG + g) * kRedTile + (kq * 4 + r) * TW_RED_STRIDE + fr] = acc[g][r];
+      for (int r = 0; r < 4; ++r) red[(wave * CG + g) * kRedTile + (kq * 4 + r) * kRedStride + fr] = acc[g][r];
     if (LN && (!MULTI || grp == 0)) {
 #pragma unroll
       for (int g = 0; g < CG; ++g) {
@@ -702,7 +662,6 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
       }
     }
     __syncthreads();
-    TW_TS(3);
     if (tid < (EALL ? 512 : 256)) {
       const int j = ej, i = ei;  // stream (within its group), row: 16 consecutive rows of one stream per 16 threads
       const int n = tile * TR + i;
@@ -714,10 +673,10 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
         if constexpr (NW >= 16) {   // sixteen slices added in pairs: the order the 8-wavefront SPLIT2 flavour reproduces (kernel header)
 #pragma unroll
           for (int w = 0; w < NW; w += 2)
-            v += red[(w * CG + g) * kRedTile + i * TW_RED_STRIDE + j] + red[((w + 1) * CG + g) * kRedTile + i * TW_RED_STRIDE + j];
+            v += red[(w * CG + g) * kRedTile + i * kRedStride + j] + red[((w + 1) * CG + g) * kRedTile + i * kRedStride + j];
         } else {
 #pragma unroll
-          for (int w = 0; w < NW; ++w) v += red[(w * CG + g) * kRedTile + i * TW_RED_STRIDE + j];
+          for (int w = 0; w < NW; ++w) v += red[(w * CG + g) * kRedTile + i * kRedStride + j];
         }
         const float vraw = v;
         if (LN) {
@@ -777,7 +736,6 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
 #pragma unroll
       for (int g = 0; g < GPT; ++g) e_res[g] = n_res[g];
     }
-    TW_TS(4);
   }
 }
 
@@ -1618,52 +1576,28 @@ __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
 }  // namespace
 
-hipError_t init_decode_kernels() { return hipSuccess; }  // nothing to configure (kept for the call site in tw_create)
+// ---------------------------------------------------------------------------------------------
+// Projection dispatch.  api.hip's decode_core issues seven projections per token (with the tile rows its retile picks): QKV
+// (LN, K/V scatter, 16-row tiles), out-projection (residual; 16-row tiles when the fused form has more than 2048 rows), cross query
+// (LN, 8-row), cross out-projection (residual, 8-row), fc1 (LN + GELU; 16-row above 2048 rows), fc2 (residual, 8-row) and the tied
+// logits (LN, fp32 out, 16-row).  Only those flavours are built.
 
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-// how launches for more than 16 streams move their operands (skinny_mfma_kernel's MODE): 2 = operand rings where the shape allows
-// (default), 0 = plain rounds (rounds 3-4); TW_SK_CG_MODE for A/B runs
-static int cg_mode() {
-  static const int m = env_int("TW_SK_CG_MODE", 3);   // 3 = 2 + two tiles per workgroup (DUAL) for the launches with more tiles than TW_SK_RING_BLOCKS
-  return m;
-}
-
+// one launch; the epilogue follows from the arguments
 template <typename T, int NW, int SK_MAXS, bool MULTI, bool W8, int CG, int TR, bool A16 = false, int MODE = 0, bool SPLIT2 = false>
-static hipError_t skinny_launch_cg(const GemvArgs& a, dim3 grid, size_t lds1, hipStream_t st) {
+static hipError_t sk_go(const GemvArgs& a, dim3 grid, size_t lds1, hipStream_t st) {
   const bool ln = a.ln_gw != nullptr;
   const size_t lds = lds1 * CG;
 #define SK_GO(LNV, EPIV) hipLaunchKernelGGL((skinny_mfma_kernel<T, NW, SK_MAXS, LNV, EPIV, MULTI, W8, CG, TR, A16, MODE, SPLIT2>), grid, dim3(NW * 64), lds, st, \
                                             a.x, a.W, a.K, a.B, a.N, a.rg, a.wscale, a.bias, a.res, a.ln_gw, a)
-  if constexpr (SPLIT2) {  // the 8-wavefront flavour of the long-K residual projection (fc2 above 16 rows): kernel header
-    if (ln || a.y_f32 || a.kcache || a.gelu) return hipErrorInvalidValue;
-    if constexpr (MULTI || NW != 8 || CG == 1) {
-      return hipErrorInvalidValue;
-    } else {
-      if (a.res) SK_GO(false, SK_RES);
-      else SK_GO(false, SK_STORE);
-    }
-  } else if constexpr (TR != 16) {  // narrow tiles: plain / residual / GELU projections, one tile per workgroup
+  if constexpr (NW >= 16 || SPLIT2) {  // the long-K residual projection (fc2)
+    if (ln || a.y_f32 || a.kcache || a.gelu || !a.res) return hipErrorInvalidValue;
+    SK_GO(false, SK_RES);
+  } else if constexpr (TR != 16) {  // narrow tiles: residual, LN, LN + GELU projections
     if (a.y_f32 || a.kcache) return hipErrorInvalidValue;
-    if constexpr (MULTI || (W8 && TR != 8)) {
-      return hipErrorInvalidValue;
-    } else if constexpr (NW >= 16) {
-      if (ln || a.gelu) return hipErrorInvalidValue;
-      if (a.res) SK_GO(false, SK_RES);
-      else SK_GO(false, SK_STORE);
-    } else {
-      if (a.gelu) { if (!ln || a.res) return hipErrorInvalidValue; SK_GO(true, SK_GELU); }
-      else if (a.res) { if (ln) return hipErrorInvalidValue; SK_GO(false, SK_RES); }
-      else if (ln) SK_GO(true, SK_STORE);
-      else SK_GO(false, SK_STORE);
-    }
-  } else if constexpr (NW >= 16) {  // 16 wavefronts per tile only for the long-K residual projections (fc2)
-    if (ln || a.y_f32 || a.kcache || a.gelu) return hipErrorInvalidValue;
-    if (a.res) SK_GO(false, SK_RES);
-    else SK_GO(false, SK_STORE);
+    if (a.gelu) { if (!ln || a.res) return hipErrorInvalidValue; SK_GO(true, SK_GELU); }
+    else if (a.res) { if (ln) return hipErrorInvalidValue; SK_GO(false, SK_RES); }
+    else if (ln) SK_GO(true, SK_STORE);
+    else return hipErrorInvalidValue;
   } else if (a.y_f32) {
     if (!ln || a.res || a.gelu || a.kcache) return hipErrorInvalidValue;
     SK_GO(true, SK_F32);
@@ -1676,52 +1610,15 @@ static hipError_t skinny_launch_cg(const GemvArgs& a, dim3 grid, size_t lds1, hi
   } else if (a.res) {
     if (ln) return hipErrorInvalidValue;
     SK_GO(false, SK_RES);
-  } else if (ln) {
-    SK_GO(true, SK_STORE);
   } else {
-    SK_GO(false, SK_STORE);
+    return hipErrorInvalidValue;
   }
 #undef SK_GO
   return hipGetLastError();
 }
 
-template <typename T, int NW, int SK_MAXS, bool MULTI, bool W8, int TR, bool SPLIT2 = false>
-static hipError_t skinny_launch_v(const GemvArgs& a, dim3 grid, size_t lds1, hipStream_t st) {
-  if constexpr (W8) {
-    // MXFP8 weights.  a.a16: W8A16 (weights widened in registers, bf16 activations) - the only flavour with several groups
-    // of 16 streams (2 steps = 8 activation fragments per group in flight, further rounds for longer K)
-    if (a.a16) {
-      if (a.B <= 16) {
-        if constexpr (SPLIT2) return hipErrorInvalidValue;
-        else return skinny_launch_cg<T, NW, SK_MAXS, MULTI, true, 1, TR, true>(a, grid, lds1, st);
-      }
-      if constexpr (NW != 8 || SK_MAXS != 2) {
-        return hipErrorInvalidValue;
-      } else {
-        if (a.B <= 32) return skinny_launch_cg<T, NW, SK_MAXS, MULTI, true, 2, TR, true, 0, SPLIT2>(a, grid, lds1, st);
-        return skinny_launch_cg<T, NW, SK_MAXS, MULTI, true, 4, TR, true, 0, SPLIT2>(a, grid, lds1, st);
-      }
-    }
-    if (a.B > 16 || SPLIT2) return hipErrorInvalidValue;
-    if constexpr (!SPLIT2) return skinny_launch_cg<T, NW, SK_MAXS, MULTI, true, 1, TR>(a, grid, lds1, st);
-    return hipErrorInvalidValue;
-  } else {
-    if (a.B <= 16) {
-      if constexpr (SPLIT2) return hipErrorInvalidValue;
-      else return skinny_launch_cg<T, NW, SK_MAXS, MULTI, W8, 1, TR>(a, grid, lds1, st);
-    }
-    // several groups of 16 streams: 8 wavefronts x 5 fragments in flight (more rounds for long K) keeps the per-group
-    // activation fragments inside the register file
-    if constexpr (NW != 8 || SK_MAXS != 5) {
-      return hipErrorInvalidValue;
-    } else {
-      if (a.B <= 32) return skinny_launch_cg<T, NW, SK_MAXS, MULTI, W8, 2, TR, false, 0, SPLIT2>(a, grid, lds1, st);
-      return skinny_launch_cg<T, NW, SK_MAXS, MULTI, W8, 4, TR, false, 0, SPLIT2>(a, grid, lds1, st);
-    }
-  }
-}
-
-// split2: this launch is the several-groups form of a projection whose one-group form runs on 16 wavefronts (skinny_launch: `longk`)
+// 16-bit or f32 weights.  NW = 16 only for the long-K residual projection with one group of streams (`big` in skinny_launch);
+// split2: its several-groups form on 8 wavefronts.
 template <typename T, int NW, int TR>
 static hipError_t skinny_launch_nw(const GemvArgs& a0, hipStream_t st, bool split2 = false) {
   constexpr int E = ElemTraits<T>::kPer16B;
@@ -1729,119 +1626,117 @@ static hipError_t skinny_launch_nw(const GemvArgs& a0, hipStream_t st, bool spli
   if (a.K % (4 * E) != 0 || a.B > 64) return hipErrorInvalidValue;
   const size_t lds = (size_t)NW * kRedTile * 4;
   const int tiles = (a.N + TR - 1) / TR;
-  // at most `max_blocks` workgroups: tall matrices (the tied logits projection) walk several tiles per workgroup
-  static const int max_blocks = env_int("TW_SK_MAX_BLOCKS", 512);
-  const int steps_per_wave = (a.K / E / 4 + NW - 1) / NW;
+  const int steps = a.K / E / 4;
+  const int steps_per_wave = (steps + NW - 1) / NW;
   const bool groups = a.B > 16;  // several groups of 16 streams: 5 fragments in flight, further rounds for longer K
-  a.rg = (tiles + max_blocks - 1) / max_blocks;
+  // at most 512 workgroups: tall matrices (the tied logits projection) walk several tiles per workgroup
+  a.rg = (tiles + 511) / 512;
   if (a.rg < 1 || steps_per_wave > (groups ? 5 : 10)) a.rg = 1;  // several tiles per workgroup only with one round per tile
+  if constexpr (TR != 16) { if (a.rg > 1) return hipErrorInvalidValue; }
   dim3 grid((tiles + a.rg - 1) / a.rg);
-  if constexpr (NW == 8) {
+  if constexpr (NW == 16) {   // K >= 4096: at least 8 steps per wavefront, rounds of 10
+    if (groups || a.rg != 1) return hipErrorInvalidValue;
+    return sk_go<T, 16, 10, false, false, 1, TR>(a, grid, lds, st);
+  } else {
     // more than 16 streams, K an exact multiple of the wavefronts' step: operand rings (skinny_mfma_kernel MODE 2), one tile per
     // workgroup - or, for the launches with more 16-row tiles than the decode loop has compute units (QKV, fc1: 320 on 160 CUs),
     // TWO tiles per workgroup contracted against one sweep of the activation rings (DUAL: half the activation traffic)
-    const int steps = a.K / E / 4;
-    static const int ring_blocks = env_int("TW_SK_RING_BLOCKS", 160);
-    if (groups && a.rg == 1 && cg_mode() >= 2 && steps % NW == 0 && !a.y_f32) {
+    if (groups && a.rg == 1 && steps % NW == 0 && !a.y_f32) {
       const int spw = steps / NW;
+      constexpr int SPW = E == 8 ? 5 : 10;    // K = 1280
       bool dual = false;
-      if constexpr (TR == 16)
-        dual = cg_mode() >= 3 && !split2 && (a.kcache || a.gelu) && ring_blocks > 0 && tiles > ring_blocks && tiles <= 2 * ring_blocks && tiles % 2 == 0 && spw == (E == 8 ? 5 : 10);   // (exactly the shapes instantiated below)
+      if constexpr (TR == 16) dual = !split2 && (a.kcache || a.gelu) && tiles > 160 && tiles <= 320 && tiles % 2 == 0 && spw == SPW;
       if (dual) { a.rg = 2; grid = dim3(tiles / 2); }
-#define SK_RING(SPW, SP2, MU) (a.B <= 32 ? skinny_launch_cg<T, NW, SPW, MU, false, 2, TR, false, 2, SP2>(a, grid, lds, st) \
-                                         : skinny_launch_cg<T, NW, SPW, MU, false, 4, TR, false, 2, SP2>(a, grid, lds, st))
-      if constexpr (E == 8) {          // 16-bit contexts: K = 1280 / 5120
-        if constexpr (TR == 16) { if (dual && spw == 5) return SK_RING(5, false, true); }
-        if (spw == 5 && !split2) return SK_RING(5, false, false);
-        if (spw == 20) return split2 ? SK_RING(20, true, false) : SK_RING(20, false, false);
-      } else {                         // strict-f32 contexts
-        if constexpr (TR == 16) { if (dual && spw == 10) return SK_RING(10, false, true); }
-        if (spw == 10 && !split2) return SK_RING(10, false, false);
-        if (spw == 40) return split2 ? SK_RING(40, true, false) : SK_RING(40, false, false);
-      }
+#define SK_RING(SPWV, SP2, MU) (a.B <= 32 ? sk_go<T, NW, SPWV, MU, false, 2, TR, false, 2, SP2>(a, grid, lds, st) \
+                                          : sk_go<T, NW, SPWV, MU, false, 4, TR, false, 2, SP2>(a, grid, lds, st))
+      if constexpr (TR == 16) { if (dual) return SK_RING(SPW, false, true); }
+      if (spw == SPW && !split2) return SK_RING(SPW, false, false);
+      if (spw == 4 * SPW && split2) return SK_RING(4 * SPW, true, false);   // K = 5120: fc2 of the large models
 #undef SK_RING
     }
     if (split2) {   // other long K (e.g. ffn = 4096): rounds of 5 fragments, the slice's midpoint found per step
       if (!groups || a.rg != 1) return hipErrorInvalidValue;
-      return skinny_launch_v<T, NW, 5, false, false, TR, true>(a, grid, lds, st);
+      return a.B <= 32 ? sk_go<T, NW, 5, false, false, 2, TR, false, 0, true>(a, grid, lds, st)
+                       : sk_go<T, NW, 5, false, false, 4, TR, false, 0, true>(a, grid, lds, st);
     }
-  } else if (split2) {
-    return hipErrorInvalidValue;
-  }
-  if constexpr (TR != 16) {
-    if (a.rg > 1) return hipErrorInvalidValue;
-    if (steps_per_wave <= 5 || groups) return skinny_launch_v<T, NW, 5, false, false, TR>(a, grid, lds, st);
-    return skinny_launch_v<T, NW, 10, false, false, TR>(a, grid, lds, st);
-  } else {
-    if (a.rg > 1) {
-      if (steps_per_wave <= 5 || groups) return skinny_launch_v<T, NW, 5, true, false, 16>(a, grid, lds, st);
-      return skinny_launch_v<T, NW, 10, true, false, 16>(a, grid, lds, st);
+    if (groups) {   // several groups of 16 streams: 8 wavefronts x 5 fragments in flight (more rounds for long K) keep the
+                    // per-group activation fragments inside the register file
+      if constexpr (TR == 16) {
+        if (a.rg > 1) return a.B <= 32 ? sk_go<T, NW, 5, true, false, 2, TR>(a, grid, lds, st) : sk_go<T, NW, 5, true, false, 4, TR>(a, grid, lds, st);
+      }
+      return a.B <= 32 ? sk_go<T, NW, 5, false, false, 2, TR>(a, grid, lds, st) : sk_go<T, NW, 5, false, false, 4, TR>(a, grid, lds, st);
     }
-    if (steps_per_wave <= 5 || groups) return skinny_launch_v<T, NW, 5, false, false, 16>(a, grid, lds, st);
-    return skinny_launch_v<T, NW, 10, false, false, 16>(a, grid, lds, st);
+    if constexpr (TR == 16) {
+      if (a.rg > 1) return steps_per_wave <= 5 ? sk_go<T, NW, 5, true, false, 1, TR>(a, grid, lds, st) : sk_go<T, NW, 10, true, false, 1, TR>(a, grid, lds, st);
+    }
+    return steps_per_wave <= 5 ? sk_go<T, NW, 5, false, false, 1, TR>(a, grid, lds, st) : sk_go<T, NW, 10, false, false, 1, TR>(a, grid, lds, st);
   }
 }
 
-// MXFP8 weights: 128-k steps; 2 steps per wavefront cover K = 1280 with 8 wavefronts, 3 cover K = 5120 with 16
+// MXFP8 weights: 128-k steps; 2 steps per wavefront cover K = 1280 with 8 wavefronts, 3 cover K = 5120 with 16.  a.a16: W8A16
+// (weights widened in registers, bf16 activations) - the only flavour with several groups of 16 streams (2 steps = 8 activation
+// fragments per group in flight, further rounds for longer K)
 template <int NW, int TR>
 static hipError_t skinny_launch_w8(const GemvArgs& a0, hipStream_t st, bool split2 = false) {
   GemvArgs a = a0;
   if (a.K % 128 != 0 || a.B > 64) return hipErrorInvalidValue;
   const size_t lds = (size_t)NW * kRedTile * 4;
   const int tiles = (a.N + TR - 1) / TR;
-  static const int max_blocks = env_int("TW_SK_MAX_BLOCKS", 512);
   const int steps_per_wave = (a.K / 128 + NW - 1) / NW;
-  const bool groups = a.B > 16;   // W8A16 only (skinny_launch_v): 2 steps in flight per group, further rounds for longer K
+  const bool groups = a.B > 16;
+  if (groups && !a.a16) return hipErrorInvalidValue;
   // several groups of streams: every workgroup re-reads the whole activation block (164 KB per 64 streams at K = 1280, more bytes than
   // its weight tile), so the 320-tile launches walk TWO tiles per workgroup and keep the activation fragments in registers
-  // (64 streams x 15 s: 3.50 -> 3.32 ms per step, profiles/r04_b64_15s_two_tiles_per_workgroup.txt; neutral for the bf16 kernels)
-  static const int max_blocks_groups = env_int("TW_SK_MAX_BLOCKS_W8_GROUPS", 160);
-  a.rg = (tiles + (groups ? max_blocks_groups : max_blocks) - 1) / (groups ? max_blocks_groups : max_blocks);
+  // (64 streams x 15 s: 3.50 -> 3.32 ms per step, profiles/r04_b64_15s_two_tiles_per_workgroup.txt; neutral for the bf16 kernels);
+  // one group: at most 512 workgroups (the tied logits projection)
+  const int max_blocks = groups ? 160 : 512;
+  a.rg = (tiles + max_blocks - 1) / max_blocks;
   if (a.rg < 1 || steps_per_wave > (groups ? 2 : 3)) a.rg = 1;   // several tiles per workgroup only with one round per tile
-  static const int dbg_mask = env_int("TW_DBG_W8_MULTI_MASK", 7);   // diagnostics: bit 0 QKV, 1 fc1, 2 logits may walk several tiles per workgroup
-  if (groups && a.rg > 1 && !((a.kcache ? 1 : (a.gelu ? 2 : (a.y_f32 ? 4 : 0))) & dbg_mask)) a.rg = 1;
+  if (groups && !a.kcache && !a.gelu && !a.y_f32) a.rg = 1;      // ... and with several groups only for QKV, fc1 and the logits
+  if constexpr (TR != 16) { if (a.rg > 1) return hipErrorInvalidValue; }
   dim3 grid((tiles + a.rg - 1) / a.rg);
   if (split2) {   // W8A16 above 16 rows, long K: rounds of 2 steps, two accumulator sets (skinny_mfma_kernel's header)
     if constexpr (NW != 8) {
       return hipErrorInvalidValue;
     } else {
-      if (!groups || !a.a16 || a.rg != 1) return hipErrorInvalidValue;
-      return skinny_launch_v<bf16_t, NW, 2, false, true, TR, true>(a, grid, lds, st);
+      if (!groups || a.rg != 1) return hipErrorInvalidValue;
+      return a.B <= 32 ? sk_go<bf16_t, NW, 2, false, true, 2, TR, true, 0, true>(a, grid, lds, st)
+                       : sk_go<bf16_t, NW, 2, false, true, 4, TR, true, 0, true>(a, grid, lds, st);
     }
   }
-  if constexpr (TR != 16) {
-    if (a.rg > 1) return hipErrorInvalidValue;
-    if (steps_per_wave <= 2 || groups) return skinny_launch_v<bf16_t, NW, 2, false, true, TR>(a, grid, lds, st);
-    return skinny_launch_v<bf16_t, NW, 3, false, true, TR>(a, grid, lds, st);
-  } else {
-    if (a.rg > 1) {
-      if (steps_per_wave <= 2 || groups) return skinny_launch_v<bf16_t, NW, 2, true, true, 16>(a, grid, lds, st);
-      return skinny_launch_v<bf16_t, NW, 3, true, true, 16>(a, grid, lds, st);
+  if (groups) {
+    if constexpr (NW != 8) {
+      return hipErrorInvalidValue;
+    } else {
+      if constexpr (TR == 16) {
+        if (a.rg > 1) return a.B <= 32 ? sk_go<bf16_t, NW, 2, true, true, 2, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, 2, true, true, 4, TR, true>(a, grid, lds, st);
+      }
+      return a.B <= 32 ? sk_go<bf16_t, NW, 2, false, true, 2, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, 2, false, true, 4, TR, true>(a, grid, lds, st);
     }
-    if (steps_per_wave <= 2 || groups) return skinny_launch_v<bf16_t, NW, 2, false, true, 16>(a, grid, lds, st);
-    return skinny_launch_v<bf16_t, NW, 3, false, true, 16>(a, grid, lds, st);
   }
+#define SK_W8(S, MU) (a.a16 ? sk_go<bf16_t, NW, S, MU, true, 1, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, S, MU, true, 1, TR>(a, grid, lds, st))
+  if constexpr (TR == 16) {
+    if (a.rg > 1) return steps_per_wave <= 2 ? SK_W8(2, true) : SK_W8(3, true);
+  }
+  return steps_per_wave <= 2 ? SK_W8(2, false) : SK_W8(3, false);
+#undef SK_W8
 }
 
 template <typename T>
 static hipError_t skinny_launch(const GemvArgs& a, hipStream_t st) {
-  static const int nw_big = env_int("TW_SK_NW_BIGK", 16);  // wavefronts per tile when K is long (fc2: K = 5120)
-  // long-K residual projection: 16 wavefronts per tile with one group of streams, 8 (two accumulator sets: the same sixteen K slices,
-  // the same order of additions - skinny_mfma_kernel's header) with several
-  const bool longk = a.K >= 4096 && nw_big == 16 && !a.ln_gw && !a.y_f32 && !a.kcache && !a.gelu;
+  // long-K residual projection (fc2, N = d_model: always 8-row tiles): 16 wavefronts per tile with one group of streams, 8 (two
+  // accumulator sets: the same sixteen K slices, the same order of additions - skinny_mfma_kernel's header) with several
+  const bool longk = a.K >= 4096 && !a.ln_gw && !a.y_f32 && !a.kcache && !a.gelu;
   const bool big = longk && a.B <= 16, split2 = longk && a.B > 16;
+  if (a.tr != 0 && a.tr != 8 && a.tr != 16) return hipErrorInvalidValue;
+  if (a.tr != 8 && longk) return hipErrorInvalidValue;
   if (a.wscale) {
     if (ElemTraits<T>::kCode != 1) return hipErrorInvalidValue;
     if (a.tr == 8) return big ? skinny_launch_w8<16, 8>(a, st) : skinny_launch_w8<8, 8>(a, st, split2);
-    if (a.tr != 0 && a.tr != 16) return hipErrorInvalidValue;
-    return big ? skinny_launch_w8<16, 16>(a, st) : skinny_launch_w8<8, 16>(a, st, split2);
+    return skinny_launch_w8<8, 16>(a, st);
   }
-  static const int nw_narrow = env_int("TW_SK_NW_NARROW", 8);  // wavefronts per 8-row tile of the N = 1280, K = 1280 projections (4: A/B)
-  if (a.tr == 8 && !longk && nw_narrow == 4 && a.B <= 16) return skinny_launch_nw<T, 4, 8>(a, st);
   if (a.tr == 8) return big ? skinny_launch_nw<T, 16, 8>(a, st) : skinny_launch_nw<T, 8, 8>(a, st, split2);
-  if (a.tr == 4) return big ? skinny_launch_nw<T, 16, 4>(a, st) : skinny_launch_nw<T, 8, 4>(a, st, split2);
-  if (a.tr != 0 && a.tr != 16) return hipErrorInvalidValue;
-  return big ? skinny_launch_nw<T, 16, 16>(a, st) : skinny_launch_nw<T, 8, 16>(a, st, split2);
+  return skinny_launch_nw<T, 8, 16>(a, st);
 }
 
 template <typename T>
@@ -1920,11 +1815,9 @@ hipError_t launch_sampler(const SamplerArgs& a0, hipStream_t st) {
   if (a0.B < 1 || a0.B > 64 || !a0.partials || !a0.suppress_bits) return hipErrorInvalidValue;
   SamplerArgs a = a0;
   // 32 vocabulary slices per stream (<= 4 x 512 logits per workgroup).  Until round 3 launches for >= 8 streams used 8 slices of 13 x 512
-  // ("8 x B workgroups cover the chip"); same-box A/B at 16 streams: 1.3824 -> 1.3759 ms per step with 32 (TW_SAMPLER_SLICES_MANY=8 restores it)
-  static const int many = env_int("TW_SAMPLER_SLICES_MANY", 32);
-  a.n_slices = a.B >= 8 ? (many == 8 ? 8 : 32) : 32;
-  if (a.n_slices == 8) hipLaunchKernelGGL((sampler_part_kernel<8, 13>), dim3(8, a.B), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((sampler_part_kernel<32, 4>), dim3(32, a.B), dim3(256), 0, st, a);
+  // ("8 x B workgroups cover the chip"); same-box A/B at 16 streams: 1.3824 -> 1.3759 ms per step with 32
+  a.n_slices = 32;
+  hipLaunchKernelGGL((sampler_part_kernel<32, 4>), dim3(32, a.B), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sampler_finish_kernel, dim3(1), dim3(1024), 0, st, a);  // also advances the position
@@ -1938,8 +1831,6 @@ hipError_t launch_sampler_rows(const SamplerArgs& a0, hipStream_t st) {
   SamplerArgs a = a0;
   a.n_slices = 32;    // the slicing of launch_sampler (the partial sums are merged in the same order: same bits)
   a.x_next = nullptr;
-  static const int many = env_int("TW_SAMPLER_SLICES_MANY", 32);
-  if (many == 8) return hipErrorInvalidValue;   // (A/B switch of the step sampler: the two slicings sum in different orders)
   hipLaunchKernelGGL((sampler_part_kernel<32, 4>), dim3(32, a.B), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -137,7 +137,7 @@ __device__ __forceinline__ f32x4_t mfma_step<float>(const u32x4_t& wfrag, const 
 // rate the L2s MISS at.  swz = 1: the tile list, ordered in groups of GM tile-rows (m fastest inside a group, then n), is cut
 // into 8 contiguous chunks and chunk x is walked by XCD x in dispatch order, so the workgroups resident on an XCD at any
 // moment cover about GM x 8 neighbouring tiles: each activation slice is shared by ~8 and each weight slice by ~GM of them.
-// swz = 0: n fastest over the whole grid (the 2-D grid's order), kept for A/B runs (TW_GEMM_XCD=0).
+// swz = 0: n fastest over the whole grid (the 2-D grid's order): the small-M kernel's launches (gemm_grid).
 // Returns false for the padding ids of the last chunk.
 __device__ __forceinline__ bool tw_tile_of_block(int id, int Tm, int Tn, int swz, int& tm, int& tn) {
   const int NT = Tm * Tn;
@@ -852,21 +852,13 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_wreg_kernel(const T* __restri
 
 }  // namespace
 
-static int gemm_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-// 1-D grid of 8 * ceil(tiles / 8) workgroups (tw_tile_of_block).  TW_GEMM_XCD: 1 (default) = XCD-aware order for the large-M kernel
-// only, 0 = row-major everywhere, 2 = XCD-aware for both kernels.  Measured (profiles/r04_encoder_xcd_ab.txt, GPU to itself):
-// encoder of 16 x 10 / 15 / 30 s 16.90 -> 16.51 / 24.03 -> 22.72 / 51.55 -> 49.10 ms; the small-M kernel (one stream: 80-320 small
-// tiles) loses 1.5-5 % with it (3.56 -> 3.75 ms at 10 s), hence off there.
+// 1-D grid of 8 * ceil(tiles / 8) workgroups (tw_tile_of_block): XCD-aware order for the large-M kernel only.  Measured
+// (profiles/r04_encoder_xcd_ab.txt, GPU to itself): encoder of 16 x 10 / 15 / 30 s 16.90 -> 16.51 / 24.03 -> 22.72 / 51.55 -> 49.10 ms;
+// the small-M kernel (one stream: 80-320 small tiles) loses 1.5-5 % with it (3.56 -> 3.75 ms at 10 s), hence row-major there.
 static int gemm_grid(int Tm, int Tn, bool large, int* swz) {
-  static const int xcd = gemm_env("TW_GEMM_XCD", 1);
-  const bool on = xcd == 2 || (xcd == 1 && large);
-  *swz = on ? 1 : 0;
+  *swz = large ? 1 : 0;
   const int NT = Tm * Tn;
-  return on ? 8 * ((NT + 7) / 8) : NT;
+  return large ? 8 * ((NT + 7) / 8) : NT;
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int ST>
@@ -900,21 +892,37 @@ static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M
   constexpr int E = ElemTraits<T>::kPer16B;
   if (M <= 0) return hipSuccess;
   if (K % (8 * E) != 0 || N % 64 != 0) return hipErrorInvalidValue;
-  // Tile choice (TW_GEMM_CFG forces one for experiments):
-  //   5: 128 x 256, 4 wavefronts side by side, weights straight to registers, 3-stage activation ring (kernel 2)  - large M
-  //   6: same, 2 stages;   8: 64 x 256 (narrow N at large M: twice the workgroups)
-  //   4: 128 x 128, 4 wavefronts, both operands through a 2-stage LDS ring (the round-1 shape)
-  //   1: 128 x 64 (3 stages);  12: 64 x 64 (4 stages);  0: 64 x 64 (2 stages)  - small M (one to three streams)
-  static const int forced = gemm_env("TW_GEMM_CFG", -1);
-  static const int narrow = gemm_env("TW_GEMM_NARROW", 5);   // tile config for N <= 2048 at large M (experiments)
-  // kernel 2 from this many 128 x 128 tiles on: 128 x 256 tiles need >= 256 workgroups to cover the chip.  One 30 s chunk's fc1
-  // (M = 1500, N = 5120: 480 tiles = 240 workgroups) is faster in 128 x 64 tiles (encoder 6.27 -> 6.00 ms, profiles/r03_gemm_tiles.txt)
-  static const int wreg_min = gemm_env("TW_GEMM_WREG_MIN", 512);
-  const long long b128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  int cfg;
+  // Tile choice:
+  //   kernel 2: BM x 256 (BM = 80 ... 128), 4 wavefronts side by side, weights straight to registers, 3-stage activation ring - large M
+  //   kernel 1: 128 x 64 (3 stages) or 64 x 64 (4 stages), both operands through an LDS ring - small M (one to three streams)
   if (ep.mode == EPI_KV_CROSS8) {   // fp8 cross-K/V epilogue: one head per wavefront, i.e. kernel 2 whatever the shape
     if (ElemTraits<T>::kCode != 1 || N % 64 != 0) return hipErrorInvalidValue;
     return gemm_wreg_go<T, 128, 4, 3>(A, amap, W, M, N, K, ep, st);
+  }
+  // kernel 2 from 512 128 x 128 tiles on: 128 x 256 tiles need >= 256 workgroups to cover the chip.  One 30 s chunk's fc1
+  // (M = 1500, N = 5120: 480 tiles = 240 workgroups) is faster in 128 x 64 tiles (encoder 6.27 -> 6.00 ms, profiles/r03_gemm_tiles.txt)
+  const long long b128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+  if (N % 256 == 0 && b128 >= 512) {
+    // Tile HEIGHT of kernel 2 by how the grid divides over the chip.  Two workgroups share a CU's matrix pipe, so a CU's time is
+    // proportional to the rows of the tiles it gets, ceil(tiles / 256) x BM, and the kernel ends with the last CU.  The out-projection
+    // and fc2 of 16 x 10 s (M = 8000, N = 1280) are 63 x 5 = 315 tiles of 128 rows: 59 CUs get two and everybody waits for them (the
+    // launch runs at the pace of 512 tiles); 100 x 5 tiles of 80 rows put two on (almost) every CU: 160 instead of 256 rows per CU.
+    // `ovh` rows stand for the per-tile prologue + epilogue (24 picked 96-row tiles for the QKV projection, 111 vs 106 us, and lost
+    // 3 % at 16 x 30 s).
+    constexpr int ovh = 48;
+    int best = 128;
+    long long best_cost = -1;
+    for (int bm : {128, 112, 96, 80}) {
+      const long long tiles = (long long)((M + bm - 1) / bm) * (N / 256);
+      const long long cost = ((tiles + 255) / 256) * (bm + ovh);
+      if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = bm; }
+    }
+    switch (best) {
+      case 80: return gemm_wreg_go<T, 80, 4, 3>(A, amap, W, M, N, K, ep, st);
+      case 96: return gemm_wreg_go<T, 96, 4, 3>(A, amap, W, M, N, K, ep, st);
+      case 112: return gemm_wreg_go<T, 112, 4, 3>(A, amap, W, M, N, K, ep, st);
+      default: return gemm_wreg_go<T, 128, 4, 3>(A, amap, W, M, N, K, ep, st);
+    }
   }
   // Below that: 128 x 64 tiles on a 3-stage ring, or - up to 1000 rows (one chunk of <= 20 s, two of 10 s) - 64 x 64 tiles on a
   // 4-stage ring (64 KB: two workgroups per CU): one 10 s chunk 3.51 -> 3.04 ms, 15 s 3.90 -> 3.55, 2 x 10 s 4.32 -> 4.24; 30 s and
@@ -923,55 +931,15 @@ static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M
   // warmed in L2 (8 x 16 KB of a 64 x 64 tile, 6 x 24 KB of a 128 x 64 tile, one workgroup per CU): out-projection 15.5 -> 12.5 us and
   // fc2 39.5 -> 30, but fc1 18.4 -> 34 and QKV 15.3 -> 24.5 - with one workgroup per CU the wide projections run 2.5 rounds and the
   // launch is bound by the aggregate operand traffic of its small tiles (210 MB for fc1 at M = 500 = 6 TB/s), not by latency
-  // (profiles/r04_gemm_deep_ring_ab.txt).  TW_GEMM_SMALL_64=0 restores the round-3 choice.
-  static const int small64 = gemm_env("TW_GEMM_SMALL_64", 1);
-  if (forced >= 0) cfg = forced;
-  else if (N % 256 == 0 && b128 >= wreg_min) cfg = (N <= 2048) ? narrow : 5;
-  else if (small64 && M <= 1000) cfg = 12;
-  else if (M > 64) cfg = 1;
-  else cfg = 0;
-  if (cfg == 5) {
-    // Tile HEIGHT of kernel 2 by how the grid divides over the chip.  Two workgroups share a CU's matrix pipe, so a CU's time is
-    // proportional to the rows of the tiles it gets, ceil(tiles / 256) x BM, and the kernel ends with the last CU.  The out-projection
-    // and fc2 of 16 x 10 s (M = 8000, N = 1280) are 63 x 5 = 315 tiles of 128 rows: 59 CUs get two and everybody waits for them (the
-    // launch runs at the pace of 512 tiles); 100 x 5 tiles of 80 rows put two on (almost) every CU: 160 instead of 256 rows per CU.
-    // `ovh` rows stand for the per-tile prologue + epilogue.  TW_GEMM_BM forces a height (80 / 96 / 112 / 128) for A/B runs.
-    static const int bm_forced = gemm_env("TW_GEMM_BM", 0);
-    static const int ovh = gemm_env("TW_GEMM_BM_OVH", 48);   // 24 picked 96-row tiles for the QKV projection (111 vs 106 us) and lost 3 % at 16 x 30 s
-    int best = 128;
-    if (bm_forced) {
-      best = bm_forced;
-    } else {
-      long long best_cost = -1;
-      for (int bm : {128, 112, 96, 80}) {
-        const long long tiles = (long long)((M + bm - 1) / bm) * (N / 256);
-        const long long cost = ((tiles + 255) / 256) * (bm + ovh);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = bm; }
-      }
-    }
-    switch (best) {
-      case 80: return gemm_wreg_go<T, 80, 4, 3>(A, amap, W, M, N, K, ep, st);
-      case 96: return gemm_wreg_go<T, 96, 4, 3>(A, amap, W, M, N, K, ep, st);
-      case 112: return gemm_wreg_go<T, 112, 4, 3>(A, amap, W, M, N, K, ep, st);
-      default: break;
-    }
-  }
-  switch (cfg) {
-    case 5: return gemm_wreg_go<T, 128, 4, 3>(A, amap, W, M, N, K, ep, st);
-    case 6: return gemm_wreg_go<T, 128, 4, 2>(A, amap, W, M, N, K, ep, st);
-    case 8: return gemm_wreg_go<T, 64, 4, 3>(A, amap, W, M, N, K, ep, st);     // narrow N: twice the workgroups
-    case 4: return gemm_go<T, 128, 128, 2, 2, 2>(A, amap, W, M, N, K, ep, st);
-    case 1: return gemm_go<T, 128, 64, 2, 2, 3>(A, amap, W, M, N, K, ep, st);
-    case 12: return gemm_go<T, 64, 64, 2, 2, 4>(A, amap, W, M, N, K, ep, st);     // 64 KB: two workgroups per CU
-    default: return gemm_go<T, 64, 64, 2, 2, 2>(A, amap, W, M, N, K, ep, st);
-  }
+  // (profiles/r04_gemm_deep_ring_ab.txt).
+  if (M <= 1000) return gemm_go<T, 64, 64, 2, 2, 4>(A, amap, W, M, N, K, ep, st);   // 64 KB: two workgroups per CU
+  return gemm_go<T, 128, 64, 2, 2, 3>(A, amap, W, M, N, K, ep, st);
 }
 
 hipError_t launch_gemm(int dtype, const void* A, RowMap amap, const void* W, int M, int N, int K,
                        const GemmEpilogue& ep0, hipStream_t st) {
-  static const int staged = gemm_env("TW_GEMM_STAGED", 1);   // 0: the round-3 epilogue everywhere, 2: not for the V^T segment (A/B runs)
   GemmEpilogue ep = ep0;
-  ep.staged = staged;
+  ep.staged = 1;   // the LDS-staged epilogue (and its V^T form) everywhere
   if (dtype == 1) return gemm_dispatch<bf16_t>(A, amap, W, M, N, K, ep, st);
   if (dtype == 2) return gemm_dispatch<f16_t>(A, amap, W, M, N, K, ep, st);
   return gemm_dispatch<float>(A, amap, W, M, N, K, ep, st);

@@ -291,7 +291,6 @@ struct GemvArgs {
   int rows_streams;  // rows mode (tw_row_of): > 0 = number of streams the B rows cycle through; only the K / V^T scatter uses it
 };
 hipError_t launch_gemv(int dtype, const GemvArgs& a, hipStream_t st);
-hipError_t init_decode_kernels();
 // row-major [N][K] -> the fragment-major layout launch_gemv reads (k_decode.hip); dst holds ceil(N/16)*16 rows
 hipError_t launch_tile_weights(int dtype, const void* src, void* dst, int N, int K, int tr, hipStream_t st);
 // row-major bf16 [N][K] -> MXFP8 fragments (ceil(N/16)*16*K bytes) + block scales (ceil(N/16)*16*K/32 bytes); K % 128 == 0

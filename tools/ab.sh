@@ -3,12 +3,12 @@
 #
 #   bash tools/ab.sh [-o OUTFILE] [-n REPEATS] [-k KEYS] 'SETTING ...' -- COMMAND ...
 #
-# SETTING = comma-separated environment assignments ("-" = none), e.g.  'TW_SK_CG_MODE=0 TW_SK_CG_MODE=2,TW_SK_RING_BLOCKS=160 -'.
+# SETTING = comma-separated environment assignments ("-" = none), e.g.  'THEWHISPER_DECODE_CUS=128 THEWHISPER_DECODE_CUS=160 -'.
 # The command runs once per setting (REPEATS times, interleaved: A B A B, so that clock / box drift hits both arms alike); of its
 # output the LAST line that parses as JSON is reduced to KEYS (comma-separated, dotted paths: value,roofline.avg_step_ms,...),
 # otherwise the last 3 lines are echoed.  Everything is appended to OUTFILE (default gpurun_out/ab.txt).
 #
-#   bash tools/ab.sh -o gpurun_out/r05_fuse_embed.txt -k value,roofline.avg_step_ms 'TW_FUSE_EMBED=0 TW_FUSE_EMBED=1' -- \
+#   bash tools/ab.sh -n 2 -k value,roofline.avg_step_ms 'THEWHISPER_DECODE_CUS=128 THEWHISPER_DECODE_CUS=160' -- \
 #        python bench.py --steps 5 --no-cpu-baseline --no-pipeline-leg --no-secondary --latency-iters 0
 OUT=gpurun_out/ab.txt; REP=1; KEYS=value,ms_per_step,roofline.avg_step_ms
 while getopts "o:n:k:" f; do case $f in o) OUT=$OPTARG;; n) REP=$OPTARG;; k) KEYS=$OPTARG;; *) exit 2;; esac; done

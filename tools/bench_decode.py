@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Decode-step microbenchmark (MI355X): large-v3 decoder dims with a reduced layer count, graph replay, ms/step for a few
-batch sizes.  Used for A/B runs of kernel variants selected through TW_* environment variables."""
+batch sizes."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -3,8 +3,7 @@
 `AMDWhisperBackend` three ways: plain (what the reference does: every tick decodes the whole buffer), `reuse_committed_prefix` (round 4:
 approximate) and `draft_previous_tick` (round 6: exact - tw_greedy_opts::n_draft).  Prints one JSON line per variant.
 
-    python tools/bench_draft.py [--model large-v3] [--dtype bf16] [--calls 117] [--variants plain,force,draft]
-Environment: TW_DRAFT_RETRY_ROWS / TW_DRAFT_MAX_ROUNDS / TW_DRAFT_FIRST_ROWS (api.hip) for the verify policy."""
+    python tools/bench_draft.py [--model large-v3] [--dtype bf16] [--calls 117] [--variants plain,force,draft]"""
 import argparse
 import json
 import os

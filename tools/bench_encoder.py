@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Encoder-stage microbenchmark (MI355X): large-v3 encoder (32 layers) + cross-K/V projection, ms per call and achieved
-TFLOP/s against SURVEY.md section 8d's algorithmic flops, for (T, B) pairs.  A/B runs of kernel variants via TW_* env."""
+TFLOP/s against SURVEY.md section 8d's algorithmic flops, for (T, B) pairs."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -7,8 +7,8 @@
         the same streams, teacher-forced logits: (a) 17 / 63 against 0 (must be bit-identical), (b) every stream against the same
         stream decoded in a 16-stream context (bf16-rounding-level differences are legitimate: fc2 splits K differently above 16 streams)
 
-Run under TW_SK_CG_MODE / THEWHISPER_DECODE_CUS / TW_FUSE_EMBED settings (tools/ab.sh) to bisect; this is what located the failure of the
-two-tiles-per-workgroup variant of the projection kernel in round 5 (profiles/r05_group_symmetry_bisect.txt)."""
+Run under THEWHISPER_DECODE_CUS settings (tools/ab.sh) to bisect; this is what located the failure of the two-tiles-per-workgroup
+variant of the projection kernel in round 5 (profiles/r05_group_symmetry_bisect.txt)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -35,7 +35,7 @@ def mode_ids(argv):
     def first_diff(a, b):
         d = np.nonzero(a != b)[0]
         return int(d[0]) if len(d) else None
-    print(f"enc={dims['enc_layers']} mode={os.environ.get('TW_SK_CG_MODE','default')} cus={os.environ.get('THEWHISPER_DECODE_CUS','160')} layers={layers} T={T} graph={graph} new={new}: "
+    print(f"enc={dims['enc_layers']} cus={os.environ.get('THEWHISPER_DECODE_CUS','160')} layers={layers} T={T} graph={graph} new={new}: "
           f"first difference 17 vs 0: {first_diff(s[17], s[0])}, 63 vs 0: {first_diff(s[63], s[0])}, 17 vs 63: {first_diff(s[17], s[63])}", flush=True)
     eng.close()
 
@@ -66,12 +66,11 @@ def mode_logits(argv):
     got = run(big, np.arange(B)); big.close()
     small = make_engine(dims, w, T=T, max_batch=16, dtype="bf16")
     ref = np.concatenate([run(small, np.arange(lo, lo + 16)) for lo in (0, 16, 32, 48)]); small.close()
-    m = os.environ.get("TW_SK_CG_MODE", "default")
     for s in range(ids.shape[1]):
         d17, d63 = np.abs(got[17, s] - got[0, s]).max(), np.abs(got[63, s] - got[0, s]).max()
         rel = np.linalg.norm(got[:, s] - ref[:, s], axis=1) / np.linalg.norm(ref[:, s], axis=1)
         worst = np.argsort(-rel)[:6]
-        print(f"mode={m} layers={layers} step {s}: |17-0|={d17:.3e} |63-0|={d63:.3e}  rel-L2 vs 16-stream context: max {rel.max():.3e} median {np.median(rel):.3e} worst streams {worst.tolist()}"
+        print(f"layers={layers} step {s}: |17-0|={d17:.3e} |63-0|={d63:.3e}  rel-L2 vs 16-stream context: max {rel.max():.3e} median {np.median(rel):.3e} worst streams {worst.tolist()}"
               f" by group {[round(float(rel[g*16:(g+1)*16].max()),5) for g in range(4)]}", flush=True)
 
 

@@ -16,7 +16,12 @@ WORLD_SIZE from the environment.  Rank 0 prints ONE JSON line.
 `--scaling strong --total-streams 128` (round 5): the streams are a FIXED total sharded over the ranks
 (stream i on rank i % N), each rank takes its share in passes of at most 64 streams; the default is weak scaling (--streams per GPU).
 
-Besides the engine-level headline the line carries (rank 0, N = 1 only):
+A plain run does what the headline needs and nothing else: it sets up the contexts, warms up, times the steps, writes
+`--dump-outputs` and prints the line - `value`, `ms_per_step`, the stage times and the decode roofline, all of them read off the timed
+steps themselves.  Everything that takes runs, processes or records of its own is behind `--full` (off by default), where the `--no-*`
+switches below still drop single legs.
+
+With `--full` the line also carries (rank 0, N = 1 only):
   * the CONTRACT's definitions first: `value_contract` (tokens over wall-clock from transcribe() entry to return,
     host buffers in, words out, 16 free-running sessions behind the BatchingHub), `p50_chunk_latency_contract_ms` (one
     `AMDWhisperBackend.transcribe` call on a 10 s host buffer, R:thestage_speechkit/streaming/streaming_pipeline.py:388-435),
@@ -29,8 +34,11 @@ Besides the engine-level headline the line carries (rank 0, N = 1 only):
     the id-identity figures of both from the committed GPU-suite log (refused when that log belongs to other kernel sources);
   * `pipeline`: everything measured through the drop-in API (hub legs, two cohorts, short passes, lock-step);
   * `cpu_baseline`: the reference's own `nvidia.ASRPipeline` on this box's host cores (bounded sample; `kind: "reference"` wherever the
-    reference package is importable - /root/reference, or the oracle/_ref bundle on the GPU box);
-  * `roofline`: decode step, algorithmic bytes (W = 2*(Ld*14*d^2 + V*d)) over HIP-event time.
+    reference package is importable - a checkout beside this one, or the bundle build() packs into oracle/_ref);
+  * `p50_chunk_latency_ms` / `streaming_tick_breakdown` (one stream on the raw engine), `other_configs`, `rtfx`, `streams_sweep`;
+  * `roofline.traffic`: the HBM bytes per decode step of the committed PMC passes (profiles/*_pmc_step_traffic.json).
+`roofline` itself (decode step, algorithmic bytes - SURVEY.md section 8d: W = 2*(Ld*14*d^2 + V*d) - over the HIP-event time of the timed
+steps) is in every line.
 """
 from __future__ import annotations
 
@@ -777,6 +785,10 @@ def main(argv=None):
                          "the fp32 reference's on every full-depth clip (parity_full_depth); bf16 is reported beside it (value_bf16).  "
                          "fp8 = bf16 activations/encoder + MXFP8 decoder projection weights (BASELINE config 5)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line can carry: single-stream latency, the "
+                         "drop-in API (pipeline, config3), the other configurations / dtypes / stream counts, RTFx, the CPU baseline, the "
+                         "committed parity and PMC records.  Off by default: a plain run sets up, warms up, times the steps and prints")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tokens", type=int, default=32, help="forced tokens per CPU-baseline call (BASELINE.md section 3: >= 3 calls x 32)")
     ap.add_argument("--cpu-calls", type=int, default=3)
@@ -860,7 +872,7 @@ def main(argv=None):
 
     # single-stream chunk latency (config 3 shape) on the raw engine: same context, B = 1, PCM already in HBM
     lat = []
-    if rank == 0 and args.latency_iters > 0 and not stub:
+    if rank == 0 and args.full and args.latency_iters > 0 and not stub:
         for _ in range(min(10, args.latency_iters)):   # warm-ups
             step(1)
         tick = {"logmel_ms": 0.0, "encode_ms": 0.0, "cross_kv_ms": 0.0, "greedy_ms": 0.0, "token_timestamps_ms": 0.0}
@@ -880,7 +892,7 @@ def main(argv=None):
         esz, wsz = rf["esz"], rf["wsz"]
         n_pass = args.steps * passes
         args_for_pmc = argparse.Namespace(**{**vars(args), "streams": B})
-        pmc = load_pmc_traffic(args_for_pmc)
+        pmc = load_pmc_traffic(args_for_pmc) if args.full else None
         if args.scaling == "strong":
             workload = (f"whisper-{args.model}, {args.chunk_s} s chunks, {args.total_streams} concurrent streams over ALL GPUs (configs[3], fixed total: "
                         f"{share} on this GPU in {passes} pass(es) of {B}), {args.new_tokens} new tokens/stream forced (min=max), timestamp grammar + "
@@ -899,6 +911,7 @@ def main(argv=None):
             "ms_per_step": round(dt / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": args.scaling,
+            "full": args.full,
             "vs_baseline": None,
             "dtype": (f"bf16 activations, MXFP8 (e4m3 + block scales) decoder weights [{args.dtype}]" if args.dtype.startswith("fp8") else args.dtype),
             "data": "synthetic 16 kHz gaussian audio (sigma 0.1), random-init weights of the named architecture",
@@ -925,7 +938,8 @@ def main(argv=None):
                 "traffic": (round(pmc[0]["hbm_bytes_per_step"]) if pmc else None),
                 "traffic_source": (f"profiles/{pmc[1]}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command line with THESE kernels "
                                    f"(kernel_source_sha256 matches the running build), FETCH_SIZE x2 (gfx950 correction, MI355X_MICROARCH.md)"
-                                   if pmc else "no PMC summary under profiles/ for this workload (model, streams, chunk length, dtype, new tokens) taken with this build's kernel sources (tools/profile_round.sh)"),
+                                   if pmc else "the committed PMC summaries are looked up with --full" if not args.full
+                                   else "no PMC summary under profiles/ for this workload (model, streams, chunk length, dtype, new tokens) taken with this build's kernel sources (tools/profile_round.sh)"),
                 "algorithmic_bytes_per_step": int(alg_bytes / max(1, steps_per_call)),
                 "algorithmic_bytes_per_call": alg_bytes, "weight_bytes_per_step": W, "decode_steps_per_call": steps_per_call,
                 # what the launches really stream: the "cross query ahead" fusion reads 2 d^2 more weight elements per layer (DESIGN.md
@@ -951,36 +965,37 @@ def main(argv=None):
             result["chunk_latency_note"] = (f"raw engine, 1 stream, {args.chunk_s} s chunk resident in HBM, {args.new_tokens} tokens + DTW, "
                                             f"{len(lat)} calls; the contract's latency (one backend call, host buffer in, words out) is "
                                             f"p50_chunk_latency_contract_ms")
-        if world == 1 and not stub and not args.no_pipeline_leg and args.scaling == "weak":
+        if args.full and world == 1 and not stub and not args.no_pipeline_leg and args.scaling == "weak":
             try:
                 pargs = argparse.Namespace(**{**vars(args), "streams": B})
                 result["pipeline"] = pipeline_leg(eng, dims, pargs, local, heads, args.latency_iters, args.hub_rounds)
             except Exception as e:  # noqa: BLE001
                 result["pipeline"] = {"error": repr(e)}
-        pl = result.get("pipeline") or {}
-        # ---- the CONTRACT's definitions first (R:thestage_speechkit/streaming/streaming_pipeline.py:388-435), the
-        # engine-level readings beside them
-        result["value_contract"] = pl.get("hub_tok_per_s")
-        result["p50_chunk_latency_contract_ms"] = pl.get("backend_transcribe_p50_ms")
-        result["p90_chunk_latency_contract_ms"] = pl.get("backend_transcribe_p90_ms")
-        result["hub_request_p50_ms"] = pl.get("hub_request_p50_ms")
-        result["hub_request_p90_ms"] = pl.get("hub_request_p90_ms")
-        result["config3"] = pl.get("config3")
         result["value_definition"] = ("value = tokens/s of the hot path driven through the C ABI with the PCM resident in HBM (what a host written "
-                                      "against include/thewhisper.h gets; bench.py's contract: inputs resident when the timed region starts). "
-                                      "value_contract (= value_api) = SURVEY.md section 8d's definition: generated tokens over wall-clock from "
-                                      "transcribe() entry to return, host buffers in, word dictionaries out, 16 free-running sessions through "
-                                      "AMDWhisperBackend / BatchingHub (pipeline.hub_tok_per_s).  p50_chunk_latency_contract_ms = median wall time of one "
-                                      "AMDWhisperBackend.transcribe call on a 10 s host buffer (8d: 'one backend call'), p50_chunk_latency_ms = the raw "
-                                      "engine on resident PCM.  config3 = the reference scheduler's own 60 s call trace replayed through the backend")
-        result["value_api"] = pl.get("hub_tok_per_s")
-        # the same API with two cohorts of sessions taking turns on the same passes (32 sessions for 16 rows): the encoder stage of the
-        # cohort that sits a pass out runs on the side stream under that pass's decode loop
-        result["value_api_two_cohorts"] = pl.get("hub_2x_tok_per_s")
-        # value_api over the window in which every session still has requests to send (no drain passes at the end of the finite run)
-        result["value_api_steady_state"] = pl.get("hub_steady_tok_per_s")
-        result["value_api_two_cohorts_steady_state"] = pl.get("hub_2x_steady_tok_per_s")
-        if world == 1 and not stub and not args.no_secondary:
+                                      "against include/thewhisper.h gets; bench.py's contract: inputs resident when the timed region starts).")
+        if args.full:
+            pl = result.get("pipeline") or {}
+            # ---- the CONTRACT's definitions first (R:thestage_speechkit/streaming/streaming_pipeline.py:388-435), the
+            # engine-level readings beside them
+            result["value_contract"] = pl.get("hub_tok_per_s")
+            result["p50_chunk_latency_contract_ms"] = pl.get("backend_transcribe_p50_ms")
+            result["p90_chunk_latency_contract_ms"] = pl.get("backend_transcribe_p90_ms")
+            result["hub_request_p50_ms"] = pl.get("hub_request_p50_ms")
+            result["hub_request_p90_ms"] = pl.get("hub_request_p90_ms")
+            result["config3"] = pl.get("config3")
+            result["value_definition"] += (" value_contract (= value_api) = SURVEY.md section 8d's definition: generated tokens over wall-clock from "
+                                          "transcribe() entry to return, host buffers in, word dictionaries out, 16 free-running sessions through "
+                                          "AMDWhisperBackend / BatchingHub (pipeline.hub_tok_per_s).  p50_chunk_latency_contract_ms = median wall time of one "
+                                          "AMDWhisperBackend.transcribe call on a 10 s host buffer (8d: 'one backend call'), p50_chunk_latency_ms = the raw "
+                                          "engine on resident PCM.  config3 = the reference scheduler's own 60 s call trace replayed through the backend")
+            result["value_api"] = pl.get("hub_tok_per_s")
+            # the same API with two cohorts of sessions taking turns on the same passes (32 sessions for 16 rows): the encoder stage of the
+            # cohort that sits a pass out runs on the side stream under that pass's decode loop
+            result["value_api_two_cohorts"] = pl.get("hub_2x_tok_per_s")
+            # value_api over the window in which every session still has requests to send (no drain passes at the end of the finite run)
+            result["value_api_steady_state"] = pl.get("hub_steady_tok_per_s")
+            result["value_api_two_cohorts_steady_state"] = pl.get("hub_2x_steady_tok_per_s")
+        if args.full and world == 1 and not stub and not args.no_secondary:
             legs = []
             for label, model, chunk_s, nb, dt_, k in (("configs[1]: large-v3-turbo, 30 s chunk, batch 1, bf16", "large-v3-turbo", 30, 1, "bf16", 5),
                                                         ("configs[4]: large-v3, MXFP8 decoder weights + fp8 cross-K/V, 15 s chunks, word timestamps", "large-v3", 15, min(B, 16), "fp8", 3),
@@ -1005,14 +1020,15 @@ def main(argv=None):
         # (R:...streaming_pipeline.py:369-370) and the 16-bit context whose greedy ids are identical to the fp32 reference on every clip of
         # the full-depth suite; bfloat16 (the nvidia pipeline's alternative, R:thestage_speechkit/nvidia/asr_pipeline.py:47-60) runs the SAME
         # timed schedule (overlap pipeline, K steps) with its own roofline; the parity figures of both from the committed GPU-suite log
-        result["parity_full_depth"] = {args.dtype: full_depth_parity(args.dtype)} if args.dtype in ("bf16", "f16", "f32") else {}
+        if args.full:
+            result["parity_full_depth"] = {args.dtype: full_depth_parity(args.dtype)} if args.dtype in ("bf16", "f16", "f32") else {}
         if args.dtype == "f16":
             result["dtype_note"] = ("float16 is the headline dtype since round 6: it is the reference's streaming default (torch.float16, "
                                     "streaming_pipeline.py:369-370), costs what bf16 costs (value_bf16 beside it) and carries the north star's "
                                     "'greedy token IDs identical' claim at full depth (parity_full_depth.f16.ids_identical_clips); HF's own bf16 "
                                     "arithmetic flips sub-margin decisions too (tests/test_golden_ctrl.py)")
         other = {"f16": "bf16", "bf16": "f16"}.get(args.dtype)
-        if world == 1 and not stub and not args.no_secondary and other is not None:
+        if args.full and world == 1 and not stub and not args.no_secondary and other is not None:
             run.close()
             run = None
             torch.cuda.empty_cache()
@@ -1039,7 +1055,7 @@ def main(argv=None):
         # streams as two passes of 64 = the N = 1 point of the strong-scaling curve.  Replicas share nothing, so
         # the other points of that curve are these per-GPU rates times N (128 / N streams per GPU): N = 2 -> 2 x the 64-stream rate,
         # N = 4 -> 4 x the 32-stream rate, N = 8 -> 8 x the headline; a node run with `--scaling strong` measures them directly.
-        if world == 1 and not stub and not args.no_secondary and args.streams_sweep and args.scaling == "weak" and args.streams == 16:
+        if args.full and world == 1 and not stub and not args.no_secondary and args.streams_sweep and args.scaling == "weak" and args.streams == 16:
             if run is not None:
                 run.close()
                 run = None
@@ -1069,7 +1085,7 @@ def main(argv=None):
                     "note": "128 concurrent streams (BASELINE configs[3]) on N GPUs; N = 1 is measured here (two passes of 64), N = 2 / 4 / 8 are N x the "
                             "measured single-GPU rate at 64 / 32 / 16 streams per GPU (replicas, no data-path collective: DESIGN.md section 5) - a "
                             "projection, NOT a measurement; `python bench.py --gpus N --scaling strong --total-streams 128` measures it on a node"}
-        if world == 1 and not stub and not args.no_cpu_baseline:
+        if args.full and world == 1 and not stub and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline(args.model, args.chunk_s, args.cpu_tokens, args.cpu_calls)
             except Exception as e:  # noqa: BLE001

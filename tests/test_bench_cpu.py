@@ -53,6 +53,31 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     assert sorted(os.listdir(tmp_path)) == ["sequences.npy", "token_timestamps.npy"]
 
 
+# what only `--full` puts on the line: figures that take runs, processes or committed records of their own
+FULL_ONLY = ("pipeline", "cpu_baseline", "other_configs", "rtfx", "streams_sweep", "strong_scaling_128_streams", "value_bf16", "roofline_bf16",
+             "parity_full_depth", "p50_chunk_latency_ms", "streaming_tick_breakdown", "value_contract", "value_api", "config3",
+             "p50_chunk_latency_contract_ms", "hub_request_p50_ms")
+
+
+@pytest.mark.timeout(300)
+def test_bench_full_is_an_option_and_off_by_default():
+    """A plain run prints the headline, the stage times and the roofline of its own timed steps and none of the `--full` blocks;
+    `--full` is accepted, says so on the line and adds the parity block read from the committed GPU-suite log (the measured legs need
+    the MI355X: tests/test_gpu_bench.py)."""
+    plain, full = _run(["--gpus", "1"]), _run(["--gpus", "1", "--full"])
+    assert plain.returncode == 0 and full.returncode == 0, (plain.stderr[-1000:], full.stderr[-1000:])
+    p = json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][0])
+    f = json.loads([l for l in full.stdout.splitlines() if l.startswith("{")][0])
+    assert p["full"] is False and f["full"] is True
+    assert not [k for k in FULL_ONLY if k in p], sorted(p)
+    for d in (p, f):
+        assert d["unit"] == "tok/s" and d["higher_is_better"] is True and d["dtype"] == "f16" and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["metric"] == "transcription tokens/sec (node), whisper-large-v3 10s chunks"
+        assert d["roofline"]["decode_steps_per_call"] == 130 and d["value_definition"].startswith("value = tokens/s")
+    assert p["roofline"]["traffic"] is None and "--full" in p["roofline"]["traffic_source"]
+    assert f["parity_full_depth"]["f16"]["ids_identical_clips"] == 16 and "value_contract" in f and "config3" in f
+
+
 @pytest.mark.timeout(120)
 def test_bench_refuses_a_rank_count_mismatch():
     r = _run(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0"})     # a launcher gave one rank, the command line says two

@@ -9,7 +9,7 @@
 # otherwise the last 3 lines are echoed.  Everything is appended to OUTFILE (default gpurun_out/ab.txt).
 #
 #   bash tools/ab.sh -n 2 -k value,roofline.avg_step_ms 'THEWHISPER_DECODE_CUS=128 THEWHISPER_DECODE_CUS=160' -- \
-#        python bench.py --steps 5 --no-cpu-baseline --no-pipeline-leg --no-secondary --latency-iters 0
+#        python bench.py --steps 5
 OUT=gpurun_out/ab.txt; REP=1; KEYS=value,ms_per_step,roofline.avg_step_ms
 while getopts "o:n:k:" f; do case $f in o) OUT=$OPTARG;; n) REP=$OPTARG;; k) KEYS=$OPTARG;; *) exit 2;; esac; done
 shift $((OPTIND - 1))

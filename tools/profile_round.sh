@@ -10,10 +10,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# the default line carries every BASELINE configuration since round 3 (other_configs: turbo 30 s x 1, fp8 / bf16 15 s x 16; rtfx)
-python $ROOT/bench.py --steps 20 > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err
+# the --full line carries every BASELINE configuration (other_configs: turbo 30 s x 1, fp8 / bf16 15 s x 16; rtfx)
+python $ROOT/bench.py --full --steps 20 > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err
 if [ -z "$QUICK" ]; then
-python $ROOT/bench.py --model large-v3-turbo --chunk-s 30 --streams 1 --no-cpu-baseline --no-secondary --latency-iters 30 > $OUT/${R}_bench_turbo_30s_b1.json 2>/dev/null
+python $ROOT/bench.py --model large-v3-turbo --chunk-s 30 --streams 1 --full --no-cpu-baseline --no-secondary --latency-iters 30 > $OUT/${R}_bench_turbo_30s_b1.json 2>/dev/null
 fi
 rm -rf /tmp/prof_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o p -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pipeline-leg --no-secondary --latency-iters 0 > $OUT/${R}_bench_profiled_run.json 2>/dev/null

@@ -1,6 +1,6 @@
 """MI355X counterpart of the reference's examples/run_nvidia_asr.py (same flow, `amd` backend).
 
-    python examples/run_amd_asr.py --audio-file speech.wav            # needs a checkpoint + librosa
+    python examples/run_amd_asr.py --audio-file speech.wav            # needs a checkpoint; a PCM WAV at any rate from 8 to 96 kHz
     python examples/run_amd_asr.py --synthetic                        # seeded random weights + synthetic clip (no network)
 """
 import argparse
@@ -41,12 +41,16 @@ if args.synthetic:
     audio = (np.random.default_rng(5).standard_normal(16000 * 25) * 0.1).astype(np.float32)
     generate_kwargs["max_new_tokens"] = 32
 else:
-    from librosa import load, resample
+    from thewhisper_amd.gateway import decode_wav_frames
+    from thewhisper_amd.resample import resample
 
     pipe = ASRPipeline(args.model, chunk_length_s=chunk_length_s, model_size="S", batch_size=16, device="cuda",
                        torch_dtype=torch.bfloat16)
-    audio, sr = load(args.audio_file)
-    audio = resample(audio, orig_sr=sr, target_sr=16000)
+    # the reference loads and resamples with librosa (R:examples/run_nvidia_asr.py:30); here the file's own frames (int16, any
+    # channel count) are converted, down-mixed and resampled on the device by tw_resample
+    with open(args.audio_file, "rb") as f:
+        audio, sr = decode_wav_frames(f.read())
+    audio = resample(audio, sr, 16000)
 
 output = pipe(audio, generate_kwargs=generate_kwargs, chunk_length_s=chunk_length_s - 1, return_timestamps="word")
 print(output)

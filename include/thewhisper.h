@@ -230,6 +230,30 @@ int tw_last_timings(tw_ctx* ctx, float* ms_out5, int32_t* steps_out);
 int tw_vad_energy(int32_t device, const float* pcm_dev, int64_t stream_stride, int32_t B, int32_t n_frames, float* state_dev,
                   float* prob_dev, void* stream);
 
+/* Front end.  Stands where the reference resamples a client's audio to 16 kHz with librosa before its pipeline sees it
+ * (R:thestage_speechkit/streaming/streams.py:103-105, R:examples/run_nvidia_asr.py:30).  NOT a port of librosa / soxr: a rational
+ * polyphase Kaiser-windowed-sinc resampler of this project's own definition (thewhisper_amd/csrc/k_resample.hip), context-free
+ * like tw_vad_energy.  Supported: sr_in, sr_out >= 4000 whose prototype table (2 * 16 * max(L, M) + 1 taps, L / M = sr_out / sr_in
+ * in lowest terms) is at most 1 MiB of float32; sr_in == sr_out is a bit-exact copy (after conversion and down-mix). */
+enum { TW_PCM_F32 = 0, TW_PCM_S16 = 1 };   /* S16: little-endian int16, value / 32767 */
+/* Host only, no GPU needed: L, M, half (prototype half-width in taps) and taps per output of the (sr_in -> sr_out) plan - what a
+ * caller of R:thestage_speechkit/streaming/streams.py:103-105 never sees of librosa's filter.  Any pointer may be NULL. */
+int tw_resample_plan(int32_t sr_in, int32_t sr_out, int32_t* L, int32_t* M, int32_t* half, int32_t* taps_per_output);
+/* Host only: the n = 2*half+1 prototype taps in double, exactly what the device table is rounded from (the filter that replaces
+ * librosa's inside R:thestage_speechkit/streaming/streams.py:103-105). */
+int tw_resample_taps(int32_t sr_in, int32_t sr_out, double* out_host, int32_t n);
+/* Replaces: `librosa.resample(chunk, orig_sr=sr, target_sr=16000)` (R:thestage_speechkit/streaming/streams.py:103-105) and the
+ * int16 / channel handling in front of it, for B rows in ONE launch.  in_dev: [B, in_stride_frames, channels] of in_fmt,
+ * interleaved; the channels of a frame are averaged in float32 before filtering.  Row b holds in_count_host[b] frames, the first
+ * of which is frame in_first_host[b] of its stream; frames outside that window or before frame 0 read as zero.  out_dev:
+ * float32 [B, out_stride]; row b receives output samples out_first_host[b] .. out_first_host[b] + n_out - 1 of its stream
+ * (y[n] = sum_k x[k] h[n M - k L]).  A pure function of its arguments: streaming state (a tail of input, two counters) is the
+ * caller's (thewhisper_amd/resample.py), and a sample's bits do not depend on B or on how the stream was cut.  1 <= B <= 64,
+ * 1 <= channels <= 8.  Asynchronous on `stream`. */
+int tw_resample(int32_t device, const void* in_dev, int32_t in_fmt, int32_t channels, int64_t in_stride_frames,
+                const int64_t* in_first_host, const int32_t* in_count_host, int32_t sr_in, int32_t sr_out,
+                const int64_t* out_first_host, int32_t n_out, float* out_dev, int64_t out_stride, int32_t B, void* stream);
+
 /* Host-side schedule helpers (no reference counterpart: the reference processes one request at a time,
  * R:examples/server.py:22-115).  Streams and events created by the SAME HIP runtime the library and torch use, for the
  * encoder / decoder stage overlap (thewhisper_amd/overlap.py): a stream whose kernels may only run on the compute units

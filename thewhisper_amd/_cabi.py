@@ -16,6 +16,7 @@ TW_F32, TW_BF16, TW_F16 = 0, 1, 2
 TW_BF16_MXFP8 = 3  # context dtype only: bf16 activations, MXFP8 decoder projection weights, activations quantised in registers (W8A8)
 TW_BF16_W8A16 = 4  # context dtype only: MXFP8 decoder projection weights widened to bf16 in registers, bf16 activations
 TW_MAX_ALIGN_HEADS = 32
+TW_PCM_F32, TW_PCM_S16 = 0, 1   # tw_resample input formats
 
 
 class tw_config(C.Structure):
@@ -64,6 +65,11 @@ SYMBOLS = [
     ("tw_get_alignment", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),
     ("tw_last_timings", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     ("tw_vad_energy", C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("tw_resample_plan", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32)]),
+    ("tw_resample_taps", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32]),
+    ("tw_resample", C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
+                              C.c_int32, C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64, C.c_int32, _P]),
     ("tw_stream_create_masked", C.c_int, [C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(_P)]),
     ("tw_stream_destroy", C.c_int, [_P]),
     ("tw_stream_synchronize", C.c_int, [_P]),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "libthewhisper_gfx950.so"
-SOURCES = ["api.hip", "k_gemm.hip", "k_misc.hip", "k_logmel.hip", "k_attn.hip", "k_decode.hip", "k_dtw.hip", "k_vad.hip"]
+SOURCES = ["api.hip", "k_gemm.hip", "k_misc.hip", "k_logmel.hip", "k_attn.hip", "k_decode.hip", "k_dtw.hip", "k_vad.hip", "k_resample.hip"]
 # -amdgpu-kernarg-preload-count: gfx950 hands the leading kernel-argument dwords to every wave in SGPRs (as many as the free user
 # SGPRs allow); the decode kernels order their arguments so that the request addresses need nothing else (k_decode.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result",

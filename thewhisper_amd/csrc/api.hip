@@ -9,9 +9,11 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <set>
 #include <chrono>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace {
@@ -1457,6 +1459,145 @@ int tw_vad_energy(int32_t device, const float* pcm_dev, int64_t stream_stride, i
   DeviceGuard guard(device);
   hipError_t e = launch_vad_energy(pcm_dev, stream_stride, B, n_frames, state_dev, prob_dev, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) { g_create_error = std::string("vad_energy_kernel: ") + hipGetErrorString(e); return TW_EHIP; }
+  return TW_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Resampling front end (k_resample.hip): the plan and the prototype taps are host arithmetic in double, so C-ABI users get
+// them without Python; the float32 table is uploaded once per (device, sr_in, sr_out) and kept for the process.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kResampleZ = 16;               // zero crossings of the sinc kept on each side, in units of F
+constexpr double kResampleBeta = 8.6;        // Kaiser window
+constexpr double kResampleRho = 0.945;       // cut-off as a fraction of the narrower Nyquist
+constexpr long long kResampleMaxTaps = 1 << 18;   // 1 MiB of float32 on the device
+
+struct ResamplePlan { int L, M, half, taps_per_output; };
+
+double bessel_i0(double x) {                 // power series: sum ((x/2)^k / k!)^2
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < 1e-18 * sum) break;
+  }
+  return sum;
+}
+
+int resample_plan(const char* who, int32_t sr_in, int32_t sr_out, ResamplePlan* p) {
+  if (sr_in < 4000 || sr_out < 4000) return fail(nullptr, TW_EINVAL, "%s: sample rates must be >= 4000 Hz (got %d -> %d)", who, sr_in, sr_out);
+  long long a = sr_in, b = sr_out;
+  while (b) { const long long t = a % b; a = b; b = t; }
+  const long long L = sr_out / a, M = sr_in / a, F = std::max(L, M);
+  if (L == 1 && M == 1) { *p = {1, 1, 0, 1}; return TW_OK; }      // same rate: the one-tap table {1}, a bit-exact copy
+  const long long half = kResampleZ * F;
+  if (2 * half + 1 > kResampleMaxTaps)
+    return fail(nullptr, TW_EINVAL, "%s: %d -> %d Hz needs a table of %lld taps (L=%lld M=%lld), more than the supported %lld", who, sr_in,
+                sr_out, 2 * half + 1, L, M, kResampleMaxTaps);
+  *p = {(int)L, (int)M, (int)half, (int)(2 * half / L) + 1};
+  return TW_OK;
+}
+
+void resample_taps(const ResamplePlan& p, double* h) {
+  if (p.half == 0) { h[0] = 1.0; return; }
+  const double F = (double)std::max(p.L, p.M), fc = kResampleRho / F, i0b = bessel_i0(kResampleBeta), pi = 3.14159265358979323846;
+  for (int j = -p.half; j <= p.half; ++j) {
+    const double u = (double)j / (double)p.half, a = pi * fc * (double)j;
+    const double sinc = j == 0 ? 1.0 : std::sin(a) / a;
+    h[j + p.half] = (double)p.L * fc * sinc * bessel_i0(kResampleBeta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b;
+  }
+}
+
+std::mutex g_resample_mu;
+std::map<std::tuple<int, int, int>, float*> g_resample_tables;   // (device, sr_in, sr_out) -> float32 [2 half + 1], device
+
+int resample_table(int device, int32_t sr_in, int32_t sr_out, const ResamplePlan& p, const float** out) {
+  std::lock_guard<std::mutex> lock(g_resample_mu);
+  const auto key = std::make_tuple(device, (int)sr_in, (int)sr_out);
+  auto it = g_resample_tables.find(key);
+  if (it == g_resample_tables.end()) {
+    const size_t n = 2 * (size_t)p.half + 1;
+    std::vector<double> h(n);
+    resample_taps(p, h.data());
+    std::vector<float> hf(h.begin(), h.end());
+    float* d = nullptr;
+    HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float)));
+    hipError_t e = hipMemcpy(d, hf.data(), n * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return fail(nullptr, TW_EHIP, "tw_resample: tap table upload failed: %s", hipGetErrorString(e));
+    }
+    it = g_resample_tables.emplace(key, d).first;
+  }
+  *out = it->second;
+  return TW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tw_resample_plan(int32_t sr_in, int32_t sr_out, int32_t* L, int32_t* M, int32_t* half, int32_t* taps_per_output) {
+  ResamplePlan p;
+  const int rc = resample_plan("tw_resample_plan", sr_in, sr_out, &p);
+  if (rc != TW_OK) return rc;
+  if (L) *L = p.L;
+  if (M) *M = p.M;
+  if (half) *half = p.half;
+  if (taps_per_output) *taps_per_output = p.taps_per_output;
+  return TW_OK;
+}
+
+int tw_resample_taps(int32_t sr_in, int32_t sr_out, double* out_host, int32_t n) {
+  if (!out_host) return fail(nullptr, TW_EINVAL, "tw_resample_taps: null argument");
+  ResamplePlan p;
+  const int rc = resample_plan("tw_resample_taps", sr_in, sr_out, &p);
+  if (rc != TW_OK) return rc;
+  if (n != 2 * p.half + 1) return fail(nullptr, TW_EINVAL, "tw_resample_taps: n=%d, the %d -> %d Hz table has %d taps", n, sr_in, sr_out, 2 * p.half + 1);
+  resample_taps(p, out_host);
+  return TW_OK;
+}
+
+int tw_resample(int32_t device, const void* in_dev, int32_t in_fmt, int32_t channels, int64_t in_stride_frames,
+                const int64_t* in_first_host, const int32_t* in_count_host, int32_t sr_in, int32_t sr_out,
+                const int64_t* out_first_host, int32_t n_out, float* out_dev, int64_t out_stride, int32_t B, void* stream) {
+  if (!in_dev || !in_first_host || !in_count_host || !out_first_host || !out_dev) return fail(nullptr, TW_EINVAL, "tw_resample: null argument");
+  if (in_fmt != TW_PCM_F32 && in_fmt != TW_PCM_S16) return fail(nullptr, TW_EINVAL, "tw_resample: in_fmt %d is not TW_PCM_F32 / TW_PCM_S16", in_fmt);
+  if (B < 1 || B > 64) return fail(nullptr, TW_EINVAL, "tw_resample: B=%d outside [1,64]", B);
+  if (channels < 1 || channels > 8) return fail(nullptr, TW_EINVAL, "tw_resample: channels=%d outside [1,8]", channels);
+  if (n_out < 1) return fail(nullptr, TW_EINVAL, "tw_resample: n_out=%d, nothing to produce", n_out);
+  if (out_stride < n_out || in_stride_frames < 0) return fail(nullptr, TW_EINVAL, "tw_resample: a row stride is shorter than the row");
+  if (reinterpret_cast<uintptr_t>(in_dev) & (in_fmt == TW_PCM_S16 ? 1 : 3)) return fail(nullptr, TW_EINVAL, "tw_resample: in_dev is not aligned to its sample type");
+  ResamplePlan p;
+  int rc = resample_plan("tw_resample", sr_in, sr_out, &p);
+  if (rc != TW_OK) return rc;
+  ResampleArgs a{};
+  for (int b = 0; b < B; ++b) {
+    if (in_count_host[b] < 0 || in_count_host[b] > in_stride_frames || out_first_host[b] < 0 ||
+        in_first_host[b] < -((int64_t)1 << 40) || in_first_host[b] > ((int64_t)1 << 40) || out_first_host[b] > ((int64_t)1 << 40))
+      return fail(nullptr, TW_EINVAL, "tw_resample: row %d: in_count %d (stride %lld frames), in_first %lld, out_first %lld", b,
+                  in_count_host[b], (long long)in_stride_frames, (long long)in_first_host[b], (long long)out_first_host[b]);
+    a.rows.in_first[b] = in_first_host[b];
+    a.rows.in_count[b] = in_count_host[b];
+    a.rows.out_first[b] = out_first_host[b];
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, TW_EHIP, "no HIP device available (the MI355X path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(nullptr, TW_EINVAL, "device %d out of range", device);
+  DeviceGuard guard(device);
+  const float* taps = nullptr;
+  rc = resample_table(device, sr_in, sr_out, p, &taps);
+  if (rc != TW_OK) return rc;
+  a.in = in_dev; a.s16 = in_fmt == TW_PCM_S16; a.channels = channels; a.in_stride_frames = in_stride_frames;
+  a.taps = taps; a.L = p.L; a.M = p.M; a.half = p.half;
+  a.out = out_dev; a.out_stride = out_stride; a.n_out = n_out; a.B = B;
+  hipError_t e = launch_resample(a, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, TW_EHIP, "resample_kernel: %s", hipGetErrorString(e));
   return TW_OK;
 }
 

@@ -374,3 +374,20 @@ hipError_t launch_token_timestamps(const DtwArgs& a, hipStream_t st);
 // 8f-2: energy voice-activity gate, one wavefront per stream, `n_frames` consecutive 512-sample frames each (k_vad.hip)
 hipError_t launch_vad_energy(const float* pcm, long long stream_stride, int B, int n_frames, float* state, float* prob,
                              hipStream_t st);
+
+// Front end: rational polyphase resampler + int16 / multi-channel conversion (k_resample.hip).  Per-row parameters travel by
+// value in the kernel arguments (B <= 64): no host-to-device copy per launch.
+struct ResampleRows {
+  long long in_first[64];    // absolute index of the row's first input frame
+  long long out_first[64];   // absolute index of the row's first output sample
+  int in_count[64];          // frames the row holds
+};
+constexpr int kResampleWindow = 4096;    // floats of LDS for a block's converted input window
+constexpr int kResampleTapsLds = 2048;   // floats of LDS for the whole tap table when L <= 2
+struct ResampleArgs {
+  const void* in; bool s16; int channels; long long in_stride_frames;
+  const float* taps; int L; int M; int half;   // taps: float32 [2 half + 1], device
+  float* out; long long out_stride; int n_out; int B;
+  ResampleRows rows;
+};
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t st);

@@ -21,7 +21,7 @@ import numpy as np
 from .serving import BatchingHub
 from .streaming import AMDWhisperBackend
 
-__all__ = ["create_app", "decode_wav", "words_to_response", "multipart_file", "SessionHost", "HostBusy"]
+__all__ = ["create_app", "decode_wav", "decode_wav_frames", "words_to_response", "multipart_file", "SessionHost", "HostBusy"]
 
 
 def multipart_file(body: bytes, content_type: str, field: str = "file") -> bytes:
@@ -42,15 +42,30 @@ def multipart_file(body: bytes, content_type: str, field: str = "file") -> bytes
     raise ValueError(f"multipart body has no part named '{field}'")
 
 
-def decode_wav(data: bytes) -> "Tuple[np.ndarray, int]":
-    """WAV bytes -> (float32 mono in [-1, 1], sample rate).  Accepts what the reference client sends (16-bit PCM, mono;
-    R:...streaming_pipeline.py:93-112) plus 8/32-bit PCM and multi-channel input (averaged)."""
+def _read_wav(data: bytes):
     try:
         with wave.open(io.BytesIO(data), "rb") as wf:
             ch, width, sr, n = wf.getnchannels(), wf.getsampwidth(), wf.getframerate(), wf.getnframes()
             raw = wf.readframes(n)
     except (wave.Error, EOFError) as e:
         raise ValueError(f"not a PCM WAV file: {e}") from e
+    return raw, ch, width, sr
+
+
+def decode_wav_frames(data: bytes) -> "Tuple[np.ndarray, int]":
+    """WAV bytes -> (what ``tw_resample`` takes, sample rate): 16-bit PCM stays int16 ``[frames, channels]`` - conversion and
+    down-mix then happen on the device (resample.py) - anything else is ``decode_wav``'s float32 mono."""
+    raw, ch, width, sr = _read_wav(data)
+    if width == 2 and 1 <= ch <= 8:
+        x = np.frombuffer(raw, dtype="<i2")
+        return np.ascontiguousarray(x[: (len(x) // ch) * ch].reshape(-1, ch)), int(sr)
+    return decode_wav(data)
+
+
+def decode_wav(data: bytes) -> "Tuple[np.ndarray, int]":
+    """WAV bytes -> (float32 mono in [-1, 1], sample rate).  Accepts what the reference client sends (16-bit PCM, mono;
+    R:...streaming_pipeline.py:93-112) plus 8/32-bit PCM and multi-channel input (averaged)."""
+    raw, ch, width, sr = _read_wav(data)
     if width == 2:
         x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32767.0  # inverse of the client's x * 32767 (:101)
     elif width == 1:
@@ -98,7 +113,7 @@ class SessionHost:
     the same methods over N such hosts in N processes (one per MI355X)."""
 
     def __init__(self, backend: Union[BatchingHub, AMDWhisperBackend], scheduler_factory=None, max_sessions: int = 1024,
-                 session_ttl_s: float = 900.0, vad=None):
+                 session_ttl_s: float = 900.0, vad=None, resample: bool = False, resample_kernel=None, resample_device: int = 0):
         import threading
 
         self.hub = backend if isinstance(backend, BatchingHub) else None
@@ -108,6 +123,11 @@ class SessionHost:
         self.max_sessions = int(max_sessions)
         self.session_ttl_s = float(session_ttl_s)
         self.vad = vad                      # thewhisper_amd.vad.VadService or None (sessions then run with use_vad=False)
+        # opt-in: sessions may declare another sample rate / encoding / channel count; their chunks then pass through a
+        # StreamResampler (resample.py) on their way to the scheduler.  ``resample_kernel``: the tests' stand-in for tw_resample
+        self.resample = bool(resample)
+        self._resample_kernel = resample_kernel
+        self._resample_device = int(resample_device)
         self.sessions: Dict[str, Dict[str, Any]] = {}
         self._creating = 0                  # sessions being built outside the table lock: they count against max_sessions
         self._lock = threading.Lock()
@@ -134,13 +154,29 @@ class SessionHost:
             if vs is not None:
                 vs.close()
 
-    def create(self, session_id: Optional[str] = None) -> str:
+    def _session_resampler(self, sample_rate, encoding, channels):
+        """The ``StreamResampler`` of a session that declared ``sample_rate`` / ``encoding`` / ``channels`` (None = the engine's),
+        or None for 16 kHz mono float32.  ``ValueError`` (HTTP 400) for what this host does not take."""
+        from .resample import StreamResampler, normalise_encoding
+
+        sr = self.sample_rate if sample_rate is None else int(sample_rate)
+        fmt = normalise_encoding("f32le" if encoding is None else encoding)
+        ch = 1 if channels is None else int(channels)
+        if sr == self.sample_rate and fmt == "f32" and ch == 1:
+            return None
+        if not self.resample:
+            raise ValueError(f"expected {self.sample_rate} Hz mono float32 audio (this gateway runs without --resample)")
+        return StreamResampler(sr, self.sample_rate, channels=ch, fmt=fmt, kernel=self._resample_kernel, device=self._resample_device)
+
+    def create(self, session_id: Optional[str] = None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+               channels: Optional[int] = None) -> str:
         import base64
         import os
         import threading
         import time
 
         sid = session_id or base64.urlsafe_b64encode(os.urandom(16)).decode("ascii")     # as R:examples/server.py:122
+        resampler = self._session_resampler(sample_rate, encoding, channels)
         now = time.monotonic()
         with self._lock:
             dead = self._evict_idle(now)
@@ -165,7 +201,7 @@ class SessionHost:
                 except BaseException:
                     vs.close()          # the detector slot must not outlive a session that was never created
                     raise
-            sess = {"scheduler": sched, "lock": threading.Lock(), "last_used": now, "vad": vs, "closed": False}
+            sess = {"scheduler": sched, "lock": threading.Lock(), "last_used": now, "vad": vs, "closed": False, "resampler": resampler}
         finally:
             with self._lock:
                 self._creating -= 1
@@ -189,7 +225,13 @@ class SessionHost:
         with s["lock"]:
             if s["closed"]:
                 raise KeyError(sid)
-            sched, vs = s["scheduler"], s["vad"]
+            sched, vs, rs = s["scheduler"], s["vad"], s.get("resampler")
+            if isinstance(audio_np, (bytes, bytearray)) or getattr(audio_np, "dtype", None) == np.uint8:
+                # raw bytes (a gateway with resampling on does not know the session's encoding): the session's sample type
+                audio_np = np.frombuffer(bytes(audio_np) if isinstance(audio_np, bytearray) else audio_np,
+                                         dtype=np.dtype("<i2") if rs is not None and rs.fmt == "s16" else np.float32)
+            if rs is not None:
+                audio_np = rs.push(audio_np)     # 16 kHz mono float32 from here on: the detector and the scheduler see nothing else
             if vs is not None and getattr(sched, "use_vad", False):
                 # the reference evaluates its detector frame by frame on (left-over samples + this chunk)
                 # (R:...streaming_pipeline.py:589-622): ask for all of those frames in ONE request, which the VadService merges
@@ -214,6 +256,8 @@ class SessionHost:
                 s["scheduler"].clear()   # per-session state: clearing is safe here (the reference's shared pipeline leaves it commented out)
             if s["vad"] is not None:
                 s["vad"].reset_states()
+            if s.get("resampler") is not None:
+                s["resampler"].reset()
 
     def end(self, sid: str) -> None:
         with self._lock:
@@ -257,12 +301,20 @@ class _LockedBackend:
 
 def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Optional[str] = None, path: str = "/transcribe",
                scheduler_factory=None, max_sessions: int = 1024, session_ttl_s: float = 900.0, vad=None,
-               host_threads: Optional[int] = None):
+               host_threads: Optional[int] = None, resample: bool = False, resample_kernel=None):
     """FastAPI application.  ``backend``: a ``BatchingHub`` (concurrent requests share passes), a bare ``AMDWhisperBackend``, a
     ready ``SessionHost`` or a ``thewhisper_amd.node.NodeRouter`` (one host process per GPU).  ``auth_token``: when set,
     requests must carry ``Authorization: Bearer <token>``.  ``lang_id``: when set, a request's ``X-Lang-Id`` must equal it
     (the engine is built for one language prompt).  ``vad``: a ``thewhisper_amd.vad.VadService`` - sessions are then gated
     like the reference's default ``use_vad=True`` (energy rule, not silero - vad.py), all sessions' frames in shared launches.
+
+    ``resample`` (off by default; ``--resample``): audio at other rates, as int16 and with several channels is converted on the
+    device (resample.py) instead of being refused - ``/transcribe`` takes a WAV at any supported rate (400 only for an
+    unsupported one), and ``POST /session/create/?sample_rate=48000&encoding=s16le&channels=2`` /
+    ``/ws/stream?sample_rate=...&encoding=...&channels=...`` create a session whose chunks (``add_chunk``, binary WebSocket
+    messages) are raw interleaved samples of that format, passed through the session's ``StreamResampler`` before the
+    detector and the scheduler.  Sessions at 16 kHz mono float32 create no resampler.  With a ready host the host's own
+    ``resample`` setting holds.
 
     Two surfaces:
       * ``POST /transcribe`` - stateless, the wire format of the reference's remote backend (module docstring);
@@ -293,10 +345,36 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
 
     if hasattr(backend, "create") and hasattr(backend, "add_chunk"):
         host = backend                       # SessionHost or NodeRouter
+        resample = bool(getattr(host, "resample", False))
     else:
-        host = SessionHost(backend, scheduler_factory=scheduler_factory, max_sessions=max_sessions, session_ttl_s=session_ttl_s, vad=vad)
+        host = SessionHost(backend, scheduler_factory=scheduler_factory, max_sessions=max_sessions, session_ttl_s=session_ttl_s, vad=vad,
+                           resample=resample, resample_kernel=resample_kernel)
     app.state.host = host
     sample_rate = host.sample_rate
+
+    def session_format(sample_rate_q, encoding, channels):
+        """The three session parameters of a create request -> arguments of ``host.create`` (none for a plain session, so a host
+        without them in its signature keeps working); 400 for what the host will not take."""
+        if sample_rate_q is None and encoding is None and channels is None:
+            return ()
+        if not resample:
+            raise HTTPException(status_code=400, detail=f"expected {sample_rate} Hz mono float32 audio (this gateway runs without --resample)")
+        try:
+            from .resample import normalise_encoding, plan
+
+            sr, ch = sample_rate if sample_rate_q is None else int(sample_rate_q), 1 if channels is None else int(channels)
+            plan(sr, sample_rate)
+            normalise_encoding("f32le" if encoding is None else encoding)
+            if not 1 <= ch <= 8:
+                raise ValueError(f"{ch} channels: 1 to 8 are supported")
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e)) from e
+        return (None, sr, encoding, ch)
+
+    def chunk_array(data: bytes) -> np.ndarray:
+        """A chunk's bytes as the host wants them: float32 as ever; raw bytes when sessions may have another sample type (the
+        host views them as its session's)."""
+        return np.frombuffer(data, dtype=np.uint8) if resample else np.frombuffer(data, dtype=np.float32)
 
     def check_auth(authorization: Optional[str]):
         if auth_token and not hmac.compare_digest((authorization or "").encode(), f"Bearer {auth_token}".encode()):
@@ -323,10 +401,12 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
             raise HTTPException(status_code=500, detail=str(e)) from e
 
     @app.post("/session/create/")
-    async def session_create(authorization: Optional[str] = Header(default=None)):
+    async def session_create(authorization: Optional[str] = Header(default=None), sample_rate: Optional[int] = None,
+                             encoding: Optional[str] = None, channels: Optional[int] = None):
         check_auth(authorization)
+        fmt = session_format(sample_rate, encoding, channels)
         try:
-            return {"session_id": await run_in_threadpool(host.create)}
+            return {"session_id": await run_in_threadpool(host.create, *fmt)}
         except HostBusy as e:
             raise HTTPException(status_code=503, detail=str(e), headers={"Retry-After": "1"}) from e
         except RuntimeError as e:
@@ -345,7 +425,7 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
         """``audio_data``: base64 of float32 PCM, a query parameter exactly as in the reference (R:examples/server.py:135-144)."""
         check_auth(authorization)
         try:
-            audio_np = np.frombuffer(base64.b64decode(audio_data), dtype=np.float32)
+            audio_np = chunk_array(base64.b64decode(audio_data))
         except Exception as e:  # noqa: BLE001
             raise HTTPException(status_code=500, detail=str(e)) from e
         await guarded(host.add_chunk, session_id, audio_np)
@@ -376,9 +456,14 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
         try:
             wav = body if ctype.startswith("audio/") else multipart_file(body, ctype)
             audio, sr = decode_wav(wav)
+            if resample and sr != sample_rate:
+                from .resample import plan
+
+                plan(sr, sample_rate)                    # ValueError (400) for a rate the library does not support
+                audio, sr = decode_wav_frames(wav)       # int16 frames as they are: converted, down-mixed and resampled on the device
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e)) from e
-        if sr != sample_rate:
+        if sr != sample_rate and not resample:
             raise HTTPException(status_code=400, detail=f"expected {sample_rate} Hz audio, got {sr} Hz")
         if len(audio) == 0:
             return words_to_response([], model_name)
@@ -390,13 +475,19 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
         """One streaming session over a WebSocket (SURVEY.md section 8f rank 1 names the surface; the reference's server imports
         ``WebSocket`` without using it, R:examples/server.py:1).  Binary message = float32 PCM chunk at 16 kHz: it is added to
         the session (``add_chunk``) and processed (``process``); every message is answered with the JSON of the ``/process``
-        route.  Text message "clear" / "end" as the routes.  ``?token=`` carries the bearer token.  Closing ends the session."""
+        route.  With resampling on, ``?sample_rate=48000&encoding=s16le&channels=2`` declares what the binary messages hold.  Text message "clear" / "end" as the routes.  ``?token=`` carries the bearer token.  Closing ends the session."""
         if auth_token and not hmac.compare_digest((ws.query_params.get("token") or "").encode(), auth_token.encode()):
             await ws.close(code=4401)
             return
         await ws.accept()
         try:
-            sid = await run_in_threadpool(host.create)
+            q = ws.query_params
+            fmt = session_format(q.get("sample_rate"), q.get("encoding"), q.get("channels"))
+            sid = await run_in_threadpool(host.create, *fmt)
+        except HTTPException as e:
+            await ws.send_json({"error": e.detail})
+            await ws.close(code=1008)
+            return
         except Exception as e:  # noqa: BLE001
             await ws.send_json({"error": str(e)})
             await ws.close(code=1013)
@@ -407,7 +498,7 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
                 if msg["type"] == "websocket.disconnect":
                     break
                 if msg.get("bytes") is not None:
-                    audio_np = np.frombuffer(msg["bytes"], dtype=np.float32)
+                    audio_np = chunk_array(msg["bytes"])
                     await guarded(host.add_chunk, sid, audio_np)
                     words, uncommited_words = await guarded(host.process, sid)
                     await ws.send_json({"words": words, "uncommited_words": uncommited_words})
@@ -448,6 +539,8 @@ def build_host(argv: Optional[List[str]] = None):
     ap.add_argument("--max-batch", type=int, default=16)
     ap.add_argument("--gpus", type=int, default=1, help="serving processes, one per MI355X (sessions sticky by index %% gpus; thewhisper_amd/node.py)")
     ap.add_argument("--vad", action="store_true", help="gate sessions with the on-device energy VAD (the reference's default use_vad=True; vad.py)")
+    ap.add_argument("--resample", action="store_true", help="accept audio at other sample rates (8-96 kHz), as int16 and with several channels: "
+                         "converted to 16 kHz mono float32 on the device (resample.py); sessions declare sample_rate / encoding / channels")
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--auth-token", default="")
@@ -468,7 +561,7 @@ def build_host(argv: Optional[List[str]] = None):
 
         host = NodeRouter(args.gpus, "thewhisper_amd.node:default_host_factory",
                           dict(model=args.model, chunk_length_s=args.chunk_length_s, max_batch=args.max_batch, language=args.language,
-                               use_vad=args.vad, torch_dtype=args.dtype, prefetch_cus=args.prefetch_cus))
+                               use_vad=args.vad, torch_dtype=args.dtype, prefetch_cus=args.prefetch_cus, resample=args.resample))
     else:
         backend = AMDWhisperBackend(args.model, chunk_length_s=args.chunk_length_s, language=args.language, batch_size=args.max_batch,
                                     torch_dtype=dtype)
@@ -477,7 +570,7 @@ def build_host(argv: Optional[List[str]] = None):
             from .vad import VadService
 
             vad = VadService(max_streams=1024)
-        host = SessionHost(BatchingHub(backend, max_batch=args.max_batch, prefetch_cus=args.prefetch_cus), vad=vad)
+        host = SessionHost(BatchingHub(backend, max_batch=args.max_batch, prefetch_cus=args.prefetch_cus), vad=vad, resample=args.resample)
     return host, args
 
 

@@ -44,7 +44,7 @@ def worker_main(rank: int, world: int, conn, host_factory: str, factory_kwargs: 
     os.environ["THEWHISPER_RANK"] = str(rank)
     try:
         host = _resolve(host_factory)(rank=rank, world=world, **factory_kwargs)
-        conn.send((0, True, {"rank": rank, "sample_rate": host.sample_rate}))
+        conn.send((0, True, {"rank": rank, "sample_rate": host.sample_rate, "resample": bool(getattr(host, "resample", False))}))
     except BaseException as e:  # noqa: BLE001
         conn.send((0, False, f"worker {rank} failed to start: {e!r}"))
         return
@@ -174,6 +174,7 @@ class NodeRouter:
         self.workers = [_Worker(ctx, r, world, host_factory, dict(factory_kwargs or {})) for r in range(world)]
         hellos = [w.hello.result(timeout=start_timeout_s) for w in self.workers]
         self.sample_rate = hellos[0]["sample_rate"]
+        self.resample = bool(hellos[0].get("resample", False))     # the workers' hosts convert other rates / encodings (gateway.py)
         self._ids = itertools.count(1)
         self._id_lock = threading.Lock()
         self._session_rank: Dict[str, int] = {}
@@ -281,12 +282,15 @@ class NodeRouter:
         return r
 
     # -- SessionHost interface -------------------------------------------------------------------------
-    def create(self) -> str:
+    def create(self, session_id: Optional[str] = None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+               channels: Optional[int] = None) -> str:
+        """``sample_rate`` / ``encoding`` / ``channels``: what the session's chunks hold, forwarded to the worker's host as they
+        are (its ``StreamResampler`` lives next to its scheduler)."""
         import base64
 
         from .gateway import HostBusy
 
-        sid = base64.urlsafe_b64encode(os.urandom(16)).decode("ascii")
+        sid = session_id or base64.urlsafe_b64encode(os.urandom(16)).decode("ascii")
         with self._lock:
             rank = self._created % self.world          # dist.shard_streams: stream_id % world
             self._created += 1
@@ -295,7 +299,8 @@ class NodeRouter:
             if not alive:
                 raise HostBusy("no serving process is alive")
             rank = alive[rank % len(alive)]
-        self.call(rank, "create", sid)
+        fmt = () if sample_rate is None and encoding is None and channels is None else (sample_rate, encoding, channels)
+        self.call(rank, "create", sid, *fmt)
         with self._lock:
             self._session_rank[sid] = rank
         return sid
@@ -359,7 +364,7 @@ class NodeRouter:
 
 
 def default_host_factory(rank: int, world: int, model: str, chunk_length_s: int = 10, max_batch: int = 16, language: str = "en",
-                         use_vad: bool = False, torch_dtype: Optional[str] = None, prefetch_cus: int = 0, **_):  # pragma: no cover - needs weights and GPUs
+                         use_vad: bool = False, torch_dtype: Optional[str] = None, prefetch_cus: int = 0, resample: bool = False, **_):  # pragma: no cover - needs weights and GPUs
     """What ``python -m thewhisper_amd.gateway --gpus N`` runs in every worker: the backend of GPU ``rank`` behind a hub."""
     os.environ["THEWHISPER_DEVICE"] = f"cuda:{rank}"
     from .gateway import SessionHost
@@ -375,4 +380,4 @@ def default_host_factory(rank: int, world: int, model: str, chunk_length_s: int 
         from .vad import VadService
 
         vad = VadService(max_streams=1024, device=rank)
-    return SessionHost(BatchingHub(backend, max_batch=max_batch, prefetch_cus=prefetch_cus), vad=vad)
+    return SessionHost(BatchingHub(backend, max_batch=max_batch, prefetch_cus=prefetch_cus), vad=vad, resample=resample, resample_device=rank)

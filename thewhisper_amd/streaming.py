@@ -39,6 +39,7 @@ class AMDWhisperBackend:
         reuse_committed_prefix: bool = False,
         reuse_margin_s: float = 1.0,
         draft_previous_tick: Optional[bool] = None,
+        resample_kernel=None,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -95,11 +96,24 @@ class AMDWhisperBackend:
                             "verify_launches": 0}
         self._reuse_codec = None      # JobCodec (learned plan), built on the first reuse-enabled call
         self._last = None             # what the previous call left: start time, samples, first-iteration tokens + timestamps
+        self._resample_kernel = resample_kernel   # tests: the numpy restatement in place of tw_resample (resample.py)
+
+    def to_engine_rate(self, audio, sample_rate: int):
+        """``(audio, sample_rate)`` as the engine wants it: a buffer at another rate (or int16 / multi-channel) goes through
+        ``tw_resample`` first (resample.py; the reference does this with librosa before its backend is called,
+        R:thestage_speechkit/streaming/streams.py:103-105).  16 kHz buffers pass untouched.  A buffer that grew is resampled from
+        its first frame again, so the previous result is a prefix of the new one up to the filter's reach: drafts keep matching."""
+        if int(sample_rate) == self.sample_rate:
+            return audio, self.sample_rate
+        from .resample import resample
+
+        return resample(audio, int(sample_rate), self.sample_rate, kernel=self._resample_kernel), self.sample_rate
 
     def _generate_kwargs(self) -> Dict[str, Any]:
         return {"use_cache": True, "num_beams": 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
 
     def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
+        audio, sample_rate = self.to_engine_rate(audio, sample_rate)
         if self.reuse_committed_prefix or self.draft_previous_tick:
             words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate))
             if words is not None:
@@ -201,6 +215,7 @@ class AMDWhisperBackend:
     def transcribe_many(self, requests, batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """Several streams' rolling buffers in ONE pipeline call: [(audio, buffer_start_time, sample_rate), ...].
         HF collates the chunks of different buffers into batched engine calls; per-stream results are unchanged."""
+        requests = [(self.to_engine_rate(a, sr)[0], t0, self.sample_rate) for a, t0, sr in requests]
         audios = [np.asarray(a) for a, _, _ in requests]
         kw = {} if batch_size is None else {"batch_size": int(batch_size)}
         results = self.asr_pipeline(
@@ -302,6 +317,7 @@ class JobCodec:
         """Stage 1 (HF:pipelines/automatic_speech_recognition.py:346-482 via ``pipe.preprocess``)."""
         from .shortform import ChunkWork
 
+        audio, sample_rate = self.backend.to_engine_rate(audio, sample_rate)
         audio = np.asarray(audio)
         works, meta = [], []
         for item in self.pipe.preprocess(audio, **self.pre):

@@ -203,6 +203,37 @@ int tw_generate_greedy(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */
 int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds);
 
+/* Token log-probabilities and the no-speech probability of FINISHED sequences, by a teacher-forced re-scoring pass.  Replaces: the
+ * `scores` HF's generate keeps per step and WhisperGenerationMixin._retrieve_avg_logprobs reduces
+ * (HF:models/whisper/generation_whisper.py:1957-1974: log_softmax of the PROCESSED scores, gathered at the chosen tokens, summed and divided
+ * by length + 1), and WhisperNoSpeechDetection (HF:generation/logits_process.py:2050-2112).  The greedy loop keeps no logits; this call runs
+ * positions 0 .. seq_len-2 of ids_host through the decoder again in launches of up to 64 rows (streams x consecutive positions, 16 rows in
+ * TW_BF16_MXFP8 contexts) whose logits are bit for bit the one-position step's, and reduces every row on the device.
+ *   ids_host: int32 [B, ld], the first seq_len of every row are used (e.g. the out_ids of tw_generate_greedy, ld = max_length,
+ *   seq_len = out_len); n_prompt = the begin index of the generation: n_prompt < seq_len <= target_positions, ld >= seq_len.
+ *   out[b, p], n_prompt <= p < seq_len, is the natural-log probability of ids[b, p] given ids[b, :p]:
+ *     out_logprob_raw_host  softmax of the logits as the model produced them;
+ *     out_logprob_host      softmax of the logits after the processors `opts` describes, applied for the history ids[b, :p] exactly as
+ *                           tw_generate_greedy applies them (suppress lists, begin-suppress at p = n_prompt, the min_new_tokens <eos>
+ *                           mask, the timestamp pairing / monotonic / initial rules, "timestamp mass beats every text token");
+ *                           -inf where ids[b, p] itself is masked.  This is the number HF averages into avg_logprob.
+ *   Entries with p < n_prompt are 0.0f, and so are the entries behind a row's first opts->eos_id at p >= n_prompt (the padding; the <eos>
+ *   itself is scored).  Both are float32 [B, seq_len] (row stride seq_len) and may be NULL.
+ *   Of `opts` only eos_id, pad_id, min_new_tokens and the processor fields (timestamps, no_timestamps_id, max_initial_timestamp_index, the
+ *   two suppress lists) are read; n_forced, n_draft, want_alignment and max_* are ignored.  opts = NULL: raw numbers only
+ *   (out_logprob_host must be NULL) and no <eos> is known, so nothing counts as padding.
+ *   no_speech_id >= 0: out_no_speech_host[b] (float32 [B], may be NULL) = softmax(raw logits of position no_speech_pos)[no_speech_id],
+ *   0 <= no_speech_pos < seq_len - 1; no_speech_id < 0: off, out_no_speech_host is not written.
+ * Deviation: HF reads the no-speech probability from a SECOND model call on the decoder inputs
+ * (:2094-2110, logits[:, 0] when the prompt is longer than one token); here it is read from the teacher-forced pass at the position
+ * the caller names - position 0 sees the same first token, and the decoder is causal, so it is the same distribution.
+ * Requires tw_cross_kv for B slots (else TW_ESTATE).  Overwrites the self-attention caches, the decoder position and the logits;
+ * leaves alone the alignment rows, tw_last_timings, tw_last_draft, the captured step graphs and everything the next
+ * tw_generate_greedy depends on: tw_token_timestamps may be called before or after it.  Synchronises the stream once, at the end. */
+int tw_score_tokens(tw_ctx* ctx, int32_t B, const int32_t* ids_host, int32_t ld, int32_t seq_len, int32_t n_prompt,
+                    const tw_greedy_opts* opts, int32_t no_speech_id, int32_t no_speech_pos, float* out_logprob_host,
+                    float* out_logprob_raw_host, float* out_no_speech_host, void* stream);
+
 /* A11.  Replaces: _extract_token_timestamps + _median_filter + _dynamic_time_warping
  * (HF:models/whisper/generation_whisper.py:241-381, :43-61, :64-115) on the alignment rows recorded by the
  * last tw_generate_greedy(want_alignment=1).  num_frames_host[b] = valid mel frames: the time columns of row b are

@@ -103,6 +103,14 @@ struct tw_ctx {
   int* h_verify = nullptr;       // pinned: [2 + 64] read back | [1] reset value
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
   size_t row_ids_cap = 0;
+  // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
+  // (or its captured step graphs) reads is touched
+  int* score_seq = nullptr;            // [Bmax][P]
+  int *score_bsup = nullptr, *score_sup = nullptr;   // [64], [1024]
+  unsigned* score_bits = nullptr;      // [(V+31)/32]
+  ScorePartial* score_parts = nullptr; // [64][32]
+  float* score_out = nullptr;          // masked [Bmax][P] | raw [Bmax][P] | no-speech [Bmax]
+  float* h_score = nullptr;            // pinned, the same layout
   int row_cap = 0;          // rows the per-token activation buffers hold (>= max_batch; 64 for the prefill launches)
   int* h_stage = nullptr;   // pinned staging of tw_generate_greedy: token table [Bmax][P] (up and down) | 3 x [Bmax] | suppress lists | DecState
   size_t h_stage_ints = 0;
@@ -244,6 +252,7 @@ int tw_destroy(tw_ctx* c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_rows) (void)hipHostFree(c->h_rows);
   if (c->h_verify) (void)hipHostFree(c->h_verify);
+  if (c->h_score) (void)hipHostFree(c->h_score);
   for (int i = 0; i < 5; ++i) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
@@ -466,6 +475,11 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CALLOC(c->begin_suppress_dev, 64 * 4, true); CALLOC(c->suppress_dev, 1024 * 4, true);
   CALLOC(c->suppress_bits, ((V + 31) / 32 + 2048) * 4, true);
   CALLOC(c->sampler_partials, 64 * 32 * sizeof(SamplerPartial), true);
+  CALLOC(c->score_seq, B * P * 4, true); CALLOC(c->score_bsup, 64 * 4, true); CALLOC(c->score_sup, 1024 * 4, true);
+  CALLOC(c->score_bits, ((V + 31) / 32 + 2048) * 4, true);
+  CALLOC(c->score_parts, 64 * 32 * sizeof(ScorePartial), true);
+  CALLOC(c->score_out, (2 * B * P + B) * 4, true);
+  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_score), sizeof(float) * (2 * B * P + B), hipHostMallocDefault));
   // ---- dtw workspace ----
   CALLOC(c->zbuf, B * Ha * P * T * 4, false);
   CALLOC(c->mat, B * P * T * 4, false);
@@ -915,7 +929,10 @@ bool getenv_off_fuse() {
 // embed = false: the input rows are already in place (the sampler's last launch of the previous step wrote them, SamplerArgs::x_next)
 // rows_logits: rows mode WITH the tied-logits projection of every row (draft-and-verify: verify_round) - the same launch the step uses,
 // so a row's logits are bit for bit what the one-position step would have produced (k_decode.hip: one reduction order for every B)
-int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = nullptr, bool embed = true, bool rows_logits = false) {
+// record_alignment = false: the cross attention is launched with Ha = 0 and no slot table, so the alignment rows an earlier
+// tw_generate_greedy recorded stay as they are (tw_score_tokens); its output does not depend on it
+int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = nullptr, bool embed = true, bool rows_logits = false,
+                bool record_alignment = true) {
   const int d = c->d, H = c->H, F = c->ffn, T = c->T, P = c->P, dt = c->dtype;
   const size_t e = c->esz;
   if (embed) HIPCHK(c, launch_embed(dt, rs > 0 ? ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
@@ -958,7 +975,8 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = n
       HIPCHK(c, launch_gemv(dt, a, st));
     }
     HIPCHK(c, launch_dec_cross_attn(dt, c->dq, fq, at(c->cross_k, cross_layer * l, c->w8 ? 1 : e), at(c->cross_v, cross_layer * l, c->w8 ? 1 : e),
-                                    c->datt, B, H, T, c->Tp, c->Ha > 0 ? c->align_slot + (size_t)l * H : nullptr, c->align, c->Ha,
+                                    c->datt, B, H, T, c->Tp, (c->Ha > 0 && record_alignment) ? c->align_slot + (size_t)l * H : nullptr, c->align,
+                                    record_alignment ? c->Ha : 0,
                                     P, c->stt, c->w8 ? c->cross_ksc + (size_t)c->Bmax * H * c->Tp * l : nullptr,
                                     c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, st));
     {
@@ -1365,6 +1383,115 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   *out_len = L;
   c->last_seq_len = L;
   c->last_n_prompt = n_prompt;
+  return TW_OK;
+}
+
+int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_t seq_len, int32_t n_prompt, const tw_greedy_opts* o,
+                    int32_t no_speech_id, int32_t no_speech_pos, float* out_logprob, float* out_logprob_raw, float* out_no_speech,
+                    void* stream) {
+  if (!c || !ids) return fail(c, TW_EINVAL, "tw_score_tokens: null argument");
+  TW_ON_DEVICE(c);
+  const int P = c->P;
+  const int cap = std::min((c->w8 && !c->a16) ? 16 : 64, c->row_cap);   // W8A8 quantises activations per group of 16 rows: one group per launch
+  if (B < 1 || B > cap) return fail(c, TW_EINVAL, "tw_score_tokens: %d streams, a launch has %d rows", B, cap);
+  if (n_prompt < 1 || seq_len <= n_prompt || seq_len > P) return fail(c, TW_EINVAL, "tw_score_tokens: seq_len %d outside (n_prompt %d, %d]", seq_len, n_prompt, P);
+  if (ld < seq_len) return fail(c, TW_EINVAL, "tw_score_tokens: ld %d < seq_len %d", ld, seq_len);
+  const int n_pos = seq_len - 1;    // position p yields the score of the token at p + 1
+  if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "tw_score_tokens: %d positions x %d streams exceed the row table", n_pos, B);
+  if (!o && out_logprob) return fail(c, TW_EINVAL, "tw_score_tokens: the masked log-probabilities need the processors' options");
+  if (o) {
+    if (o->n_begin_suppress < 0 || o->n_begin_suppress > 64 || o->n_suppress < 0 || o->n_suppress > 1024 ||
+        (o->n_begin_suppress > 0 && !o->begin_suppress) || (o->n_suppress > 0 && !o->suppress))
+      return fail(c, TW_EINVAL, "suppress lists too long");
+    if (o->pad_id < 0 || o->pad_id >= c->V || o->eos_id < 0 || o->eos_id >= c->V)
+      return fail(c, TW_EINVAL, "pad_id %d / eos_id %d outside the vocabulary", o->pad_id, o->eos_id);
+  }
+  if (no_speech_id >= c->V) return fail(c, TW_EINVAL, "tw_score_tokens: no_speech_id %d outside the vocabulary", no_speech_id);
+  if (no_speech_id >= 0 && (no_speech_pos < 0 || no_speech_pos >= seq_len - 1))
+    return fail(c, TW_EINVAL, "tw_score_tokens: no_speech_pos %d outside [0, %d)", no_speech_pos, seq_len - 1);
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < seq_len; ++i) {
+      const int t = ids[(size_t)b * ld + i];
+      if (t < 0 || t >= c->V) return fail(c, TW_EINVAL, "tw_score_tokens: token %d out of range", t);
+    }
+  if (B > c->cross_B) return fail(c, TW_ESTATE, "tw_score_tokens: B=%d but cross K/V holds %d clips", B, c->cross_B);
+  hipStream_t st = pick_stream(c, stream);
+
+  // ---- staging (pinned; not touched again before the synchronisation at the end of this call) ----
+  int* hseq = c->h_stage;                                       // [B][P]
+  int* bsup = hseq + (size_t)c->Bmax * P + 3 * (size_t)c->Bmax; // [64]
+  int* sup = bsup + 64;                                         // [1024]
+  int* h = c->h_rows;                                           // position-major token table
+  int* hl = c->h_rows + c->row_ids_cap;                         // ... and the last timestamp token among the tokens sampled so far
+  const int ts_begin = (o && o->timestamps) ? o->no_timestamps_id + 1 : c->V;
+  for (int b = 0; b < B; ++b) {
+    int lt = -1;
+    for (int i = 0; i < P; ++i) hseq[(size_t)b * P + i] = i < seq_len ? ids[(size_t)b * ld + i] : 0;
+    for (int p = 0; p < n_pos; ++p) {
+      const int t = ids[(size_t)b * ld + p];
+      if (p >= n_prompt && t >= ts_begin) lt = t;
+      h[(size_t)p * B + b] = t;
+      hl[(size_t)p * B + b] = lt;
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->score_seq, hseq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->row_ids, h, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->row_lastts, hl, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  const int n_bsup = o ? o->n_begin_suppress : 0, n_sup = o ? o->n_suppress : 0;
+  if (n_bsup > 0) {
+    memcpy(bsup, o->begin_suppress, sizeof(int) * n_bsup);
+    HIPCHK(c, hipMemcpyAsync(c->score_bsup, bsup, sizeof(int) * n_bsup, hipMemcpyHostToDevice, st));
+  }
+  if (n_sup > 0) {
+    memcpy(sup, o->suppress, sizeof(int) * n_sup);
+    HIPCHK(c, hipMemcpyAsync(c->score_sup, sup, sizeof(int) * n_sup, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, launch_suppress_bitmap(c->score_sup, n_sup, c->score_bits, c->V, st));
+  int r = reset_state(c, n_prompt, st);     // device position 0, begin index n_prompt
+  if (r != TW_OK) return r;
+
+  ScoreArgs a{};
+  a.s.logits = c->logits; a.s.V = c->V; a.s.seq = c->score_seq; a.s.seq_ld = P; a.s.stt = c->stt;
+  a.s.begin_suppress = c->score_bsup; a.s.n_begin_suppress = n_bsup; a.s.suppress_bits = c->score_bits;
+  a.s.max_initial_ts = -1;
+  if (o) {   // (NULL: nothing is masked and the masked numbers, equal to the raw ones, are not handed out)
+    a.s.eos = o->eos_id; a.s.pad = o->pad_id; a.s.min_new = o->min_new_tokens; a.s.timestamps = o->timestamps;
+    a.s.no_ts_id = o->no_timestamps_id; a.s.max_initial_ts = o->max_initial_timestamp_index;
+  }
+  const size_t plane = (size_t)c->Bmax * P;
+  a.parts = c->score_parts; a.out_masked = c->score_out; a.out_raw = c->score_out + plane; a.out_ld = P;
+  a.ns_id = no_speech_id >= 0 ? no_speech_id : -1; a.ns_pos = no_speech_pos; a.out_ns = c->score_out + 2 * plane;
+
+  // ---- positions 0 .. seq_len-2 in rows-mode launches with logits (B streams x L consecutive positions), each scored at once ----
+  const int key_bound_before = c->dec_key_bound;
+  const int L = std::max(1, cap / B);
+  for (int p0 = 0; p0 < n_pos; p0 += L) {
+    const int l = std::min(L, n_pos - p0);
+    const size_t off = (size_t)p0 * B;
+    c->dec_key_bound = std::min(((p0 + l + 63) / 64) * 64, ((P + 63) / 64) * 64);
+    r = decode_core(c, l * B, st, B, c->row_ids + off, true, true, /*record_alignment=*/false);
+    if (r != TW_OK) { c->dec_key_bound = key_bound_before; return r; }
+    a.s.B = l * B; a.s.rows_streams = B; a.s.row_pos0 = p0; a.s.row_lastts = c->row_lastts + off;
+    HIPCHK(c, launch_score_rows(a, st));
+    HIPCHK(c, launch_advance(c->stt, l, st));
+  }
+  c->dec_key_bound = key_bound_before;
+  HIPCHK(c, hipMemcpyAsync(c->h_score, c->score_out, sizeof(float) * (2 * plane + c->Bmax), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+
+  // ---- [B, seq_len]: 0 for the prompt and for the padding behind a row's first <eos> (the <eos> itself is scored) ----
+  for (int b = 0; b < B; ++b) {
+    int last = seq_len - 1;
+    if (o)
+      for (int i = n_prompt; i < seq_len; ++i)
+        if (ids[(size_t)b * ld + i] == o->eos_id) { last = i; break; }
+    for (int i = 0; i < seq_len; ++i) {
+      const bool scored = i >= n_prompt && i <= last;
+      if (out_logprob) out_logprob[(size_t)b * seq_len + i] = scored ? c->h_score[(size_t)b * P + i] : 0.f;
+      if (out_logprob_raw) out_logprob_raw[(size_t)b * seq_len + i] = scored ? c->h_score[plane + (size_t)b * P + i] : 0.f;
+    }
+    if (no_speech_id >= 0 && out_no_speech) out_no_speech[b] = c->h_score[2 * plane + b];
+  }
   return TW_OK;
 }
 

@@ -1572,6 +1572,179 @@ __global__ __launch_bounds__(1024) void sampler_rows_finish_kernel(SamplerArgs a
   }
 }
 
+// Scoring (tw_score_tokens, api.hip): log-softmax of the GIVEN next token of every row of a rows-mode launch, twice - over the raw
+// logits, and over the logits after Whisper's processors for that row's history (what HF's _retrieve_avg_logprobs takes its
+// log_softmax of).  Shaped like the sampler for the sampler's reason (exp over 51866 logits is VALU work no single CU does in time):
+//  * score_part_kernel: SCORE_NS workgroups per row, each holding its vocabulary slice in registers; ONE read of the slice yields the
+//    slice maximum and sum exp(x - maximum) of three sets - every logit, the unmasked text tokens, the unmasked timestamp tokens.
+//  * score_finish_kernel: one workgroup, wavefront r merges the 32 slices of row r in double precision by a fixed butterfly, applies the
+//    "timestamp mass beats every text token" rule (text drops out of the masked normaliser), and lane 0 stores both numbers.
+// The slicing and the merge order are compile-time constants: a row's numbers do not depend on the other rows of its launch.
+// score_masked_at is sampler_part_kernel's mask, spelled out a second time so that the sampler's kernels stay as they are.
+constexpr int SCORE_NS = 32;
+
+__device__ __forceinline__ bool score_masked_at(const SamplerArgs& a, const SamplerMask& k, int v, unsigned word) {
+  bool masked = ((word >> (v & 31)) & 1u) != 0;
+  if (k.mask_eos && v == a.eos) masked = true;
+  if (a.timestamps && v == a.no_ts_id) masked = true;
+  if (v >= k.b_lo && v < k.b_hi) masked = true;
+  if (v >= k.c_lo && v < k.c_hi) masked = true;
+  if (v < k.d_hi) masked = true;
+  if (v >= k.e_lo) masked = true;
+  if (k.first)
+    for (int i = 0; i < a.n_begin_suppress; ++i) masked |= (v == a.begin_suppress[i]);
+  return masked;
+}
+
+// the block's value of three per-thread values: wavefront reduction, then the four wavefronts in a fixed order through LDS
+template <bool MAX>
+__device__ __forceinline__ void score_block3(float (&v)[3], float (*red)[4], int lane, int wave) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float w = MAX ? wave_max(v[j]) : wave_sum(v[j]);
+    if (lane == 0) red[j][wave] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    v[j] = MAX ? fmaxf(fmaxf(red[j][0], red[j][1]), fmaxf(red[j][2], red[j][3])) : ((red[j][0] + red[j][1]) + red[j][2]) + red[j][3];
+  __syncthreads();
+}
+
+template <int SCORE_IT>
+__global__ __launch_bounds__(256) void score_part_kernel(ScoreArgs sa) {
+  __shared__ float red[3][4];
+  const SamplerArgs& a = sa.s;
+  const int part = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int V = a.V;
+  const float* lg = a.logits + (long long)b * V;
+  const int chunk = ((V + 2 * SCORE_NS - 1) / (2 * SCORE_NS)) * 2;  // even slice length
+  const int v0 = part * chunk, v1 = min(v0 + chunk, V);
+  const bool vec_ok = (chunk <= SCORE_IT * 512) && ((V & 1) == 0) && V >= 2;
+  const int v_last = max(V - 2, 0) & ~1;
+  float s0[SCORE_IT], s1[SCORE_IT];
+  unsigned wb[SCORE_IT];
+  if (vec_ok) {
+#pragma unroll
+    for (int it = 0; it < SCORE_IT; ++it) {  // unconditional (clamped) requests; the pair (v, v+1) shares one bitmap word
+      const int v = min(v0 + (it * 256 + tid) * 2, v_last);
+      const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
+      s0[it] = x2.x;
+      s1[it] = x2.y;
+      wb[it] = a.suppress_bits[v >> 5];
+    }
+  }
+  const SamplerMask k = sampler_mask(a, b);
+  // ---- pass 1: the three maxima (0 raw, 1 unmasked text, 2 unmasked timestamps); cls = the set an element's exp goes to (-1 none) ----
+  float m[3] = {-INFINITY, -INFINITY, -INFINITY};
+  int cls0[SCORE_IT], cls1[SCORE_IT];
+  auto classify = [&](int v, unsigned word) -> int { return score_masked_at(a, k, v, word) ? -1 : (v < k.ts_begin ? 1 : 2); };
+  if (vec_ok) {
+#pragma unroll
+    for (int it = 0; it < SCORE_IT; ++it) {
+      const int v = v0 + (it * 256 + tid) * 2;
+      const bool in = v < v1;      // (v1 - v0 is even: the pair is inside or outside together)
+      cls0[it] = cls1[it] = -2;    // outside the slice
+      if (in) {
+        cls0[it] = classify(v, wb[it]);
+        cls1[it] = classify(v + 1, wb[it]);
+        m[0] = fmaxf(m[0], fmaxf(s0[it], s1[it]));
+        if (cls0[it] == 1) m[1] = fmaxf(m[1], s0[it]); else if (cls0[it] == 2) m[2] = fmaxf(m[2], s0[it]);
+        if (cls1[it] == 1) m[1] = fmaxf(m[1], s1[it]); else if (cls1[it] == 2) m[2] = fmaxf(m[2], s1[it]);
+      }
+    }
+  } else {
+    for (int v = v0 + tid; v < v1; v += 256) {
+      const float x = lg[v];
+      const int cl = classify(v, a.suppress_bits[v >> 5]);
+      m[0] = fmaxf(m[0], x);
+      if (cl == 1) m[1] = fmaxf(m[1], x); else if (cl == 2) m[2] = fmaxf(m[2], x);
+    }
+  }
+  score_block3<true>(m, red, lane, wave);
+  // ---- pass 2: sum exp(x - maximum) of each set (an element of a set is finite and <= the set's maximum: no exp of inf - inf) ----
+  float s[3] = {0.f, 0.f, 0.f};
+  if (vec_ok) {
+#pragma unroll
+    for (int it = 0; it < SCORE_IT; ++it) {
+      if (cls0[it] != -2) {
+        s[0] += expf(s0[it] - m[0]);
+        s[0] += expf(s1[it] - m[0]);
+        if (cls0[it] == 1) s[1] += expf(s0[it] - m[1]); else if (cls0[it] == 2) s[2] += expf(s0[it] - m[2]);
+        if (cls1[it] == 1) s[1] += expf(s1[it] - m[1]); else if (cls1[it] == 2) s[2] += expf(s1[it] - m[2]);
+      }
+    }
+  } else {
+    for (int v = v0 + tid; v < v1; v += 256) {
+      const float x = lg[v];
+      const int cl = classify(v, a.suppress_bits[v >> 5]);
+      s[0] += expf(x - m[0]);
+      if (cl == 1) s[1] += expf(x - m[1]); else if (cl == 2) s[2] += expf(x - m[2]);
+    }
+  }
+  score_block3<false>(s, red, lane, wave);
+  if (tid == 0) {
+    ScorePartial o;
+    o.raw_m = m[0]; o.raw_s = s[0]; o.tx_m = m[1]; o.tx_s = s[1]; o.ts_m = m[2]; o.ts_s = s[2]; o.pad_[0] = o.pad_[1] = 0.f;
+    sa.parts[b * SCORE_NS + part] = o;
+  }
+}
+
+__device__ __forceinline__ double score_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double score_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// (maximum, sum exp(x - maximum)) of a set over the whole vocabulary from its 32 slices, in every lane; an empty set: (-inf, 0)
+__device__ __forceinline__ void score_merge(float pm, float ps, bool on, double& M, double& S) {
+  const double mi = on ? (double)pm : -INFINITY;
+  M = score_wave_max(mi);
+  S = score_wave_sum(mi > -INFINITY ? (double)ps * exp(mi - M) : 0.0);
+}
+
+__global__ __launch_bounds__(1024) void score_finish_kernel(ScoreArgs sa) {
+  const SamplerArgs& a = sa.s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int rs = a.rows_streams;
+  for (int r = tid >> 6; r < a.B; r += 16) {
+    const int stream = r % rs, p = a.row_pos0 + r / rs;
+    const SamplerMask k = sampler_mask(a, r);
+    const ScorePartial q = sa.parts[r * SCORE_NS + min(lane, SCORE_NS - 1)];
+    const bool on = lane < SCORE_NS;
+    double rM, rS, xM, xS, tM, tS;
+    score_merge(q.raw_m, q.raw_s, on, rM, rS);
+    score_merge(q.tx_m, q.tx_s, on, xM, xS);
+    score_merge(q.ts_m, q.ts_s, on, tM, tS);
+    if (lane == 0) {
+      const float* lg = a.logits + (long long)r * a.V;
+      const int t = a.seq[(long long)stream * a.seq_ld + p + 1];   // the given next token (host-checked: inside the vocabulary)
+      const double z = (double)lg[t];
+      const double lse_raw = rM + log(rS);
+      // "if the probability mass of the timestamps is above every text token, sample a timestamp": log_softmax subtracts the same
+      // constant on both sides (HF:generation/logits_process.py:2040-2047)
+      const bool force_ts = a.timestamps && tM > -INFINITY && (tM + log(tS)) > xM;
+      double lse_m = -INFINITY;
+      if (force_ts) {
+        lse_m = tM + log(tS);
+      } else {
+        const double M = fmax(xM, tM);
+        if (M > -INFINITY) lse_m = M + log((xM > -INFINITY ? xS * exp(xM - M) : 0.0) + (tM > -INFINITY ? tS * exp(tM - M) : 0.0));
+      }
+      const bool t_masked = score_masked_at(a, k, t, a.suppress_bits[t >> 5]) || (force_ts && t < k.ts_begin);
+      const long long o = (long long)stream * sa.out_ld + p + 1;
+      sa.out_raw[o] = (float)(z - lse_raw);
+      sa.out_masked[o] = t_masked ? -INFINITY : (float)(z - lse_m);
+      if (sa.ns_id >= 0 && p == sa.ns_pos) sa.out_ns[stream] = (float)exp((double)lg[sa.ns_id] - lse_raw);
+    }
+  }
+}
+
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
 }  // namespace
@@ -1835,6 +2008,20 @@ hipError_t launch_sampler_rows(const SamplerArgs& a0, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sampler_rows_finish_kernel, dim3(1), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t st) {
+  const SamplerArgs& s = a.s;
+  if (s.B < 1 || s.B > 64 || s.rows_streams < 1 || s.B % s.rows_streams != 0 || !s.logits || !s.seq || !s.stt || !s.suppress_bits ||
+      !s.row_lastts || !a.parts || !a.out_masked || !a.out_raw || (a.ns_id >= 0 && !a.out_ns) || a.ns_id >= s.V)
+    return hipErrorInvalidValue;
+  // 32 slices of <= 4 x 512 logits per row whatever the number of rows (the sampler's slicing): a row's partials, and the order they
+  // are merged in, are the same in every launch
+  hipLaunchKernelGGL((score_part_kernel<4>), dim3(SCORE_NS, s.B), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(score_finish_kernel, dim3(1), dim3(1024), 0, st, a);
   return hipGetLastError();
 }
 

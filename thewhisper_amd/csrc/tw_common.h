@@ -355,6 +355,21 @@ hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);   // sampler + 
 // rows mode: sampler over every row + the round's decision (see SamplerArgs); the position is NOT advanced unless the round is decided
 hipError_t launch_sampler_rows(const SamplerArgs& a, hipStream_t st);
 hipError_t launch_suppress_bitmap(const int* list, int n, unsigned* bits, int V, hipStream_t st);  // zero + set bits
+// Scoring of GIVEN tokens (tw_score_tokens): rows mode only.  `s` carries what sampler_mask() needs - logits, V, B rows, seq / seq_ld,
+// stt (n_prompt = the begin index), the processor fields, begin_suppress, suppress_bits, rows_streams, row_pos0, row_lastts - and
+// nothing of the sampler's outputs.  Row r (stream r % rows_streams, position p = row_pos0 + r / rows_streams) with target
+// t = seq[stream][p + 1] stores at [stream * out_ld + p + 1]:
+//   out_raw    = z[t] - logsumexp(z)
+//   out_masked = z'[t] - logsumexp(z'), z' = z after Whisper's logits processors for the history seq[stream][0 .. p] (-inf: t is masked)
+// and, for the row at position ns_pos when ns_id >= 0, out_ns[stream] = softmax(z)[ns_id].
+struct ScorePartial { float raw_m, raw_s, tx_m, tx_s, ts_m, ts_s; float pad_[2]; };  // per vocabulary slice: (max, sum exp(x - max)) of three sets
+struct ScoreArgs {
+  SamplerArgs s;
+  ScorePartial* parts;            // [64][32] workspace between the two launches
+  float* out_masked; float* out_raw; int out_ld;
+  int ns_id, ns_pos; float* out_ns;
+};
+hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t st);
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st);     // pos += n only (teacher-forced stepping, prefill)
 
 // A11: alignment rows -> token timestamps

@@ -378,6 +378,54 @@ class WhisperEngine:
             res["draft"] = {"offered": int(v[0].value), "accepted": int(v[1].value), "launches": int(v[2].value), "rounds": int(v[3].value)}
         return res
 
+    # ---- scores of finished sequences --------------------------------------------------------
+    def score_tokens(
+        self,
+        sequences: np.ndarray,
+        n_prompt: int,
+        *,
+        no_speech_id: Optional[int] = None,
+        no_speech_pos: int = 0,
+        min_new_tokens: int = 0,
+        eos_id: int = 50257,
+        pad_id: int = 50257,
+        timestamps: bool = False,
+        no_timestamps_id: int = 50364,
+        max_initial_timestamp_index: Optional[int] = 50,
+        begin_suppress: Iterable[int] = (220, 50257),
+        suppress: Iterable[int] = (),
+        **ignored,
+    ) -> Dict[str, Optional[np.ndarray]]:
+        """Log-probability of every token of ``sequences`` [B, L] behind the first ``n_prompt`` given the tokens before it, by a
+        teacher-forced pass (tw_score_tokens).  ``logprob``: after the logits processors the keywords describe - the ones
+        ``generate_greedy`` takes; its other keywords (``max_new_tokens``, ``n_draft`` ...) are accepted and ignored - which is what HF
+        averages into ``avg_logprob``; ``logprob_raw``: of the unprocessed logits.  Both float32 [B, L], 0 for the prompt and for the
+        padding behind a row's first ``eos_id``.  ``no_speech_prob`` [B]: probability of ``no_speech_id`` at position ``no_speech_pos``
+        (None when no id is given)."""
+        seq = np.ascontiguousarray(sequences, dtype=np.int32)
+        B, L = seq.shape
+        o = _cabi.tw_greedy_opts()
+        o.eos_id, o.pad_id, o.min_new_tokens = int(eos_id), int(pad_id), int(min_new_tokens)
+        o.timestamps = 1 if timestamps else 0
+        o.no_timestamps_id = int(no_timestamps_id)
+        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+        bs = [int(x) for x in begin_suppress]
+        sp = [int(x) for x in suppress]
+        bs_arr = (C.c_int32 * max(1, len(bs)))(*bs)
+        sp_arr = (C.c_int32 * max(1, len(sp)))(*sp)
+        o.n_begin_suppress, o.begin_suppress = len(bs), bs_arr
+        o.n_suppress, o.suppress = len(sp), sp_arr
+        lp = np.zeros((B, L), dtype=np.float32)
+        raw = np.zeros((B, L), dtype=np.float32)
+        ns = np.zeros((B,), dtype=np.float32) if no_speech_id is not None else None
+        fp = C.POINTER(C.c_float)
+        rc = self.lib.tw_score_tokens(self.ctx, B, seq.ctypes.data_as(C.POINTER(C.c_int32)), L, L, int(n_prompt), C.byref(o),
+                                      -1 if no_speech_id is None else int(no_speech_id), int(no_speech_pos),
+                                      lp.ctypes.data_as(fp), raw.ctypes.data_as(fp), ns.ctypes.data_as(fp) if ns is not None else None,
+                                      self._sp())
+        self._chk(rc, "tw_score_tokens")
+        return {"logprob": lp, "logprob_raw": raw, "no_speech_prob": ns}
+
     # ---- A11 ---------------------------------------------------------------------------------
     def token_timestamps(self, B: int, n_prompt: int, seq_len: int, num_frames: Optional[Sequence[int]] = None,
                          time_precision: float = 0.02) -> np.ndarray:

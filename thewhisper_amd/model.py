@@ -106,6 +106,11 @@ class _EngineGreedyMixin(GenerationMixin):
             probe.append({"prompt": prompt.copy(), "greedy": dict(greedy_kw),
                           "dict": bool(getattr(gc, "return_dict_in_generate", False))})
         out = eng.generate_greedy(prompt, **greedy_kw)
+        sink = getattr(self, "score_sink", None)
+        if sink is not None:    # AMDWhisperBackend(token_scores=True): the calls HF's own control flow makes are scored too
+            from . import shortform
+
+            sink["entries"].extend(shortform.score_entries(eng, out["sequences"], n_prompt, greedy_kw, sink.get("no_speech_id")))
         seq = torch.from_numpy(out["sequences"]).to(decoder_input_ids.device, torch.long)
         self._last_greedy = {"B": B, "n_prompt": n_prompt, "len": int(seq.shape[1])}
         if getattr(gc, "return_dict_in_generate", False):
@@ -231,6 +236,9 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
     _plans: Optional[Dict[Any, Any]] = None
     _plan_probe: Optional[list] = None
     last_plan = None   # the ShortFormPlan of the most recent eligible call (serving.py picks it up after its warm-up call)
+    #: opt-in (streaming.py, token_scores): {"entries": list, "no_speech_id": id or None} - every greedy call made while it is set
+    #: appends its token scores (shortform.score_entries) to ``entries``; None = nothing is scored
+    score_sink: Optional[Dict[str, Any]] = None
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
@@ -302,6 +310,10 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
             self.last_plan = self._plans[key]
             return out
         self.last_plan = plan
+        sink = self.score_sink
+        if sink is not None:
+            return shortform.generate_shortform(self._require_engine(), plan, kwargs["input_features"], kwargs.get("attention_mask"),
+                                                scores_out=sink["entries"], no_speech_id=sink.get("no_speech_id"))
         return shortform.generate_shortform(self._require_engine(), plan, kwargs["input_features"], kwargs.get("attention_mask"))
 
     def _learn_plan(self, kwargs, recs):

@@ -61,7 +61,7 @@ class ShortFormPlan:
 class ChunkWork:
     """Decoding state of one <= chunk_length_s piece of audio (one row of a ``generate`` batch)."""
 
-    __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass")
+    __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass", "scores")
 
     def __init__(self, feats: torch.Tensor, num_frames: Optional[int], tag: Any = None):
         # SURVEY.md section 8f-3 (opt-in, streaming.py): output tokens of the FIRST seek iteration that are already known - they
@@ -72,6 +72,7 @@ class ChunkWork:
         self.draft: Optional[np.ndarray] = None
         self.draft_result: Optional[Dict[str, int]] = None
         self.first_pass: Optional[Tuple[np.ndarray, np.ndarray]] = None   # (ids after the prompt, their timestamps) of iteration 1
+        self.scores: List[Dict[str, Any]] = []     # ``Pass(score=True)``: one ``score_entries`` entry per seek iteration
         self.feats = feats                      # [n_mels, frames] log-mel (device tensor); frames = 2 * T for short-form
         self.num_frames = num_frames            # frames of real audio (attention_mask.sum), None if no mask was given
         self.max_frames = int(feats.shape[-1])  # HF:...:1769 - short-form: the padded feature length, not the audio length
@@ -175,14 +176,51 @@ def columns_as_num_frames(cols: Sequence[int]) -> List[int]:
     return [2 * int(c) for c in cols]
 
 
+def generated_tokens(row: np.ndarray, pad: int, eos: int) -> Tuple[np.ndarray, bool]:
+    """(tokens of one row behind the prompt without padding and <eos>, whether an <eos> stood behind them) - HF:...:1068-1076."""
+    stop = np.flatnonzero(row == eos)
+    if stop.size:
+        return row[: int(stop[0])], True
+    keep = len(row)
+    while keep > 0 and row[keep - 1] == pad:
+        keep -= 1
+    return row[:keep], False
+
+
+def score_entries(engine, sequences: np.ndarray, n_prompt: int, greedy: Dict[str, Any], no_speech_id: Optional[int] = None
+                  ) -> List[Dict[str, Any]]:
+    """Token scores of one finished greedy call (``WhisperEngine.score_tokens`` with the call's own logits processors), one entry per
+    row: ``tokens`` (generated ids, no padding, no <eos>), ``logprob`` / ``logprob_raw`` (of those tokens FOLLOWED by the <eos>'s
+    when the row ended with one: float32 [n_tokens (+ 1)]), ``avg_logprob`` = sum(logprob) / (n_tokens + 1) - the number HF's
+    ``_retrieve_avg_logprobs`` (HF:models/whisper/generation_whisper.py:1957-1974) gives for a row that ended with <eos>; a row cut at
+    the token budget has no <eos> term and keeps the divisor, as openai/whisper does - and ``no_speech_prob`` (None without an id)."""
+    seq = np.ascontiguousarray(sequences)
+    res = engine.score_tokens(seq, n_prompt, no_speech_id=no_speech_id, no_speech_pos=0, **greedy)
+    eos, pad = int(greedy.get("eos_id", 50257)), int(greedy.get("pad_id", 50257))
+    out = []
+    for i in range(seq.shape[0]):
+        toks, ended = generated_tokens(seq[i, n_prompt:], pad, eos)
+        n = len(toks) + (1 if ended else 0)
+        lp = np.asarray(res["logprob"][i, n_prompt : n_prompt + n], dtype=np.float32).copy()
+        raw = np.asarray(res["logprob_raw"][i, n_prompt : n_prompt + n], dtype=np.float32).copy()
+        ns = res.get("no_speech_prob")
+        out.append({"tokens": np.asarray(toks).copy(), "logprob": lp, "logprob_raw": raw,
+                    "avg_logprob": float(lp.astype(np.float64).sum() / (len(toks) + 1)),
+                    "no_speech_prob": None if ns is None else float(ns[i])})
+    return out
+
+
 class Pass:
     """One seek iteration (HF:...:785-903) for up to ``engine.max_batch`` chunks, assembled in GROUPS: ``add(works)`` cuts the
     groups' segments and enqueues their encoder + cross-K/V stage at the next free slots (asynchronous launches), ``run()``
     decodes all slots in one greedy loop and advances every chunk.  A serving loop adds the chunks that need a further
-    iteration first and whatever arrives while the GPU is still encoding those; ``run_pass`` is the one-group form."""
+    iteration first and whatever arrives while the GPU is still encoding those; ``run_pass`` is the one-group form.
+    ``score`` (opt-in): after the greedy call and the token timestamps, the pass's sequences are scored (``score_entries``) and
+    every chunk's ``scores`` list gains the entry of this iteration; nothing else changes."""
 
-    def __init__(self, engine, plan: ShortFormPlan):
+    def __init__(self, engine, plan: ShortFormPlan, score: bool = False, no_speech_id: Optional[int] = None):
         self.engine, self.plan = engine, plan
+        self.score, self.no_speech_id = bool(score), no_speech_id
         self.works: List[ChunkWork] = []
         self.snf: List[int] = []
         self._keep: List[torch.Tensor] = []       # segment tensors stay alive until the pass has run
@@ -286,6 +324,9 @@ class Pass:
                 elif works[0].num_frames is not None:                          # HF:...:1152-1155: num_frames - seek
                     nf = columns_as_num_frames([hf_kept_columns([int(w.num_frames) - int(w.seek)], 1, int(engine.T))[0] for w in works])
                 ts = torch.from_numpy(engine.token_timestamps(B, n_prompt, L, nf, plan.time_precision))
+        if self.score:     # (the begin index is the plan's prompt length: forced and drafted tokens count as generated)
+            for w, entry in zip(works, score_entries(engine, out["sequences"], n_prompt, plan.greedy, self.no_speech_id)):
+                w.scores.append(entry)
         for i, w in enumerate(works):
             if plan.result_is_dict:
                 result: Any = {"sequences": seq[i]}
@@ -336,12 +377,13 @@ def first_segment(work: ChunkWork, T: int) -> torch.Tensor:
     return next_segment(work, T)
 
 
-def run_pass(engine, plan: ShortFormPlan, works: Sequence[ChunkWork], kept_columns: Optional[Sequence[int]] = None) -> None:
+def run_pass(engine, plan: ShortFormPlan, works: Sequence[ChunkWork], kept_columns: Optional[Sequence[int]] = None,
+             score: bool = False, no_speech_id: Optional[int] = None) -> None:
     """One seek iteration for every work in ``works`` (all unfinished, len <= engine.max_batch): segment cut-out, encoder +
     cross-K/V + greedy loop (+ token timestamps) on the engine, segment slicing, seek advance."""
     if len(works) < 1 or len(works) > engine.max_batch:
         raise ValueError(f"a pass takes 1..{engine.max_batch} chunks, got {len(works)}")
-    p = Pass(engine, plan)
+    p = Pass(engine, plan, score=score, no_speech_id=no_speech_id)
     p.add(works)
     p.run(kept_columns)
 
@@ -389,8 +431,11 @@ def assemble(plan: ShortFormPlan, works: Sequence[ChunkWork], device) -> Any:
     return outputs
 
 
-def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor, attention_mask: Optional[torch.Tensor]) -> Any:
-    """Drop-in for ``WhisperGenerationMixin.generate`` on an eligible batch: identical return value, fewer Python layers."""
+def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor, attention_mask: Optional[torch.Tensor],
+                       scores_out: Optional[List[Dict[str, Any]]] = None, no_speech_id: Optional[int] = None) -> Any:
+    """Drop-in for ``WhisperGenerationMixin.generate`` on an eligible batch: identical return value, fewer Python layers.
+    ``scores_out`` (a list): every pass also scores its tokens (``Pass(score=True)``) and the entries are appended to it, row by row,
+    a row's seek iterations in order."""
     B = int(input_features.shape[0])
     nf: List[Optional[int]] = [None] * B
     if plan.return_token_timestamps and attention_mask is not None:
@@ -406,8 +451,11 @@ def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor
             # HF hands `(num_frames - seek)[batch_idx_map]` of the WHOLE active batch to `_extract_token_timestamps` (:1152-1155)
             cols = hf_kept_columns([int(w.num_frames) - int(w.seek) for w in active], len(active), int(engine.T))
         for i in range(0, len(active), cap):                                   # a call wider than the engine: several passes per iteration
-            run_pass(engine, plan, active[i : i + cap], None if cols is None else cols[i : i + cap])
+            run_pass(engine, plan, active[i : i + cap], None if cols is None else cols[i : i + cap],
+                     score=scores_out is not None, no_speech_id=no_speech_id)
         if any(w.passes > MAX_SEEK_PASSES for w in active):
             # a decoder that keeps closing its segments at <|0.00|> never advances `seek`; HF's loop spins forever on such a row
             raise RuntimeError(f"a chunk needed more than {MAX_SEEK_PASSES} seek passes (the decoder keeps seeking to frame 0)")
+    if scores_out is not None:
+        scores_out.extend(e for w in works for e in w.scores)
     return assemble(plan, works, input_features.device)

@@ -40,6 +40,7 @@ class AMDWhisperBackend:
         reuse_margin_s: float = 1.0,
         draft_previous_tick: Optional[bool] = None,
         resample_kernel=None,
+        token_scores: bool = False,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -64,7 +65,12 @@ class AMDWhisperBackend:
         of speed, not of correctness.  ``reuse_stats`` counts drafted and confirmed tokens.  Not together with
         ``reuse_committed_prefix``.  Because the result is the plain call's, this is ON by default (``None`` = on unless
         ``reuse_committed_prefix`` was asked for); ``False`` gives the reference's behaviour literally - every tick decoded from
-        scratch (R:thestage_speechkit/streaming/streaming_pipeline.py:388-435)."""
+        scratch (R:thestage_speechkit/streaming/streaming_pipeline.py:388-435).
+
+        ``token_scores`` (opt-in): every greedy call of a ``transcribe`` / ``transcribe_many`` is followed by a re-scoring pass
+        (tw_score_tokens) and ``last_scores`` holds, for the most recent call, one entry per seek iteration of every chunk -
+        ``{tokens, logprob, logprob_raw, avg_logprob, no_speech_prob}`` (shortform.score_entries).  The returned words are what
+        they are with the option off: the scores travel beside them."""
         from .asr_pipeline import ASRPipeline
 
         if torch_dtype is None:
@@ -97,6 +103,9 @@ class AMDWhisperBackend:
         self._reuse_codec = None      # JobCodec (learned plan), built on the first reuse-enabled call
         self._last = None             # what the previous call left: start time, samples, first-iteration tokens + timestamps
         self._resample_kernel = resample_kernel   # tests: the numpy restatement in place of tw_resample (resample.py)
+        self.token_scores = bool(token_scores)
+        self.last_scores: List[Dict[str, Any]] = []
+        self._no_speech_id: Any = False           # not looked up yet
 
     def to_engine_rate(self, audio, sample_rate: int):
         """``(audio, sample_rate)`` as the engine wants it: a buffer at another rate (or int16 / multi-channel) goes through
@@ -112,13 +121,43 @@ class AMDWhisperBackend:
     def _generate_kwargs(self) -> Dict[str, Any]:
         return {"use_cache": True, "num_beams": 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
 
+    @property
+    def no_speech_id(self) -> Optional[int]:
+        """Id of ``<|nospeech|>`` (``<|nocaptions|>`` on older vocabularies) in the pipeline's tokenizer, or None."""
+        if self._no_speech_id is False:
+            tok = getattr(self.asr_pipeline, "tokenizer", None)
+            found = None
+            for name in ("<|nospeech|>", "<|nocaptions|>"):
+                try:
+                    i = tok.convert_tokens_to_ids(name)
+                    if i is not None and int(i) >= 0 and tok.convert_ids_to_tokens(int(i)) == name:
+                        found = int(i)
+                        break
+                except Exception:  # noqa: BLE001 - no tokenizer, or one without the token
+                    continue
+            self._no_speech_id = found
+        return self._no_speech_id
+
+    def _run_pipeline(self, *args, **kwargs):
+        """``self.asr_pipeline(...)``; with ``token_scores`` the model object scores every greedy call it makes meanwhile."""
+        model = getattr(self.asr_pipeline, "model", None)
+        if not self.token_scores or model is None:
+            return self.asr_pipeline(*args, **kwargs)
+        entries: List[Dict[str, Any]] = []
+        model.score_sink = {"entries": entries, "no_speech_id": self.no_speech_id}
+        try:
+            return self.asr_pipeline(*args, **kwargs)
+        finally:
+            model.score_sink = None
+            self.last_scores = entries
+
     def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
         audio, sample_rate = self.to_engine_rate(audio, sample_rate)
         if self.reuse_committed_prefix or self.draft_previous_tick:
             words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate))
             if words is not None:
                 return words
-        result: Dict[str, Any] = self.asr_pipeline(
+        result: Dict[str, Any] = self._run_pipeline(
             audio,
             return_timestamps="word",
             generate_kwargs=self._generate_kwargs(),
@@ -198,7 +237,7 @@ class AMDWhisperBackend:
                 self.reuse_stats["forced_tokens"] += int(len(forced))
         while not job.done:
             for w in [w for w in job.works if not w.done]:
-                shortform.run_pass(eng, codec.plan, [w])
+                shortform.run_pass(eng, codec.plan, [w], score=codec.score, no_speech_id=codec.no_speech_id)
                 if w.passes > shortform.MAX_SEEK_PASSES:
                     raise RuntimeError(f"a chunk needed more than {shortform.MAX_SEEK_PASSES} seek passes")
         if len(job.works) == 1 and job.works[0].first_pass is not None:
@@ -210,7 +249,10 @@ class AMDWhisperBackend:
             self.reuse_stats["decoded_tokens"] += int(len(ids)) - (int(len(forced)) if forced is not None else 0) - (int(dr["accepted"]) if dr else 0)
             self._last = {"start": buffer_start_time, "n_samples": len(audio), "sr": sample_rate, "ids": ids, "ts": ts,
                           "audio": np.array(audio, copy=True)}
-        return codec.close(job)
+        words = codec.close(job)
+        if self.token_scores:
+            self.last_scores = job.scores
+        return words
 
     def transcribe_many(self, requests, batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """Several streams' rolling buffers in ONE pipeline call: [(audio, buffer_start_time, sample_rate), ...].
@@ -218,7 +260,7 @@ class AMDWhisperBackend:
         requests = [(self.to_engine_rate(a, sr)[0], t0, self.sample_rate) for a, t0, sr in requests]
         audios = [np.asarray(a) for a, _, _ in requests]
         kw = {} if batch_size is None else {"batch_size": int(batch_size)}
-        results = self.asr_pipeline(
+        results = self._run_pipeline(
             audios, return_timestamps="word", generate_kwargs=self._generate_kwargs(), chunk_length_s=self.chunk_length_s, **kw
         )
         return [self._to_tokens(res, len(a) / sr, t0) for res, (a, t0, sr) in zip(results, requests)]
@@ -260,7 +302,7 @@ class _NotEligible(Exception):
 class BufferJob:
     """One ``transcribe`` request on its way through the hub: its chunks' decoding states and what post-processing needs."""
 
-    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit")
+    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit", "scores")
 
     def __init__(self, works, meta, audio_duration, buffer_start_time):
         self.works = works                        # [shortform.ChunkWork] - one per <= chunk_length_s piece of the buffer
@@ -269,6 +311,7 @@ class BufferJob:
         self.buffer_start_time = buffer_start_time
         self.future = None
         self.t_submit = 0.0
+        self.scores: List[Dict[str, Any]] = []     # JobCodec.close: the chunks' score entries when the backend asked for them
 
     @property
     def done(self) -> bool:
@@ -294,6 +337,9 @@ class JobCodec:
         self.pre = {**pipe._preprocess_params, **pre}
         self.post = {**pipe._postprocess_params, **post}
         self.plan = None
+        # AMDWhisperBackend(token_scores=True): whoever runs this codec's jobs builds its passes with Pass(score=..., no_speech_id=...)
+        self.score = bool(getattr(backend, "token_scores", False))
+        self.no_speech_id = backend.no_speech_id if self.score else None
 
     def learn(self) -> bool:
         """One short request through the ordinary pipeline call: HF's ``generate`` runs once with this backend's options and
@@ -341,5 +387,6 @@ class JobCodec:
             if stride is not None:
                 o["stride"] = stride
             outs.append(o)
+        job.scores = [e for w in job.works for e in w.scores]
         result = self.pipe.postprocess(outs, **self.post)
         return AMDWhisperBackend._to_tokens(result, job.audio_duration, job.buffer_start_time)

@@ -199,6 +199,37 @@ int tw_decode_step(tw_ctx* ctx, int32_t B, const int32_t* ids_host, float* logit
 int tw_generate_greedy(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt,
                        const tw_greedy_opts* opts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
 
+/* Temperature sampling on the device.  Replaces: GenerationMixin._sample with do_sample=True and a TemperatureLogitsWarper behind
+ * Whisper's logits processors (HF:generation/utils.py:1293-1312, :2925-2931), as WhisperGenerationMixin.generate_with_fallback invokes it
+ * for the temperatures behind 0 (HF:models/whisper/generation_whisper.py:970-1116; thewhisper_amd/fallback.py restates that ladder).
+ *
+ * THE DRAW.  Row b consumes position p and produces the token at p + 1.  x = the float32 logits; the mask is exactly
+ * tw_generate_greedy's, and "the timestamp mass beats every text token" is decided on the unscaled processed logits as there.  Among
+ * the ids still unmasked
+ *     score(v) = x[v] * inv_t[b] + g(v),    g(v) = -logf(-logf(u)),    u = ((w >> 9) * 2 + 1) * 2^-24   (exact, never 0 or 1),
+ *     w = output word (v & 3) of Philox4x32-10, counter (v >> 2, p, offset low, offset high), key (seed low, seed high),
+ * and the token is the lowest id that attains the maximum: Gumbel-max, a draw from softmax(x / T) over the unmasked ids.  Everything
+ * masked: id 0, as the greedy call returns.  temperature[b]
+ *     > 0 : sample, inv_t = 1.0f / T (computed on the host);
+ *    == 0 : the row is greedy (no noise, inv_t = 1): its tokens are tw_generate_greedy's, bit for bit;
+ *     < 0 : the row sits the call out: it starts finished, receives pad_id from position n_prompt on, never holds up the loop and
+ *           does not count towards out_len_host.
+ * The noise depends on (seed, offset, position, id) alone - not on the slot, the other rows of the batch or graph replay - so a
+ * stream's result does not depend on what else is in its batch.  This is NOT torch's generator: no bit parity with
+ * torch.multinomial is claimed or possible; and the draw is from the FULL distribution, as openai/whisper's, where HF's sampling
+ * also applies top_k = 50 by default.
+ *
+ * Outputs as tw_generate_greedy's; want_alignment is honoured (tw_token_timestamps works after it); tw_last_timings[3] and the step
+ * count are filled.  TW_EINVAL: n_forced or n_draft set, a NaN or infinite temperature or one so small that 1 / T is not finite, every
+ * row < 0, a NULL temperature / seed, B outside 1 .. 64; TW_ESTATE, as tw_generate_greedy: B above the clips the cross K/V hold. */
+typedef struct tw_sample_opts {
+  const float*    temperature;  /* host float32 [B]; see "the draw" */
+  const uint64_t* seed;         /* host [B]: Philox key */
+  const uint64_t* offset;       /* host [B]: counter words 2, 3; NULL = all 0 */
+} tw_sample_opts;
+int tw_generate_sample(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
+                       const tw_sample_opts* sopts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
+
 /* Of the most recent tw_generate_greedy with n_draft > 0 (all streams together): draft tokens offered, draft tokens confirmed, rows-mode
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */
 int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds);

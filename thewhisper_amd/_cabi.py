@@ -39,6 +39,10 @@ class tw_greedy_opts(C.Structure):
     ]
 
 
+class tw_sample_opts(C.Structure):
+    _fields_ = [("temperature", C.POINTER(C.c_float)), ("seed", C.POINTER(C.c_uint64)), ("offset", C.POINTER(C.c_uint64))]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -58,6 +62,8 @@ SYMBOLS = [
     ("tw_decoder_reset", C.c_int, [_P, C.c_int32, _P]),
     ("tw_decode_step", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     ("tw_generate_greedy", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_last_draft", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("tw_score_tokens", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(tw_greedy_opts),

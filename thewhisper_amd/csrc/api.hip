@@ -92,6 +92,9 @@ struct tw_ctx {
   DecState* stt = nullptr;
   int* begin_suppress_dev = nullptr; int* suppress_dev = nullptr;
   SamplerPartial* sampler_partials = nullptr;
+  // tw_generate_sample: per-row temperature reciprocals, Philox keys / offsets, noisy flags (uploaded per call) and the slice partials
+  float* sample_inv_t = nullptr; uint32_t* sample_key = nullptr; uint32_t* sample_off = nullptr; int* sample_noisy = nullptr;   // [64], [64][2], [64][2], [64]
+  SamplePartial* sample_parts = nullptr;   // [64][32]
   unsigned* suppress_bits = nullptr;  // [(V+31)/32] static suppress list as a bitmap, rebuilt per generate call
   int* h_pinned = nullptr;  // pinned host scratch: finished ring [8][64] | n_valid [64] | DecState upload [16]
   int* row_ids = nullptr;   // device token table of a prefill (position-major), row_ids_cap ints
@@ -113,6 +116,7 @@ struct tw_ctx {
   float* h_score = nullptr;            // pinned, the same layout
   int row_cap = 0;          // rows the per-token activation buffers hold (>= max_batch; 64 for the prefill launches)
   int* h_stage = nullptr;   // pinned staging of tw_generate_greedy: token table [Bmax][P] (up and down) | 3 x [Bmax] | suppress lists | DecState
+                            // | tw_generate_sample: inv_t [64] | key [64][2] | off [64][2] | noisy [64]
   size_t h_stage_ints = 0;
   hipEvent_t ring_ev[8]{};
   int last_seq_len = 0, last_n_prompt = 0;
@@ -325,7 +329,7 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   for (int i = 0; i < 5; ++i) { CHIP(hipEventCreate(&c->ev0[i])); CHIP(hipEventCreate(&c->ev1[i])); }
   for (int i = 0; i < 8; ++i) CHIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
   CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), sizeof(int) * (8 * 64 + 64 + 16), hipHostMallocDefault));
-  c->h_stage_ints = (size_t)c->Bmax * c->P + 3 * (size_t)c->Bmax + 64 + 1024 + 16;
+  c->h_stage_ints = (size_t)c->Bmax * c->P + 3 * (size_t)c->Bmax + 64 + 1024 + 16 + 6 * 64;
   CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), sizeof(int) * c->h_stage_ints, hipHostMallocDefault));
 
   const size_t e = c->esz;
@@ -475,6 +479,8 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CALLOC(c->begin_suppress_dev, 64 * 4, true); CALLOC(c->suppress_dev, 1024 * 4, true);
   CALLOC(c->suppress_bits, ((V + 31) / 32 + 2048) * 4, true);
   CALLOC(c->sampler_partials, 64 * 32 * sizeof(SamplerPartial), true);
+  CALLOC(c->sample_inv_t, 64 * 4, true); CALLOC(c->sample_key, 128 * 4, true); CALLOC(c->sample_off, 128 * 4, true);
+  CALLOC(c->sample_noisy, 64 * 4, true); CALLOC(c->sample_parts, 64 * 32 * sizeof(SamplePartial), true);
   CALLOC(c->score_seq, B * P * 4, true); CALLOC(c->score_bsup, 64 * 4, true); CALLOC(c->score_sup, 1024 * 4, true);
   CALLOC(c->score_bits, ((V + 31) / 32 + 2048) * 4, true);
   CALLOC(c->score_parts, 64 * 32 * sizeof(ScorePartial), true);
@@ -1132,11 +1138,13 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
   return TW_OK;
 }
 
-int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o,
-                       int32_t* out_ids, int32_t* out_len, void* stream) {
-  if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy: null argument");
-  TW_ON_DEVICE(c);
-  if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "tw_generate_greedy: B=%d but cross K/V holds %d clips", B, c->cross_B);
+// The generation loop of tw_generate_greedy and tw_generate_sample.  so == nullptr: the greedy call, launch for launch what it has always
+// issued.  so != nullptr (validated by tw_generate_sample: no forced / draft tokens, finite temperatures, a live row): every step's
+// sampler is launch_sample; rows with temperature < 0 start finished.
+static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
+                         int32_t* out_ids, int32_t* out_len, void* stream) {
+  const char* fn = so ? "tw_generate_sample" : "tw_generate_greedy";
+  if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
   if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
   if (o->want_alignment && c->Ha == 0) return fail(c, TW_EINVAL, "want_alignment but the context has no alignment heads");
@@ -1168,6 +1176,10 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   int* bsup = neg + c->Bmax;                               // [64]
   int* sup = bsup + 64;                                    // [1024]
   DecState* s0p = reinterpret_cast<DecState*>(sup + 1024);
+  float* h_inv_t = reinterpret_cast<float*>(sup + 1024 + 16);     // [64]
+  uint32_t* h_key = reinterpret_cast<uint32_t*>(h_inv_t + 64);    // [64][2]
+  uint32_t* h_off = h_key + 128;                                  // [64][2]
+  int* h_noisy = reinterpret_cast<int*>(h_off + 128);             // [64]
   for (size_t i = 0; i < (size_t)B * P; ++i) hseq[i] = o->pad_id;
   for (int b = 0; b < B; ++b) {
     for (int i = 0; i < n_prompt; ++i) {
@@ -1177,8 +1189,16 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
     }
     // with forced tokens the loop starts at the LAST given position (everything before it is prefilled below)
     first[b] = prompt[(size_t)b * n_prompt + (n_forced > 0 ? n_prompt - 1 : 0)];
-    zeros[b] = 0;
+    zeros[b] = (so && so->temperature[b] < 0.f) ? 1 : 0;   // a row that sits the call out starts finished
     neg[b] = -1;
+    if (so) {
+      const float t = so->temperature[b];
+      h_noisy[b] = t > 0.f ? 1 : 0;
+      h_inv_t[b] = t > 0.f ? 1.0f / t : 1.0f;
+      const uint64_t sd = so->seed ? so->seed[b] : 0, of = so->offset ? so->offset[b] : 0;
+      h_key[2 * b] = (uint32_t)sd; h_key[2 * b + 1] = (uint32_t)(sd >> 32);
+      h_off[2 * b] = (uint32_t)of; h_off[2 * b + 1] = (uint32_t)(of >> 32);
+    }
     for (int i = n_begin; i < n_prompt; ++i) {   // state the sampler would have after producing the forced tokens itself
       const int t = prompt[(size_t)b * n_prompt + i];
       if (t == o->eos_id) return fail(c, TW_EINVAL, n_draft > 0 ? "a draft token is <eos>" : "a forced token is <eos>");
@@ -1189,6 +1209,12 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   HIPCHK(c, hipMemcpyAsync(c->cur_ids, first, sizeof(int) * B, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->finished, zeros, sizeof(int) * B, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->last_ts, neg, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  if (so) {
+    HIPCHK(c, hipMemcpyAsync(c->sample_inv_t, h_inv_t, sizeof(float) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_key, h_key, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_off, h_off, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_noisy, h_noisy, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  }
   if (o->n_begin_suppress > 0) {
     memcpy(bsup, o->begin_suppress, sizeof(int) * o->n_begin_suppress);
     HIPCHK(c, hipMemcpyAsync(c->begin_suppress_dev, bsup, sizeof(int) * o->n_begin_suppress, hipMemcpyHostToDevice, st));
@@ -1255,8 +1281,16 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress);
+  // (last field: the sampler flavour - a greedy graph is never replayed for a sampling call, nor the reverse)
+  snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, so ? 's' : 'g');
+  SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
+  sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
+  auto sample_step = [&]() -> hipError_t {
+    if (!so) return launch_sampler(sa, st);
+    sma.s = sa;
+    return launch_sample(sma, st);
+  };
   const bool use_graph = c->cfg.use_graph != 0;
   if (use_graph && c->step_graph_key != keybuf) {   // other options: the captured sampler arguments are stale
     for (auto& kv : c->step_graphs) (void)hipGraphExecDestroy(kv.second);
@@ -1276,7 +1310,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
     hipError_t es = hipSuccess;
     for (int i = 0; i < n && r == TW_OK && es == hipSuccess; ++i) {
       r = decode_core(c, B, st, 0, nullptr, false);
-      if (r == TW_OK) es = launch_sampler(sa, st);
+      if (r == TW_OK) es = sample_step();
     }
     hipError_t ee = hipStreamEndCapture(st, &g);
     if (r != TW_OK) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -1327,7 +1361,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
       c->dec_key_bound = kb;
       int r = decode_core(c, B, st, 0, nullptr, false);
       if (r != TW_OK) return r;
-      HIPCHK(c, launch_sampler(sa, st));
+      HIPCHK(c, sample_step());
     }
     steps += n;
     s += n;
@@ -1352,7 +1386,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   if (host_timing) {
     float dev_ms = 0.f;
     (void)hipEventElapsedTime(&dev_ms, c->ev0[3], c->ev1[3]);
-    fprintf(stderr, "TW_HOST_TIMING generate_greedy B=%d steps=%d launches=%d: first launch submitted at %.3f ms, host loop done at %.3f ms, "
+    fprintf(stderr, "TW_HOST_TIMING generate B=%d steps=%d launches=%d: first launch submitted at %.3f ms, host loop done at %.3f ms, "
                     "synchronised at %.3f ms; device loop (events) %.3f ms\n", B, steps, launches, ht_first, ht_loop, ht_ms(), dev_ms);
   }
 
@@ -1363,6 +1397,7 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   const int scan_from = n_draft > 0 ? std::max(s_start, n_begin) : n_prompt;
   int L = scan_from + 1;
   for (int b = 0; b < B; ++b) {
+    if (so && so->temperature[b] < 0.f) continue;   // a row that sat the call out holds pad_id only: it does not set the length
     int lb = produced;
     for (int i = scan_from; i < produced; ++i)
       if (hseq[(size_t)b * P + i] == o->eos_id) { lb = i + 1; break; }
@@ -1384,6 +1419,32 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
   c->last_seq_len = L;
   c->last_n_prompt = n_prompt;
   return TW_OK;
+}
+
+int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o,
+                       int32_t* out_ids, int32_t* out_len, void* stream) {
+  if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy: null argument");
+  TW_ON_DEVICE(c);
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_sample(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
+                       int32_t* out_ids, int32_t* out_len, void* stream) {
+  if (!c || !prompt || !o || !so || !so->temperature || !so->seed || !out_ids || !out_len)
+    return fail(c, TW_EINVAL, "tw_generate_sample: null argument");
+  TW_ON_DEVICE(c);
+  if (B < 1 || B > 64) return fail(c, TW_EINVAL, "tw_generate_sample: %d streams (1..64)", B);
+  if (o->n_forced != 0 || o->n_draft != 0)
+    return fail(c, TW_EINVAL, "tw_generate_sample: n_forced %d / n_draft %d: forced and draft tokens are for greedy calls", o->n_forced, o->n_draft);
+  bool live = false;
+  for (int b = 0; b < B; ++b) {
+    const float t = so->temperature[b];
+    if (!std::isfinite(t) || (t > 0.f && !std::isfinite(1.0f / t)))   // (a subnormal T: 1 / T overflows and the noise would be lost)
+      return fail(c, TW_EINVAL, "tw_generate_sample: temperature of row %d is not finite, or too small for 1 / T to be", b);
+    live |= t >= 0.f;
+  }
+  if (!live) return fail(c, TW_EINVAL, "tw_generate_sample: every row has a negative temperature (nothing to generate)");
+  return generate_loop(c, B, prompt, n_prompt, o, so, out_ids, out_len, stream);
 }
 
 int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_t seq_len, int32_t n_prompt, const tw_greedy_opts* o,

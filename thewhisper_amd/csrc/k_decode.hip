@@ -1572,6 +1572,197 @@ __global__ __launch_bounds__(1024) void sampler_rows_finish_kernel(SamplerArgs a
   }
 }
 
+// Temperature sampling (tw_generate_sample, api.hip; the draw is defined at SampleArgs, tw_common.h): the greedy sampler's two launches
+// with Gumbel noise on the scaled logits, as kernels of their own so that the greedy sampler's stay as they are.
+//  * sample_part_kernel: the slicing, the register-resident slice and the vector / scalar paths of sampler_part_kernel.  Per slice: the
+//    greedy partials of the UNSCALED logits (best text, best timestamp, sum exp(x - slice max) over timestamps: what the mass rule is
+//    decided on) and the best perturbed text and timestamp (value, id).  One Philox4x32-10 block serves the ids 4j .. 4j + 3, so a
+//    thread's pair (v, v + 1), v even, costs one block; the block and the two logf per logit are VALU work behind the logit requests.
+//  * sample_finish_kernel: merges the unscaled partials in sampler_merge's order (a mass decision equals the greedy one bit for bit on
+//    equal logits); mass rule fired: the best perturbed timestamp, else the better of the two perturbed maxima (lower id on a tie);
+//    then sampler_finish_kernel's bookkeeping, line for line.
+// The mask is score_masked_at: ONE restatement of sampler_part_kernel's mask serves the scoring pass and the sampling kernels.
+struct Philox4 { unsigned w[4]; };
+__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+__device__ __forceinline__ float gumbel_of(unsigned w) {
+  const float u = (float)((w >> 9) * 2u + 1u) * 5.9604644775390625e-08f;   // 2^-24; the integer is odd and below 2^24: exact
+  return -logf(-logf(u));
+}
+__device__ __forceinline__ bool score_masked_at(const SamplerArgs& a, const SamplerMask& k, int v, unsigned word);   // (below: the scoring pass's)
+
+template <int SAMPLER_NS, int SAMPLER_IT>
+__global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
+  __shared__ MaxIdx red[4][4];
+  __shared__ float red_sum[4];
+  const SamplerArgs& a = sa.s;
+  const int part = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int V = a.V;
+  const float* lg = a.logits + (long long)b * V;
+  const int chunk = ((V + 2 * SAMPLER_NS - 1) / (2 * SAMPLER_NS)) * 2;  // even slice length
+  const int v0 = part * chunk, v1 = min(v0 + chunk, V);
+  const bool vec_ok = (chunk <= SAMPLER_IT * 512) && ((V & 1) == 0) && V >= 2;
+  const int v_last = max(V - 2, 0) & ~1;
+  float s0[SAMPLER_IT], s1[SAMPLER_IT];
+  unsigned wb[SAMPLER_IT];
+#pragma unroll
+  for (int it = 0; it < SAMPLER_IT; ++it) {  // unconditional (clamped) requests; the pair (v, v+1) shares one bitmap word
+    const int v = min(v0 + (it * 256 + tid) * 2, v_last);
+    const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
+    s0[it] = x2.x;
+    s1[it] = x2.y;
+    wb[it] = a.suppress_bits[v >> 5];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const SamplerMask k = sampler_mask(a, b);
+  const unsigned p = (unsigned)a.stt->pos;
+  const bool noisy = sa.noisy[b] != 0;
+  const float inv_t = sa.inv_t[b];
+  const unsigned k0 = sa.key[2 * b], k1 = sa.key[2 * b + 1], o0 = sa.off[2 * b], o1 = sa.off[2 * b + 1];
+  // x: a logit after the mask (-inf: masked, stays -inf); w: its Philox word
+  auto perturbed = [&](float x, unsigned w) -> float { return noisy ? __fadd_rn(__fmul_rn(x, inv_t), gumbel_of(w)) : x; };
+  // ---- pass 1: best text / timestamp of the slice, unscaled and perturbed ----
+  MaxIdx bt{-INFINITY, 0x7fffffff}, bs{-INFINITY, 0x7fffffff}, pt{-INFINITY, 0x7fffffff}, ps{-INFINITY, 0x7fffffff};
+  if (vec_ok) {
+#pragma unroll
+    for (int it = 0; it < SAMPLER_IT; ++it) {
+      const int v = v0 + (it * 256 + tid) * 2;
+      const bool in = v < v1;
+      const int vc = in ? v : 0;
+      s0[it] = (in && !score_masked_at(a, k, vc, wb[it])) ? s0[it] : -INFINITY;
+      s1[it] = (in && !score_masked_at(a, k, vc + 1, wb[it])) ? s1[it] : -INFINITY;
+      if (in) {
+        MaxIdx c0{s0[it], v}, c1{s1[it], v + 1};
+        MaxIdx q0 = c0, q1 = c1;
+        if (noisy) {   // (uniform) v is even: v and v + 1 are words v & 3 and (v & 3) + 1 of one block
+          const Philox4 r = philox4x32_10((unsigned)v >> 2, p, o0, o1, k0, k1);
+          const bool up = (v & 2) != 0;
+          q0.v = perturbed(c0.v, up ? r.w[2] : r.w[0]);
+          q1.v = perturbed(c1.v, up ? r.w[3] : r.w[1]);
+        }
+        if (v < k.ts_begin) { bt = better(bt, c0); pt = better(pt, q0); } else { bs = better(bs, c0); ps = better(ps, q0); }
+        if (v + 1 < k.ts_begin) { bt = better(bt, c1); pt = better(pt, q1); } else { bs = better(bs, c1); ps = better(ps, q1); }
+      }
+    }
+  } else {
+    for (int v = v0 + tid; v < v1; v += 256) {
+      MaxIdx c{score_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v};
+      MaxIdx q = c;
+      if (noisy) {
+        const Philox4 r = philox4x32_10((unsigned)v >> 2, p, o0, o1, k0, k1);
+        const unsigned lo = (v & 1) ? r.w[1] : r.w[0], hi = (v & 1) ? r.w[3] : r.w[2];
+        q.v = perturbed(c.v, (v & 2) ? hi : lo);
+      }
+      if (v < k.ts_begin) { bt = better(bt, c); pt = better(pt, q); } else { bs = better(bs, c); ps = better(ps, q); }
+    }
+  }
+  bt = wave_best(bt);
+  bs = wave_best(bs);
+  pt = wave_best(pt);
+  ps = wave_best(ps);
+  if (lane == 0) { red[0][wave] = bt; red[1][wave] = bs; red[2][wave] = pt; red[3][wave] = ps; }
+  __syncthreads();
+  bt = red[0][0]; bs = red[1][0]; pt = red[2][0]; ps = red[3][0];
+  for (int w = 1; w < 4; ++w) { bt = better(bt, red[0][w]); bs = better(bs, red[1][w]); pt = better(pt, red[2][w]); ps = better(ps, red[3][w]); }
+  // ---- pass 2: sum of exp(x - slice max) over the slice's timestamp tokens (unscaled: sampler_part_kernel's, operation for operation) ----
+  float sum = 0.f;
+  if (a.timestamps && bs.v > -INFINITY) {
+    if (vec_ok) {
+#pragma unroll
+      for (int it = 0; it < SAMPLER_IT; ++it) {
+        const int v = v0 + (it * 256 + tid) * 2;
+        if (v < v1) {
+          if (v >= k.ts_begin) sum += expf(s0[it] - bs.v);
+          if (v + 1 >= k.ts_begin) sum += expf(s1[it] - bs.v);
+        }
+      }
+    } else {
+      for (int v = max(v0, k.ts_begin) + tid; v < v1; v += 256)
+        sum += score_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? 0.f : expf(lg[v] - bs.v);
+    }
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red_sum[wave] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    SamplePartial o;
+    o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i;
+    o.sum = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
+    o.pt_v = pt.v; o.pt_i = pt.i; o.ps_v = ps.v; o.ps_i = ps.i;
+    o.pad_[0] = o.pad_[1] = o.pad_[2] = 0;
+    sa.parts[b * SAMPLER_NS_MAX + part] = o;
+  }
+}
+
+// merge of the vocabulary slices of row b by one wavefront (all 64 lanes): the mass decision on the unscaled partials in sampler_merge's
+// order and operations, the token from the perturbed ones
+__device__ __forceinline__ int sample_merge(const SampleArgs& sa, int b, int lane) {
+  const SamplerArgs& a = sa.s;
+  SamplePartial p = sa.parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
+  const bool on = lane < a.n_slices;
+  MaxIdx bt{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, bs{on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff};
+  MaxIdx pt{on ? p.pt_v : -INFINITY, on ? p.pt_i : 0x7fffffff}, ps{on ? p.ps_v : -INFINITY, on ? p.ps_i : 0x7fffffff};
+  const float my_m = bs.v;
+  bt = wave_best(bt);
+  bs = wave_best(bs);
+  pt = wave_best(pt);
+  ps = wave_best(ps);
+  float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - bs.v) : 0.f;  // log-sum-exp merge of the slices
+  const float tot = wave_sum(part_sum);
+  bool force_ts = false;
+  if (a.timestamps && bs.v > -INFINITY) force_ts = (bs.v + logf(tot)) > bt.v;
+  int choice = force_ts ? ps.i : better(pt, ps).i;   // (text ids lie below timestamp ids: a tie goes to the text token)
+  if (choice == 0x7fffffff) choice = 0;  // everything masked
+  return choice;
+}
+
+__global__ __launch_bounds__(1024) void sample_finish_kernel(SampleArgs sa) {
+  const SamplerArgs& a = sa.s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int pos_now = a.stt->pos;              // (thread 0 advances it behind the barrier at the end)
+  for (int b = tid >> 6; b < a.B; b += 16) {  // wavefront w <- streams w, w+16, ...
+    int next_id = 0;
+    const SamplerMask k = sampler_mask(a, b);
+    const int choice = sample_merge(sa, b, lane);
+    if (lane == 0) {
+      const int cur_len = a.stt->pos + 1;
+      int* seq = a.seq + (long long)b * a.seq_ld;
+      if (k.in_prompt) {
+        next_id = seq[cur_len];
+        a.cur_ids[b] = next_id;
+      } else if (k.fin) {
+        seq[cur_len] = a.pad;
+        a.cur_ids[b] = a.pad;
+        next_id = a.pad;
+      } else {
+        seq[cur_len] = choice;
+        a.cur_ids[b] = choice;
+        next_id = choice;
+        if (a.timestamps && choice >= k.ts_begin) a.last_ts[b] = choice;
+        if (choice == a.eos) a.finished[b] = 1;
+      }
+    }
+    if (a.x_next) {   // (kernel-uniform) the token just appended is the next step's input at position pos + 1
+      const int id = __builtin_amdgcn_readfirstlane(next_id);   // lane 0's
+      if (a.dtype == 1) embed_row<bf16_t>(a, b, id, pos_now + 1, lane);
+      else if (a.dtype == 2) embed_row<f16_t>(a, b, id, pos_now + 1, lane);
+      else embed_row<float>(a, b, id, pos_now + 1, lane);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) a.stt->pos += 1;
+}
+
 // Scoring (tw_score_tokens, api.hip): log-softmax of the GIVEN next token of every row of a rows-mode launch, twice - over the raw
 // logits, and over the logits after Whisper's processors for that row's history (what HF's _retrieve_avg_logprobs takes its
 // log_softmax of).  Shaped like the sampler for the sampler's reason (exp over 51866 logits is VALU work no single CU does in time):
@@ -2008,6 +2199,19 @@ hipError_t launch_sampler_rows(const SamplerArgs& a0, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sampler_rows_finish_kernel, dim3(1), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sample(const SampleArgs& a0, hipStream_t st) {
+  const SamplerArgs& s = a0.s;
+  if (s.B < 1 || s.B > 64 || s.rows_streams != 0 || !s.suppress_bits || !a0.inv_t || !a0.key || !a0.off || !a0.noisy || !a0.parts)
+    return hipErrorInvalidValue;
+  SampleArgs a = a0;
+  a.s.n_slices = 32;   // the slicing of launch_sampler: the unscaled partials, and the order they are merged in, are the greedy call's
+  hipLaunchKernelGGL((sample_part_kernel<32, 4>), dim3(32, s.B), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1024), 0, st, a);  // also advances the position
   return hipGetLastError();
 }
 

@@ -355,6 +355,28 @@ hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);   // sampler + 
 // rows mode: sampler over every row + the round's decision (see SamplerArgs); the position is NOT advanced unless the round is decided
 hipError_t launch_sampler_rows(const SamplerArgs& a, hipStream_t st);
 hipError_t launch_suppress_bitmap(const int* list, int n, unsigned* bits, int V, hipStream_t st);  // zero + set bits
+// Temperature sampling (tw_generate_sample; k_decode.hip: sample_part_kernel, sample_finish_kernel).  THE DRAW: row b consumes position
+// p and produces the token at p + 1.  x = the float32 logits, masked exactly as the greedy sampler masks them, and the "timestamp mass
+// beats every text token" rule is decided on x itself (HF applies Whisper's processors before the temperature warper).  Among the ids
+// still unmasked
+//   score(v) = x[v] * inv_t[b] + g(v),   g(v) = -logf(-logf(u)),   u = ((w >> 9) * 2 + 1) * 2^-24   (exact in float32, never 0 or 1),
+//   w = output word v & 3 of Philox4x32-10 with counter (v >> 2, p, off[b][0], off[b][1]) and key (key[b][0], key[b][1]),
+// and the token is the LOWEST id that attains the maximum (Gumbel-max: a draw from softmax(x / T) over the unmasked ids); everything
+// masked: id 0, as the greedy sampler returns.  noisy[b] == 0: g = 0 and inv_t[b] = 1, the row is greedy and its tokens are the greedy
+// call's.  The noise depends on (key, off, p, v) alone - not on the slot, the batch, the slicing or graph replay.  Not torch's RNG.
+// The arrays are [B] ([B][2] for key / off) in device memory, so one captured step graph serves every temperature and seed.
+struct SamplePartial {  // per vocabulary slice: the greedy partials of x (bt, bs, sum as in SamplerPartial) + the best perturbed text / timestamp
+  float bt_v; int bt_i; float bs_v; int bs_i; float sum; float pt_v; int pt_i; float ps_v; int ps_i; int pad_[3];
+};
+struct SampleArgs {
+  SamplerArgs s;              // ordinary step only (rows_streams == 0); s.partials is not used
+  const float* inv_t;         // [B] 1 / temperature (host-computed), 1 for greedy rows
+  const uint32_t* key;        // [B][2] Philox key (seed low, high)
+  const uint32_t* off;        // [B][2] Philox counter words 2, 3 (offset low, high)
+  const int* noisy;           // [B] 1: sample, 0: greedy row
+  SamplePartial* parts;       // [B][32] workspace between the two launches
+};
+hipError_t launch_sample(const SampleArgs& a, hipStream_t st);     // sample + pos advance (the bookkeeping of launch_sampler)
 // Scoring of GIVEN tokens (tw_score_tokens): rows mode only.  `s` carries what sampler_mask() needs - logits, V, B rows, seq / seq_ld,
 // stt (n_prompt = the begin index), the processor fields, begin_suppress, suppress_bits, rows_streams, row_pos0, row_lastts - and
 // nothing of the sampler's outputs.  Row r (stream r % rows_streams, position p = row_pos0 + r / rows_streams) with target

@@ -317,6 +317,38 @@ class WhisperEngine:
         return out
 
     # ---- A9/A10 ------------------------------------------------------------------------------
+    @staticmethod
+    def _greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress, min_new_tokens=0,
+                     max_new_tokens=0, max_length=0, want_alignment=False, n_forced=0, n_draft=0):
+        """``tw_greedy_opts`` of a call's keywords (generate_greedy, generate_sample, score_tokens build it here, so they cannot drift);
+        the struct points into the two arrays returned beside it: keep them alive for the call."""
+        o = _cabi.tw_greedy_opts()
+        o.eos_id, o.pad_id = int(eos_id), int(pad_id)
+        o.max_new_tokens, o.min_new_tokens, o.max_length = int(max_new_tokens), int(min_new_tokens), int(max_length)
+        o.timestamps = 1 if timestamps else 0
+        o.no_timestamps_id = int(no_timestamps_id)
+        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+        bs = [int(x) for x in begin_suppress]
+        sp = [int(x) for x in suppress]
+        bs_arr = (C.c_int32 * max(1, len(bs)))(*bs)
+        sp_arr = (C.c_int32 * max(1, len(sp)))(*sp)
+        o.n_begin_suppress, o.begin_suppress = len(bs), bs_arr
+        o.n_suppress, o.suppress = len(sp), sp_arr
+        o.want_alignment = 1 if want_alignment else 0
+        o.n_forced = int(n_forced)
+        o.n_draft = int(n_draft)
+        return o, (bs_arr, sp_arr)
+
+    def _loop_stream(self) -> C.c_void_p:
+        """The decode stream (``_decode_stream``) ordered behind everything enqueued so far (the encoder stage); the generate call
+        synchronises it before returning.  The caller's stream when it manages streams itself or no decode stream exists."""
+        if self.raw_stream is None:
+            ds = self._decode_stream()
+            if ds is not None:
+                torch.cuda.ExternalStream(ds, device=self.device).wait_stream(torch.cuda.current_stream(self.device))
+                return C.c_void_p(ds)
+        return self._sp()
+
     def generate_greedy(
         self,
         prompt: np.ndarray,
@@ -340,31 +372,13 @@ class WhisperEngine:
         batched launches, the call returns what it returns without them; ``draft`` in the result says how many were confirmed."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         B, n0 = prompt.shape
-        o = _cabi.tw_greedy_opts()
-        o.eos_id, o.pad_id = int(eos_id), int(pad_id)
-        o.max_new_tokens, o.min_new_tokens, o.max_length = int(max_new_tokens), int(min_new_tokens), int(max_length)
-        o.timestamps = 1 if timestamps else 0
-        o.no_timestamps_id = int(no_timestamps_id)
-        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-        bs = [int(x) for x in begin_suppress]
-        sp = [int(x) for x in suppress]
-        bs_arr = (C.c_int32 * max(1, len(bs)))(*bs)
-        sp_arr = (C.c_int32 * max(1, len(sp)))(*sp)
-        o.n_begin_suppress, o.begin_suppress = len(bs), bs_arr
-        o.n_suppress, o.suppress = len(sp), sp_arr
-        o.want_alignment = 1 if want_alignment else 0
-        o.n_forced = int(n_forced)
-        o.n_draft = int(n_draft)
+        o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
+                                     min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
         out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
         out_len = C.c_int32(0)
-        sp = self._sp()
         # (calls with a forced prefix stay on the caller's stream: their batched prefill - launches of up to 64 rows - wants the whole
         #  chip; measured on the reuse path's short calls: 16.1 ms per tick there, 19.9 on the 160-CU stream)
-        if self.raw_stream is None and int(n_forced) == 0 and int(n_draft) == 0:
-            ds = self._decode_stream()
-            if ds is not None:      # behind everything enqueued so far (the encoder stage); the call synchronises it before returning
-                torch.cuda.ExternalStream(ds, device=self.device).wait_stream(torch.cuda.current_stream(self.device))
-                sp = C.c_void_p(ds)
+        sp = self._loop_stream() if int(n_forced) == 0 and int(n_draft) == 0 else self._sp()
         rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
                                          out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
                                          sp)
@@ -377,6 +391,37 @@ class WhisperEngine:
             self._chk(self.lib.tw_last_draft(self.ctx, *[C.byref(x) for x in v]), "tw_last_draft")
             res["draft"] = {"offered": int(v[0].value), "accepted": int(v[1].value), "launches": int(v[2].value), "rounds": int(v[3].value)}
         return res
+
+    # ---- temperature sampling ----------------------------------------------------------------
+    def generate_sample(self, prompt: np.ndarray, temperature, seed, offset=None, *, max_new_tokens: int = 128, min_new_tokens: int = 0,
+                        max_length: int = 448, eos_id: int = 50257, pad_id: int = 50257, timestamps: bool = False,
+                        no_timestamps_id: int = 50364, max_initial_timestamp_index: Optional[int] = 50,
+                        begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = (), want_alignment: bool = False,
+                        n_forced: int = 0, n_draft: int = 0) -> Dict[str, np.ndarray]:
+        """``generate_greedy`` with a draw from ``softmax(processed logits / temperature[b])`` per row (tw_generate_sample; the draw is
+        defined in include/thewhisper.h).  ``temperature``, ``seed``, ``offset``: one value per row, or a scalar for every row.
+        ``temperature[b] == 0``: the row is greedy; ``< 0``: the row sits the call out (``pad_id`` from the prompt on).  The noise is a
+        function of (seed, offset, position, token id): a row's result does not depend on its slot or on its batch-mates.  ``n_forced`` /
+        ``n_draft`` are refused by the library."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        B, n0 = prompt.shape
+        rows = [None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dt).reshape(-1), (B,)))
+                for x, dt in ((temperature, np.float32), (seed, np.uint64), (offset, np.uint64))]
+        so = _cabi.tw_sample_opts()
+        so.temperature = rows[0].ctypes.data_as(C.POINTER(C.c_float))
+        so.seed = rows[1].ctypes.data_as(C.POINTER(C.c_uint64))
+        so.offset = rows[2].ctypes.data_as(C.POINTER(C.c_uint64)) if rows[2] is not None else None
+        o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
+                                     min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
+        out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
+        out_len = C.c_int32(0)
+        sp = self._loop_stream()     # the decode stream, as the plain greedy call
+        rc = self.lib.tw_generate_sample(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
+                                         out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+        self._chk(rc, "tw_generate_sample")
+        self._release_held()
+        L = int(out_len.value)
+        return {"sequences": out[:, :L].astype(np.int64), "length": L}
 
     # ---- scores of finished sequences --------------------------------------------------------
     def score_tokens(
@@ -404,17 +449,8 @@ class WhisperEngine:
         (None when no id is given)."""
         seq = np.ascontiguousarray(sequences, dtype=np.int32)
         B, L = seq.shape
-        o = _cabi.tw_greedy_opts()
-        o.eos_id, o.pad_id, o.min_new_tokens = int(eos_id), int(pad_id), int(min_new_tokens)
-        o.timestamps = 1 if timestamps else 0
-        o.no_timestamps_id = int(no_timestamps_id)
-        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-        bs = [int(x) for x in begin_suppress]
-        sp = [int(x) for x in suppress]
-        bs_arr = (C.c_int32 * max(1, len(bs)))(*bs)
-        sp_arr = (C.c_int32 * max(1, len(sp)))(*sp)
-        o.n_begin_suppress, o.begin_suppress = len(bs), bs_arr
-        o.n_suppress, o.suppress = len(sp), sp_arr
+        o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
+                                     min_new_tokens)
         lp = np.zeros((B, L), dtype=np.float32)
         raw = np.zeros((B, L), dtype=np.float32)
         ns = np.zeros((B,), dtype=np.float32) if no_speech_id is not None else None

@@ -462,7 +462,7 @@ class BatchingHub:
 
         while True:
             t_mark = time.perf_counter()
-            pas = shortform.Pass(eng, codec.plan, score=codec.score, no_speech_id=codec.no_speech_id)
+            pas = shortform.Pass(eng, codec.plan, score=codec.score, no_speech_id=codec.no_speech_id, fallback=codec.fallback)
             if pf is not None:
                 pf.pause()            # from here to resume() this thread is the only user of the queue and of the sibling context
                 jobs.extend(j for j in pf.drain_jobs() if j not in jobs)

@@ -61,7 +61,8 @@ class ShortFormPlan:
 class ChunkWork:
     """Decoding state of one <= chunk_length_s piece of audio (one row of a ``generate`` batch)."""
 
-    __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass", "scores")
+    __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass", "scores",
+                 "temperatures", "attempts", "chunk_index")
 
     def __init__(self, feats: torch.Tensor, num_frames: Optional[int], tag: Any = None):
         # SURVEY.md section 8f-3 (opt-in, streaming.py): output tokens of the FIRST seek iteration that are already known - they
@@ -73,6 +74,11 @@ class ChunkWork:
         self.draft_result: Optional[Dict[str, int]] = None
         self.first_pass: Optional[Tuple[np.ndarray, np.ndarray]] = None   # (ids after the prompt, their timestamps) of iteration 1
         self.scores: List[Dict[str, Any]] = []     # ``Pass(score=True)``: one ``score_entries`` entry per seek iteration
+        # ``Pass(fallback=policy)``: per seek iteration the temperature its result was accepted at and the attempts that took;
+        # ``chunk_index``: index of the chunk within its request (the draws' seed is ``policy.seed + chunk_index``)
+        self.temperatures: List[float] = []
+        self.attempts: List[int] = []
+        self.chunk_index = 0
         self.feats = feats                      # [n_mels, frames] log-mel (device tensor); frames = 2 * T for short-form
         self.num_frames = num_frames            # frames of real audio (attention_mask.sum), None if no mask was given
         self.max_frames = int(feats.shape[-1])  # HF:...:1769 - short-form: the padded feature length, not the audio length
@@ -216,11 +222,17 @@ class Pass:
     decodes all slots in one greedy loop and advances every chunk.  A serving loop adds the chunks that need a further
     iteration first and whatever arrives while the GPU is still encoding those; ``run_pass`` is the one-group form.
     ``score`` (opt-in): after the greedy call and the token timestamps, the pass's sequences are scored (``score_entries``) and
-    every chunk's ``scores`` list gains the entry of this iteration; nothing else changes."""
+    every chunk's ``scores`` list gains the entry of this iteration; nothing else changes.
+    ``fallback`` (opt-in, a ``fallback.FallbackPolicy``): ``run()`` drives Whisper's temperature ladder (fallback.py) instead of the one
+    greedy call - rows that fail the policy's checks are decoded again at the next temperature (``generate_sample``; draws seeded by
+    ``policy.seed + chunk_index`` at offset ``seek * 16 + attempt``, so a request's result does not depend on its pass-mates), rows of
+    different attempts are merged (padded to the longest), a row HF would skip as silence adds no segment and advances ``seek`` by its
+    frames, and every chunk's ``temperatures`` / ``attempts`` gain this iteration's.  ``fallback=None`` is the code path described above."""
 
-    def __init__(self, engine, plan: ShortFormPlan, score: bool = False, no_speech_id: Optional[int] = None):
+    def __init__(self, engine, plan: ShortFormPlan, score: bool = False, no_speech_id: Optional[int] = None, fallback=None):
         self.engine, self.plan = engine, plan
         self.score, self.no_speech_id = bool(score), no_speech_id
+        self.fallback = fallback
         self.works: List[ChunkWork] = []
         self.snf: List[int] = []
         self._keep: List[torch.Tensor] = []       # segment tensors stay alive until the pass has run
@@ -302,6 +314,8 @@ class Pass:
                 raise ValueError("a pass takes drafts of ONE length")
             n_draft = lens.pop()
             prompt = np.concatenate([prompt, np.stack([np.asarray(w.draft, dtype=np.int32) for w in works])], axis=1)
+        if self.fallback is not None:
+            return self._run_with_fallback(prompt, n_forced, n_draft, kept_columns)
         t0 = time.perf_counter()
         if n_forced:
             out = engine.generate_greedy(prompt, n_forced=n_forced, **plan.greedy)
@@ -327,7 +341,79 @@ class Pass:
         if self.score:     # (the begin index is the plan's prompt length: forced and drafted tokens count as generated)
             for w, entry in zip(works, score_entries(engine, out["sequences"], n_prompt, plan.greedy, self.no_speech_id)):
                 w.scores.append(entry)
+        self._advance(out, seq, ts)
+
+    def _token_timestamps(self, L: int, kept_columns: Optional[Sequence[int]]) -> torch.Tensor:
+        engine, plan, works = self.engine, self.plan, self.works
+        B, n_prompt = len(works), plan.n_prompt
+        if L - 1 <= n_prompt:
+            return torch.zeros((B, L), dtype=torch.float32)
+        nf = None
+        if kept_columns is not None:
+            nf = columns_as_num_frames(kept_columns)
+        elif works[0].num_frames is not None:
+            nf = columns_as_num_frames([hf_kept_columns([int(w.num_frames) - int(w.seek)], 1, int(engine.T))[0] for w in works])
+        return torch.from_numpy(engine.token_timestamps(B, n_prompt, L, nf, plan.time_precision))
+
+    def _run_with_fallback(self, prompt: np.ndarray, n_forced: int, n_draft: int, kept_columns: Optional[Sequence[int]]) -> None:
+        from . import fallback as fb
+
+        engine, plan, works, policy = self.engine, self.plan, self.works, self.fallback
+        if n_forced:
+            raise ValueError("forced output prefixes and the temperature fallback do not go together (a forced token is not redrawn)")
+        B, n_prompt = len(works), plan.n_prompt
+        base = prompt[:, :n_prompt]
+        row_ts: List[Optional[torch.Tensor]] = [None] * B
+        first_out: Dict[str, Any] = {}
+
+        def first_call():      # attempt 0: the call `fallback=None` would have made (a draft applies to it alone)
+            out = engine.generate_greedy(prompt, n_draft=n_draft, **plan.greedy) if n_draft else engine.generate_greedy(prompt, **plan.greedy)
+            first_out.update(out)
+            return out
+
+        def on_attempt(k, temperature, out, rows):     # the alignment rows belong to the engine call that has just returned
+            if plan.return_token_timestamps and rows:
+                ts = self._token_timestamps(int(np.asarray(out["sequences"]).shape[1]), kept_columns)
+                for b in rows:
+                    row_ts[b] = ts[b]
+
+        t0 = time.perf_counter()
+        res = fb.generate_with_fallback(engine, base, plan.greedy, policy, self.no_speech_id,
+                                        seeds=[int(policy.seed) + int(w.chunk_index) for w in works],
+                                        offsets=[int(w.seek) * 16 for w in works],
+                                        first_call=first_call if policy.temperatures[0] == 0.0 else None, on_attempt=on_attempt)
+        self.greedy_s = time.perf_counter() - t0
+        self._keep.clear()
+        L = max(len(r["sequence"]) for r in res)
+        seq = torch.full((B, L), int(plan.pad), dtype=torch.long)
+        ts = torch.zeros((B, L), dtype=torch.float32) if plan.return_token_timestamps else None
+        for b, r in enumerate(res):
+            n = len(r["sequence"])
+            seq[b, :n] = torch.from_numpy(np.asarray(r["sequence"], dtype=np.int64))
+            if ts is not None:
+                ts[b, :n] = row_ts[b]
+                if n < L and n > 0:
+                    ts[b, n:] = row_ts[b][-1]
+        self.last_fallback = res
+        for w, r in zip(works, res):
+            w.temperatures.append(r["temperature"])
+            w.attempts.append(r["attempts"])
+            if self.score:
+                w.scores.append(r["score"])
+        self._advance(first_out, seq, ts, skip=[r["should_skip"] for r in res])
+
+    def _advance(self, out: Dict[str, Any], seq: torch.Tensor, ts: Optional[torch.Tensor], skip: Optional[Sequence[bool]] = None) -> None:
+        """Slice every row's ids at the timestamp tokens and advance its chunk (the tail of ``run``)."""
+        plan, works, snf, n_prompt = self.plan, self.works, self.snf, self.plan.n_prompt
         for i, w in enumerate(works):
+            if skip is not None and skip[i]:      # HF:...:820-826: silence - no segment, seek advances by the segment's frames
+                w.seek += snf[i]
+                w.passes += 1
+                w.forced = None
+                if w.draft is not None:
+                    w.draft_result = out.get("draft")
+                    w.draft = None
+                continue
             if plan.result_is_dict:
                 result: Any = {"sequences": seq[i]}
                 if ts is not None:
@@ -378,12 +464,12 @@ def first_segment(work: ChunkWork, T: int) -> torch.Tensor:
 
 
 def run_pass(engine, plan: ShortFormPlan, works: Sequence[ChunkWork], kept_columns: Optional[Sequence[int]] = None,
-             score: bool = False, no_speech_id: Optional[int] = None) -> None:
+             score: bool = False, no_speech_id: Optional[int] = None, fallback=None) -> None:
     """One seek iteration for every work in ``works`` (all unfinished, len <= engine.max_batch): segment cut-out, encoder +
     cross-K/V + greedy loop (+ token timestamps) on the engine, segment slicing, seek advance."""
     if len(works) < 1 or len(works) > engine.max_batch:
         raise ValueError(f"a pass takes 1..{engine.max_batch} chunks, got {len(works)}")
-    p = Pass(engine, plan, score=score, no_speech_id=no_speech_id)
+    p = Pass(engine, plan, score=score, no_speech_id=no_speech_id, fallback=fallback)
     p.add(works)
     p.run(kept_columns)
 
@@ -432,15 +518,18 @@ def assemble(plan: ShortFormPlan, works: Sequence[ChunkWork], device) -> Any:
 
 
 def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                       scores_out: Optional[List[Dict[str, Any]]] = None, no_speech_id: Optional[int] = None) -> Any:
+                       scores_out: Optional[List[Dict[str, Any]]] = None, no_speech_id: Optional[int] = None, fallback=None) -> Any:
     """Drop-in for ``WhisperGenerationMixin.generate`` on an eligible batch: identical return value, fewer Python layers.
     ``scores_out`` (a list): every pass also scores its tokens (``Pass(score=True)``) and the entries are appended to it, row by row,
-    a row's seek iterations in order."""
+    a row's seek iterations in order.  ``fallback`` (a ``fallback.FallbackPolicy``): every pass drives the temperature ladder
+    (``Pass(fallback=...)``); row i of the batch is chunk i of the request."""
     B = int(input_features.shape[0])
     nf: List[Optional[int]] = [None] * B
     if plan.return_token_timestamps and attention_mask is not None:
         nf = [int(x) for x in attention_mask.sum(-1).cpu().tolist()]          # HF:...:1694-1695
     works = [ChunkWork(input_features[i], nf[i]) for i in range(B)]
+    for i, w in enumerate(works):
+        w.chunk_index = i
     cap = int(engine.max_batch)
     while True:
         active = [w for w in works if not w.done]                              # HF:...:790-795 (the batch shrinks)
@@ -452,7 +541,7 @@ def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor
             cols = hf_kept_columns([int(w.num_frames) - int(w.seek) for w in active], len(active), int(engine.T))
         for i in range(0, len(active), cap):                                   # a call wider than the engine: several passes per iteration
             run_pass(engine, plan, active[i : i + cap], None if cols is None else cols[i : i + cap],
-                     score=scores_out is not None, no_speech_id=no_speech_id)
+                     score=scores_out is not None, no_speech_id=no_speech_id, fallback=fallback)
         if any(w.passes > MAX_SEEK_PASSES for w in active):
             # a decoder that keeps closing its segments at <|0.00|> never advances `seek`; HF's loop spins forever on such a row
             raise RuntimeError(f"a chunk needed more than {MAX_SEEK_PASSES} seek passes (the decoder keeps seeking to frame 0)")

@@ -41,6 +41,7 @@ class AMDWhisperBackend:
         draft_previous_tick: Optional[bool] = None,
         resample_kernel=None,
         token_scores: bool = False,
+        temperature_fallback=None,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -70,7 +71,16 @@ class AMDWhisperBackend:
         ``token_scores`` (opt-in): every greedy call of a ``transcribe`` / ``transcribe_many`` is followed by a re-scoring pass
         (tw_score_tokens) and ``last_scores`` holds, for the most recent call, one entry per seek iteration of every chunk -
         ``{tokens, logprob, logprob_raw, avg_logprob, no_speech_prob}`` (shortform.score_entries).  The returned words are what
-        they are with the option off: the scores travel beside them."""
+        they are with the option off: the scores travel beside them.
+
+        ``temperature_fallback`` (opt-in; None | ``fallback.FallbackPolicy`` | a tuple of temperatures): Whisper's own repair of a
+        segment that loops or hallucinates (HF ``generate_with_fallback``) instead of only dropping a looping tick in ``_to_tokens``:
+        every seek iteration is measured (compression ratio, average log-probability, optionally the no-speech probability) and the
+        chunks that fail are decoded again at the next temperature by the engine's sampler (fallback.py, ``shortform.Pass(fallback=)``).
+        The call then ALWAYS runs the restated short-form loop; a backend whose call is not eligible for it (``job_codec()`` is None)
+        raises ``ValueError`` rather than run without the option.  A draft (``draft_previous_tick``) applies to the first attempt only;
+        not together with ``reuse_committed_prefix`` (a forced token is not redrawn).  ``last_fallback``: for the most recent call, one
+        ``{temperature, attempts}`` per seek iteration of every chunk."""
         from .asr_pipeline import ASRPipeline
 
         if torch_dtype is None:
@@ -105,6 +115,12 @@ class AMDWhisperBackend:
         self._resample_kernel = resample_kernel   # tests: the numpy restatement in place of tw_resample (resample.py)
         self.token_scores = bool(token_scores)
         self.last_scores: List[Dict[str, Any]] = []
+        from .fallback import as_policy
+
+        self.temperature_fallback = as_policy(temperature_fallback)
+        if self.temperature_fallback is not None and self.reuse_committed_prefix:
+            raise ValueError("temperature_fallback and reuse_committed_prefix do not go together (a forced token is not redrawn)")
+        self.last_fallback: List[Dict[str, Any]] = []
         self._no_speech_id: Any = False           # not looked up yet
 
     def to_engine_rate(self, audio, sample_rate: int):
@@ -153,10 +169,13 @@ class AMDWhisperBackend:
 
     def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
         audio, sample_rate = self.to_engine_rate(audio, sample_rate)
-        if self.reuse_committed_prefix or self.draft_previous_tick:
+        if self.reuse_committed_prefix or self.draft_previous_tick or self.temperature_fallback is not None:
             words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate))
             if words is not None:
                 return words
+            if self.temperature_fallback is not None:
+                raise ValueError("temperature_fallback needs the restated short-form loop, and this backend's call is not eligible for it "
+                                 "(job_codec() is None)")
         result: Dict[str, Any] = self._run_pipeline(
             audio,
             return_timestamps="word",
@@ -220,6 +239,8 @@ class AMDWhisperBackend:
         if len(job.works) != 1:
             self._last = None
             forced = None
+        elif not (self.reuse_committed_prefix or self.draft_previous_tick):     # (here for temperature_fallback alone)
+            forced = None
         else:
             forced = self._forced_prefix(audio, buffer_start_time, sample_rate)
             budget = int(codec.plan.greedy.get("max_new_tokens", 128))
@@ -237,10 +258,10 @@ class AMDWhisperBackend:
                 self.reuse_stats["forced_tokens"] += int(len(forced))
         while not job.done:
             for w in [w for w in job.works if not w.done]:
-                shortform.run_pass(eng, codec.plan, [w], score=codec.score, no_speech_id=codec.no_speech_id)
+                shortform.run_pass(eng, codec.plan, [w], score=codec.score, no_speech_id=codec.no_speech_id, fallback=codec.fallback)
                 if w.passes > shortform.MAX_SEEK_PASSES:
                     raise RuntimeError(f"a chunk needed more than {shortform.MAX_SEEK_PASSES} seek passes")
-        if len(job.works) == 1 and job.works[0].first_pass is not None:
+        if len(job.works) == 1 and job.works[0].first_pass is not None and (self.reuse_committed_prefix or self.draft_previous_tick):
             ids, ts = job.works[0].first_pass
             dr = job.works[0].draft_result
             if dr is not None:
@@ -252,11 +273,19 @@ class AMDWhisperBackend:
         words = codec.close(job)
         if self.token_scores:
             self.last_scores = job.scores
+        self.last_fallback = job.fallback
         return words
 
     def transcribe_many(self, requests, batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """Several streams' rolling buffers in ONE pipeline call: [(audio, buffer_start_time, sample_rate), ...].
         HF collates the chunks of different buffers into batched engine calls; per-stream results are unchanged."""
+        if self.temperature_fallback is not None:      # (HF's batched call knows nothing of the option: one short-form call per request)
+            out, log = [], []
+            for a, t0, sr in requests:
+                out.append(self.transcribe(a, t0, sr))
+                log.extend(self.last_fallback)
+            self.last_fallback = log
+            return out
         requests = [(self.to_engine_rate(a, sr)[0], t0, self.sample_rate) for a, t0, sr in requests]
         audios = [np.asarray(a) for a, _, _ in requests]
         kw = {} if batch_size is None else {"batch_size": int(batch_size)}
@@ -302,7 +331,7 @@ class _NotEligible(Exception):
 class BufferJob:
     """One ``transcribe`` request on its way through the hub: its chunks' decoding states and what post-processing needs."""
 
-    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit", "scores")
+    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit", "scores", "fallback")
 
     def __init__(self, works, meta, audio_duration, buffer_start_time):
         self.works = works                        # [shortform.ChunkWork] - one per <= chunk_length_s piece of the buffer
@@ -312,6 +341,7 @@ class BufferJob:
         self.future = None
         self.t_submit = 0.0
         self.scores: List[Dict[str, Any]] = []     # JobCodec.close: the chunks' score entries when the backend asked for them
+        self.fallback: List[Dict[str, Any]] = []   # JobCodec.close: {temperature, attempts} per seek iteration (temperature_fallback)
 
     @property
     def done(self) -> bool:
@@ -339,7 +369,10 @@ class JobCodec:
         self.plan = None
         # AMDWhisperBackend(token_scores=True): whoever runs this codec's jobs builds its passes with Pass(score=..., no_speech_id=...)
         self.score = bool(getattr(backend, "token_scores", False))
-        self.no_speech_id = backend.no_speech_id if self.score else None
+        # AMDWhisperBackend(temperature_fallback=...): ... and with Pass(fallback=...); chunk i of a request draws with seed policy.seed + i
+        self.fallback = getattr(backend, "temperature_fallback", None)
+        needs_ns = self.score or (self.fallback is not None and self.fallback.no_speech_threshold is not None)
+        self.no_speech_id = backend.no_speech_id if needs_ns else None
 
     def learn(self) -> bool:
         """One short request through the ordinary pipeline call: HF's ``generate`` runs once with this backend's options and
@@ -348,11 +381,14 @@ class JobCodec:
         model.last_plan = None
         b = self.backend
         mode = (b.reuse_committed_prefix, b.draft_previous_tick)     # (the ORDINARY call: the reuse / draft paths bypass HF's generate)
+        policy = getattr(b, "temperature_fallback", None)            # (... and so does the temperature fallback)
         b.reuse_committed_prefix = b.draft_previous_tick = False
+        b.temperature_fallback = None
         try:
             b.transcribe(np.zeros(b.sample_rate, dtype=np.float32), 0.0, b.sample_rate)
         finally:
             b.reuse_committed_prefix, b.draft_previous_tick = mode
+            b.temperature_fallback = policy
         plan = model.last_plan
         if plan is None or not plan.return_token_timestamps or not plan.return_segments:
             return False
@@ -371,6 +407,7 @@ class JobCodec:
             am = item.get("attention_mask")
             nf = int(am.sum()) if am is not None else None
             works.append(ChunkWork(feats[0], nf))
+            works[-1].chunk_index = len(works) - 1
             meta.append((item["is_last"], item.get("stride")))
         if not works:
             raise ValueError("empty audio buffer")
@@ -388,5 +425,6 @@ class JobCodec:
                 o["stride"] = stride
             outs.append(o)
         job.scores = [e for w in job.works for e in w.scores]
+        job.fallback = [{"temperature": t, "attempts": a} for w in job.works for t, a in zip(w.temperatures, w.attempts)]
         result = self.pipe.postprocess(outs, **self.post)
         return AMDWhisperBackend._to_tokens(result, job.audio_duration, job.buffer_start_time)

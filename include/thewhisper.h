@@ -277,6 +277,10 @@ int tw_token_timestamps(tw_ctx* ctx, int32_t B, int32_t n_prompt, int32_t seq_le
                         double time_precision, float* out_ts_host, void* stream);
 /* Debug/parity access: copy the recorded alignment rows [B, n_align_heads, n_rows, T] (float32) to host. */
 int tw_get_alignment(tw_ctx* ctx, int32_t B, int32_t n_rows, float* out_host, void* stream);
+/* Its mirror: copy host float32 [B, n_align_heads, n_rows, T] into rows 0 .. n_rows-1 of slots 0 .. B-1 of the recorded-alignment
+ * buffer (every other row keeps what it held), so that tw_token_timestamps can be run on a chosen surface without a decode.
+ * Same argument checks and error codes as the getter; synchronises the stream once. */
+int tw_set_alignment(tw_ctx* ctx, int32_t B, int32_t n_rows, const float* in_host, void* stream);
 
 /* Per-stage device timings (milliseconds, HIP events on the call's stream) of the most recent call
  * of each kind: [0]=logmel [1]=encode [2]=cross_kv [3]=greedy loop [4]=token_timestamps; also the

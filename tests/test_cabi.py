@@ -19,7 +19,7 @@ def test_header_symbols_are_exported(built_library):
     lib = ctypes.CDLL(built_library)
     names = header_functions()
     assert {"tw_create", "tw_logmel", "tw_encode", "tw_cross_kv", "tw_decode_step", "tw_generate_greedy",
-            "tw_token_timestamps"} <= set(names)
+            "tw_token_timestamps", "tw_get_alignment", "tw_set_alignment"} <= set(names)
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/thewhisper.h but not exported"
 

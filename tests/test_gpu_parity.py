@@ -860,6 +860,7 @@ def test_c_abi_error_behaviour():
         # word timestamps without recorded alignment rows
         ts = np.zeros((2, 8), np.float32)
         refused(lib.tw_token_timestamps(ctx, 2, 3, 8, None, 0.02, ts.ctypes.data_as(C.POINTER(C.c_float)), sp))
+        refused(lib.tw_set_alignment(ctx, 2, 7, ts.ctypes.data_as(C.POINTER(C.c_float)), sp))           # a context without alignment heads
         # unknown weight name / wrong shape after construction
         t = torch.zeros(4, device="cuda")
         shape = (C.c_int64 * 1)(4)

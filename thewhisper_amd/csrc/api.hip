@@ -1580,6 +1580,21 @@ int tw_get_alignment(tw_ctx* c, int32_t B, int32_t n_rows, float* out_host, void
   return TW_OK;
 }
 
+int tw_set_alignment(tw_ctx* c, int32_t B, int32_t n_rows, const float* in_host, void* stream) {
+  if (!c || !in_host) return TW_EINVAL;
+  TW_ON_DEVICE(c);
+  if (c->Ha == 0) return fail(c, TW_EINVAL, "context has no alignment heads");
+  if (B < 1 || B > c->Bmax || n_rows < 1 || n_rows > c->P) return fail(c, TW_EINVAL, "bad B/n_rows");
+  hipStream_t st = pick_stream(c, stream);
+  const size_t T = c->T, P = c->P, Ha = c->Ha;
+  for (int b = 0; b < B; ++b)
+    for (size_t h = 0; h < Ha; ++h)
+      HIPCHK(c, hipMemcpyAsync(c->align + ((size_t)b * Ha + h) * P * T, in_host + ((size_t)b * Ha + h) * n_rows * T,
+                               sizeof(float) * n_rows * T, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return TW_OK;
+}
+
 int tw_token_timestamps(tw_ctx* c, int32_t B, int32_t n_prompt, int32_t seq_len, const int32_t* num_frames_host,
                         double time_precision, float* out_ts_host, void* stream) {
   if (!c || !out_ts_host) return fail(c, TW_EINVAL, "tw_token_timestamps: null argument");

@@ -2,7 +2,7 @@
 //
 //   rows [n_prompt, n_rows) of the alignment-head cross-attention probabilities, cropped to n_cols[b]
 //   columns -> z-score over the token axis (population std) -> median filter width 7 over time
-//   (reflect padding) -> mean over heads -> DTW on the negated matrix -> jump times.
+//   (reflect padding, NaN sorted last) -> mean over heads -> DTW on the negated matrix -> jump times.
 //
 // The reference runs the DTW as an O(N*M) pure-Python double loop on the host.  Here the three
 // dependencies of a cell lie on the two previous anti-diagonals, so one workgroup per stream sweeps
@@ -31,8 +31,12 @@ __global__ void align_zscore_kernel(DtwArgs a) {
   for (int i = 0; i < N; ++i) dst[(long long)i * a.T] = (src[(long long)i * a.T] - mean) / sd;
 }
 
+// Orders NaN LAST, as the reference's sort does (torch.sort; HF:models/whisper/generation_whisper.py:58): a column whose
+// probability is the same in every row z-scores to 0/0, and that NaN has to drop out of its neighbours' windows (or, with four
+// of them in a window, BE the median).  fminf / fmaxf would replace it by a copy of the value it meets.
 __device__ __forceinline__ void cswap(float& x, float& y) {
-  const float lo = fminf(x, y), hi = fmaxf(x, y);
+  const bool swap = x != x || y < x;
+  const float lo = swap ? y : x, hi = swap ? x : y;
   x = lo; y = hi;
 }
 

@@ -481,6 +481,14 @@ class WhisperEngine:
         self._chk(rc, "tw_get_alignment")
         return out
 
+    def set_alignment(self, arr: np.ndarray) -> None:
+        """Debug/parity: put float32 [B, n_align_heads, n_rows, T] into rows 0 .. n_rows-1 of the recorded-alignment buffer."""
+        a = np.ascontiguousarray(arr, dtype=np.float32)
+        if a.ndim != 4 or a.shape[1] != len(self.alignment_heads) or a.shape[3] != self.T:
+            raise ValueError(f"alignment rows must be [B, {len(self.alignment_heads)}, n_rows, {self.T}], got {a.shape}")
+        rc = self.lib.tw_set_alignment(self.ctx, a.shape[0], a.shape[2], a.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
+        self._chk(rc, "tw_set_alignment")
+
     def last_timings(self) -> Dict[str, float]:
         ms = (C.c_float * 5)()
         steps = C.c_int32(0)

@@ -217,7 +217,7 @@ int tw_generate_greedy(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32
  * The noise depends on (seed, offset, position, id) alone - not on the slot, the other rows of the batch or graph replay - so a
  * stream's result does not depend on what else is in its batch.  This is NOT torch's generator: no bit parity with
  * torch.multinomial is claimed or possible; and the draw is from the FULL distribution, as openai/whisper's, where HF's sampling
- * also applies top_k = 50 by default.
+ * also applies top_k = 50 by default: tw_generate_sample_filtered below narrows the candidate set.
  *
  * Outputs as tw_generate_greedy's; want_alignment is honoured (tw_token_timestamps works after it); tw_last_timings[3] and the step
  * count are filled.  TW_EINVAL: n_forced or n_draft set, a NaN or infinite temperature or one so small that 1 / T is not finite, every
@@ -229,6 +229,41 @@ typedef struct tw_sample_opts {
 } tw_sample_opts;
 int tw_generate_sample(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
                        const tw_sample_opts* sopts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
+
+/* tw_generate_sample with top-k and nucleus (top-p) filtering of the candidate set.  Replaces: the TopKLogitsWarper and
+ * TopPLogitsWarper HF puts behind the TemperatureLogitsWarper, in that order (HF:generation/utils.py:1293-1321); top_k = 50 is what
+ * HF's generate resolves to when nothing is set.
+ *
+ * THE RULE.  Row b at position p; x = the float32 logits after exactly the mask of tw_generate_sample, "the timestamp mass beats
+ * every text token" included (decided on the unscaled logits, bit-equal to the greedy and unfiltered calls on equal logits); S = the
+ * ids still unmasked.
+ *   Top-k, top_k[b] = k > 0: tau = the k-th largest value of x over S, counted with multiplicity; tau = -inf if |S| <= k;
+ *     K = { v in S : x[v] >= tau }.  Ties at tau are all kept (HF's `scores < topk(scores, k)[-1]` removes nothing equal to it).  The
+ *     comparison is on the unscaled float32 x: scaling by inv_t > 0 is monotone, so only ties created by rounding could differ from
+ *     HF, and x is what every other rule of this sampler is decided on.  K is an exact function of the logits.  k = 0: off (K = S);
+ *     k > V acts as V.
+ *   Top-p, 0 < top_p[b] < 1, applied to K: y[v] = x[v] * inv_t[b] rounded to float32 (the product the draw perturbs), m = max of y
+ *     over K, e[v] = exp(y[v] - m), Z = sum of e over K, G(v) = sum of e[u] over the u in K with y[u] > y[v] (strict: equal values
+ *     share their fate); v is kept iff G(v) < top_p * Z.  The maximum is always kept (HF's min_tokens_to_keep = 1).  In exact
+ *     arithmetic this is HF's `cumsum(softmax(sorted ascending)) <= 1 - top_p` removal.  The library evaluates e in float32 and the
+ *     sums in double precision; a membership whose G / Z lies within about 1e-5 of top_p may fall either way.  top_p = 1: off.
+ *   The token is the lowest id that attains the maximum of score(v) = x[v] * inv_t[b] + g(v) over the kept ids: the noise is
+ *     tw_generate_sample's, the same Philox words for (seed, offset, position, id).
+ * Rows with temperature 0 are greedy and ignore the filters (the arg-max is always kept); rows with a negative temperature sit the
+ * call out; everything masked: id 0.  A row with both filters off produces tw_generate_sample's token for the same seed, bit for bit,
+ * whatever the other rows set.  fopts == NULL, or no sampled row with a filter on: the call IS tw_generate_sample, launch for launch.
+ * Otherwise a step issues one launch more (the row is filtered in the registers of one workgroup) and captured step graphs are kept
+ * apart from the unfiltered call's.  The filter holds vocabularies of up to 65536 ids (every Whisper vocabulary fits).
+ *
+ * Outputs, want_alignment, timings, the step count and the error codes as tw_generate_sample's.  TW_EINVAL in addition: a negative
+ * top_k, a top_p that is NaN or outside (0, 1], a filter on in a context whose vocabulary exceeds 65536 ids. */
+typedef struct tw_filter_opts {
+  const int32_t* top_k;   /* host [B]; 0 = off; NULL = off for every row */
+  const float*   top_p;   /* host [B]; 1.0f = off; NULL = off for every row */
+} tw_filter_opts;
+int tw_generate_sample_filtered(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
+                                const tw_sample_opts* sopts, const tw_filter_opts* fopts, int32_t* out_ids_host,
+                                int32_t* out_len_host, void* stream);
 
 /* Of the most recent tw_generate_greedy with n_draft > 0 (all streams together): draft tokens offered, draft tokens confirmed, rows-mode
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */

@@ -43,6 +43,10 @@ class tw_sample_opts(C.Structure):
     _fields_ = [("temperature", C.POINTER(C.c_float)), ("seed", C.POINTER(C.c_uint64)), ("offset", C.POINTER(C.c_uint64))]
 
 
+class tw_filter_opts(C.Structure):
+    _fields_ = [("top_k", C.POINTER(C.c_int32)), ("top_p", C.POINTER(C.c_float))]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -65,6 +69,9 @@ SYMBOLS = [
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
+                                              C.POINTER(tw_sample_opts), C.POINTER(tw_filter_opts), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), _P]),
     ("tw_last_draft", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("tw_score_tokens", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(tw_greedy_opts),
                                   C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),

@@ -95,6 +95,8 @@ struct tw_ctx {
   // tw_generate_sample: per-row temperature reciprocals, Philox keys / offsets, noisy flags (uploaded per call) and the slice partials
   float* sample_inv_t = nullptr; uint32_t* sample_key = nullptr; uint32_t* sample_off = nullptr; int* sample_noisy = nullptr;   // [64], [64][2], [64][2], [64]
   SamplePartial* sample_parts = nullptr;   // [64][32]
+  // tw_generate_sample_filtered: per-row top-k / top-p (uploaded per call) and the filter kernel's choice
+  int* filter_top_k = nullptr; float* filter_top_p = nullptr; int* filter_choice = nullptr;   // [64] each
   unsigned* suppress_bits = nullptr;  // [(V+31)/32] static suppress list as a bitmap, rebuilt per generate call
   int* h_pinned = nullptr;  // pinned host scratch: finished ring [8][64] | n_valid [64] | DecState upload [16]
   int* row_ids = nullptr;   // device token table of a prefill (position-major), row_ids_cap ints
@@ -117,6 +119,7 @@ struct tw_ctx {
   int row_cap = 0;          // rows the per-token activation buffers hold (>= max_batch; 64 for the prefill launches)
   int* h_stage = nullptr;   // pinned staging of tw_generate_greedy: token table [Bmax][P] (up and down) | 3 x [Bmax] | suppress lists | DecState
                             // | tw_generate_sample: inv_t [64] | key [64][2] | off [64][2] | noisy [64]
+                            // | tw_generate_sample_filtered: top_k [64] | top_p [64]
   size_t h_stage_ints = 0;
   hipEvent_t ring_ev[8]{};
   int last_seq_len = 0, last_n_prompt = 0;
@@ -329,7 +332,7 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   for (int i = 0; i < 5; ++i) { CHIP(hipEventCreate(&c->ev0[i])); CHIP(hipEventCreate(&c->ev1[i])); }
   for (int i = 0; i < 8; ++i) CHIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
   CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), sizeof(int) * (8 * 64 + 64 + 16), hipHostMallocDefault));
-  c->h_stage_ints = (size_t)c->Bmax * c->P + 3 * (size_t)c->Bmax + 64 + 1024 + 16 + 6 * 64;
+  c->h_stage_ints = (size_t)c->Bmax * c->P + 3 * (size_t)c->Bmax + 64 + 1024 + 16 + 6 * 64 + 2 * 64;
   CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), sizeof(int) * c->h_stage_ints, hipHostMallocDefault));
 
   const size_t e = c->esz;
@@ -481,6 +484,7 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CALLOC(c->sampler_partials, 64 * 32 * sizeof(SamplerPartial), true);
   CALLOC(c->sample_inv_t, 64 * 4, true); CALLOC(c->sample_key, 128 * 4, true); CALLOC(c->sample_off, 128 * 4, true);
   CALLOC(c->sample_noisy, 64 * 4, true); CALLOC(c->sample_parts, 64 * 32 * sizeof(SamplePartial), true);
+  CALLOC(c->filter_top_k, 64 * 4, true); CALLOC(c->filter_top_p, 64 * 4, true); CALLOC(c->filter_choice, 64 * 4, true);
   CALLOC(c->score_seq, B * P * 4, true); CALLOC(c->score_bsup, 64 * 4, true); CALLOC(c->score_sup, 1024 * 4, true);
   CALLOC(c->score_bits, ((V + 31) / 32 + 2048) * 4, true);
   CALLOC(c->score_parts, 64 * 32 * sizeof(ScorePartial), true);
@@ -1140,10 +1144,11 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
 
 // The generation loop of tw_generate_greedy and tw_generate_sample.  so == nullptr: the greedy call, launch for launch what it has always
 // issued.  so != nullptr (validated by tw_generate_sample: no forced / draft tokens, finite temperatures, a live row): every step's
-// sampler is launch_sample; rows with temperature < 0 start finished.
+// sampler is launch_sample; rows with temperature < 0 start finished.  fo != nullptr (validated by tw_generate_sample_filtered, which
+// hands it on only when some sampled row has a filter on): every step's sampler is launch_sample_filtered.
 static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
-                         int32_t* out_ids, int32_t* out_len, void* stream) {
-  const char* fn = so ? "tw_generate_sample" : "tw_generate_greedy";
+                         const tw_filter_opts* fo, int32_t* out_ids, int32_t* out_len, void* stream) {
+  const char* fn = fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
   if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
   if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
@@ -1180,6 +1185,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   uint32_t* h_key = reinterpret_cast<uint32_t*>(h_inv_t + 64);    // [64][2]
   uint32_t* h_off = h_key + 128;                                  // [64][2]
   int* h_noisy = reinterpret_cast<int*>(h_off + 128);             // [64]
+  int* h_top_k = h_noisy + 64;                                    // [64]
+  float* h_top_p = reinterpret_cast<float*>(h_top_k + 64);        // [64]
   for (size_t i = 0; i < (size_t)B * P; ++i) hseq[i] = o->pad_id;
   for (int b = 0; b < B; ++b) {
     for (int i = 0; i < n_prompt; ++i) {
@@ -1198,6 +1205,10 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       const uint64_t sd = so->seed ? so->seed[b] : 0, of = so->offset ? so->offset[b] : 0;
       h_key[2 * b] = (uint32_t)sd; h_key[2 * b + 1] = (uint32_t)(sd >> 32);
       h_off[2 * b] = (uint32_t)of; h_off[2 * b + 1] = (uint32_t)(of >> 32);
+      if (fo) {   // (a greedy row ignores the filters: its arg-max is always kept)
+        h_top_k[b] = (t > 0.f && fo->top_k) ? fo->top_k[b] : 0;
+        h_top_p[b] = (t > 0.f && fo->top_p) ? fo->top_p[b] : 1.0f;
+      }
     }
     for (int i = n_begin; i < n_prompt; ++i) {   // state the sampler would have after producing the forced tokens itself
       const int t = prompt[(size_t)b * n_prompt + i];
@@ -1214,6 +1225,10 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     HIPCHK(c, hipMemcpyAsync(c->sample_key, h_key, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->sample_off, h_off, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->sample_noisy, h_noisy, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  }
+  if (fo) {
+    HIPCHK(c, hipMemcpyAsync(c->filter_top_k, h_top_k, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->filter_top_p, h_top_p, sizeof(float) * B, hipMemcpyHostToDevice, st));
   }
   if (o->n_begin_suppress > 0) {
     memcpy(bsup, o->begin_suppress, sizeof(int) * o->n_begin_suppress);
@@ -1281,15 +1296,19 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  // (last field: the sampler flavour - a greedy graph is never replayed for a sampling call, nor the reverse)
+  // (last field: the sampler flavour - greedy, sampling, filtered sampling: a graph of one is never replayed for a call of another)
   snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, so ? 's' : 'g');
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, fo ? 'f' : so ? 's' : 'g');
   SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
   sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
+  FilterArgs fla{};   // ... and every top-k / top-p
+  fla.top_k = c->filter_top_k; fla.top_p = c->filter_top_p; fla.choice = c->filter_choice;
   auto sample_step = [&]() -> hipError_t {
     if (!so) return launch_sampler(sa, st);
     sma.s = sa;
-    return launch_sample(sma, st);
+    if (!fo) return launch_sample(sma, st);
+    fla.sm = sma;
+    return launch_sample_filtered(fla, st);
   };
   const bool use_graph = c->cfg.use_graph != 0;
   if (use_graph && c->step_graph_key != keybuf) {   // other options: the captured sampler arguments are stale
@@ -1425,26 +1444,49 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
                        int32_t* out_ids, int32_t* out_len, void* stream) {
   if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy: null argument");
   TW_ON_DEVICE(c);
-  return generate_loop(c, B, prompt, n_prompt, o, nullptr, out_ids, out_len, stream);
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, out_ids, out_len, stream);
 }
 
-int tw_generate_sample(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
-                       int32_t* out_ids, int32_t* out_len, void* stream) {
+// tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter
+static int generate_sample_checked(const char* fn, tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o,
+                                   const tw_sample_opts* so, const tw_filter_opts* fo, int32_t* out_ids, int32_t* out_len, void* stream) {
   if (!c || !prompt || !o || !so || !so->temperature || !so->seed || !out_ids || !out_len)
-    return fail(c, TW_EINVAL, "tw_generate_sample: null argument");
+    return fail(c, TW_EINVAL, "%s: null argument", fn);
   TW_ON_DEVICE(c);
-  if (B < 1 || B > 64) return fail(c, TW_EINVAL, "tw_generate_sample: %d streams (1..64)", B);
+  if (B < 1 || B > 64) return fail(c, TW_EINVAL, "%s: %d streams (1..64)", fn, B);
   if (o->n_forced != 0 || o->n_draft != 0)
-    return fail(c, TW_EINVAL, "tw_generate_sample: n_forced %d / n_draft %d: forced and draft tokens are for greedy calls", o->n_forced, o->n_draft);
+    return fail(c, TW_EINVAL, "%s: n_forced %d / n_draft %d: forced and draft tokens are for greedy calls", fn, o->n_forced, o->n_draft);
   bool live = false;
   for (int b = 0; b < B; ++b) {
     const float t = so->temperature[b];
     if (!std::isfinite(t) || (t > 0.f && !std::isfinite(1.0f / t)))   // (a subnormal T: 1 / T overflows and the noise would be lost)
-      return fail(c, TW_EINVAL, "tw_generate_sample: temperature of row %d is not finite, or too small for 1 / T to be", b);
+      return fail(c, TW_EINVAL, "%s: temperature of row %d is not finite, or too small for 1 / T to be", fn, b);
     live |= t >= 0.f;
   }
-  if (!live) return fail(c, TW_EINVAL, "tw_generate_sample: every row has a negative temperature (nothing to generate)");
-  return generate_loop(c, B, prompt, n_prompt, o, so, out_ids, out_len, stream);
+  if (!live) return fail(c, TW_EINVAL, "%s: every row has a negative temperature (nothing to generate)", fn);
+  bool filtered = false;   // a filter is on in a row that samples
+  if (fo) {
+    for (int b = 0; b < B; ++b) {
+      const int k = fo->top_k ? fo->top_k[b] : 0;
+      const float p = fo->top_p ? fo->top_p[b] : 1.0f;
+      if (k < 0) return fail(c, TW_EINVAL, "%s: negative top_k %d of row %d (0 = off)", fn, k, b);
+      if (!(p > 0.f && p <= 1.0f)) return fail(c, TW_EINVAL, "%s: top_p %g of row %d is NaN or outside (0, 1] (1 = off)", fn, (double)p, b);
+      filtered |= so->temperature[b] > 0.f && (k > 0 || p < 1.0f);
+    }
+  }
+  if (filtered && c->V > kFilterMaxVocab)
+    return fail(c, TW_EINVAL, "%s: the filter kernel holds %d ids, the vocabulary has %d", fn, kFilterMaxVocab, c->V);
+  return generate_loop(c, B, prompt, n_prompt, o, so, filtered ? fo : nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_sample(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
+                       int32_t* out_ids, int32_t* out_len, void* stream) {
+  return generate_sample_checked("tw_generate_sample", c, B, prompt, n_prompt, o, so, nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_sample_filtered(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o,
+                                const tw_sample_opts* so, const tw_filter_opts* fo, int32_t* out_ids, int32_t* out_len, void* stream) {
+  return generate_sample_checked("tw_generate_sample_filtered", c, B, prompt, n_prompt, o, so, fo, out_ids, out_len, stream);
 }
 
 int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_t seq_len, int32_t n_prompt, const tw_greedy_opts* o,

@@ -1936,6 +1936,238 @@ __global__ __launch_bounds__(1024) void score_finish_kernel(ScoreArgs sa) {
   }
 }
 
+// Top-k / top-p filtered draw (tw_generate_sample_filtered, api.hip; the rule is stated at FilterArgs, tw_common.h): three launches, as
+// kernels of their own so that the temperature sampler's stay as they are.
+//  * sample_part_kernel, unchanged: its unscaled partials carry the mass decision; its perturbed partials are not read.
+//  * sample_filter_kernel: ONE workgroup of 1024 threads per row, the row in registers (kFilterPerThread values per thread, as keys: the
+//    order-preserving integer image of the float, -0 folded onto +0).  Every wavefront repeats sample_merge's mass decision from the
+//    partials; the mask is score_masked_at plus "text out" when the rule fired.  tau: the largest key t with count(key >= t) >= k, bit
+//    by bit from the top (32 rounds, one block count each).  The keys of x then give way to the keys of y = x * inv_t of the ids kept so
+//    far (0: dropped).  Top-p: the smallest key c with sum of exp(y - m) over {key > c} below top_p * Z, by the same search (32 rounds,
+//    one block sum each); a thread's sum runs over its registers in float in a fixed order, the block's over the threads in double in a
+//    fixed tree, so it is monotone in c and H(0) is Z itself, bit for bit.  Last the perturbed arg-max over the kept ids (one Philox
+//    block per four consecutive ids, computed only where one of them is kept) and one choice[b] store.
+//    The slice, the trees and the searches are compile-time shapes: a row's token depends on its logits, its state and its row of the
+//    per-row arrays alone.  Rows still in the prompt, finished rows and rows that sit the call out leave at once.
+//  * sample_choice_finish_kernel: sample_finish_kernel's bookkeeping, line for line, on choice[b].
+__device__ __forceinline__ unsigned filter_key(float x) {
+  const unsigned u = __float_as_uint(x == 0.f ? 0.f : x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float filter_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+constexpr unsigned kFilterNegInfKey = 0x007fffffu;   // filter_key(-inf): masked, or outside the vocabulary
+// x, as a value the compiler knows nothing about: what is derived from it is computed where it is used, not once at the top of the
+// kernel and kept in registers (or scratch) beside the row all the way down
+__device__ __forceinline__ int filter_opaque(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// sample_merge's mass decision (its order and operations on the unscaled partials), in every lane
+__device__ __forceinline__ bool sample_mass_fired(const SampleArgs& sa, int b, int lane) {
+  const SamplerArgs& a = sa.s;
+  SamplePartial p = sa.parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
+  const bool on = lane < a.n_slices;
+  MaxIdx bt{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, bs{on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff};
+  const float my_m = bs.v;
+  bt = wave_best(bt);
+  bs = wave_best(bs);
+  float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - bs.v) : 0.f;  // log-sum-exp merge of the slices
+  const float tot = wave_sum(part_sum);
+  bool force_ts = false;
+  if (a.timestamps && bs.v > -INFINITY) force_ts = (bs.v + logf(tot)) > bt.v;
+  return force_ts;
+}
+
+// the block's sum of one value per wavefront (already reduced over the wavefront), wavefronts in index order; `red` alternates between
+// two buffers from call to call, so one barrier per call is enough
+template <typename T>
+__device__ __forceinline__ T filter_block_sum(T w, T* red, int lane, int wave) {
+  if (lane == 0) red[wave] = w;
+  __syncthreads();
+  T s = red[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) s += red[i];
+  return s;
+}
+
+__global__ __launch_bounds__(1024) void sample_filter_kernel(FilterArgs fa) {
+  constexpr int PER = kFilterPerThread;
+  __shared__ int red_n[2][16];
+  __shared__ double red_s[2][16];
+  __shared__ unsigned red_m[16];
+  __shared__ MaxIdx red_b[16];
+  const SampleArgs& sa = fa.sm;
+  const SamplerArgs& a = sa.s;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int V = a.V;
+  const SamplerMask k = sampler_mask(a, b);
+  if (k.in_prompt || k.fin) return;   // (uniform over the workgroup) the finish kernel does not read choice[b] of such a row
+  const float* lg = a.logits + (long long)b * V;
+  const bool force_ts = sample_mass_fired(sa, b, lane);
+  const bool noisy = sa.noisy[b] != 0;
+  const float inv_t = sa.inv_t[b];
+  const int top_k = noisy ? fa.top_k[b] : 0;
+  const float top_p = noisy ? fa.top_p[b] : 1.f;
+  // thread t, register 4 q + j  <-  id (q * 1024 + t) * 4 + j: four consecutive ids share a Philox block and a bitmap word.  Sixteen
+  // requests in flight at a time (all 64 at once would need their addresses beside the row: more registers than a thread has)
+  unsigned key[PER];
+#pragma unroll
+  for (int g = 0; g < PER / 16; ++g) {
+    const int tg = filter_opaque(tid);
+#pragma unroll
+    for (int q = 4 * g; q < 4 * g + 4; ++q) {
+      const int v0 = (q * 1024 + tg) * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) key[4 * q + j] = __float_as_uint(lg[min(v0 + j, V - 1)]);
+    }
+#pragma unroll
+    for (int q = 4 * g; q < 4 * g + 4; ++q) {
+      const int v0 = (q * 1024 + tg) * 4;
+      const unsigned word = a.suppress_bits[min(v0, V - 1) >> 5];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int v = v0 + j;
+        const bool out = v >= V || score_masked_at(a, k, min(v, V - 1), word) || (force_ts && v < k.ts_begin);
+        key[4 * q + j] = out ? kFilterNegInfKey : filter_key(__uint_as_float(key[4 * q + j]));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  int round = 0;
+  // ---- top-k: tau = the k-th largest key (masked ids count as -inf: with k or fewer ids unmasked tau ends at or below -inf) ----
+  unsigned tau = 0;
+  if (top_k > 0) {
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned t = tau | (1u << bit);
+      int n = 0;
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        n += key[i] >= t ? 1 : 0;
+        if ((i & 15) == 15) __builtin_amdgcn_sched_barrier(0);
+      }
+      n = filter_block_sum<int>((int)wave_sum((float)n), red_n[round & 1], lane, wave);   // (counts up to 65536: exact in float32)
+      ++round;
+      if (n >= top_k) tau = t;
+    }
+  }
+  // ---- the keys of y = x * inv_t over K; 0: not in K ----
+  unsigned kmax = 0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const unsigned kx = key[i], ky = filter_key(__fmul_rn(filter_unkey(kx), inv_t));
+    key[i] = (kx >= tau && kx > kFilterNegInfKey) ? ky : 0u;
+    kmax = max(kmax, key[i]);
+    if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);   // (eight at a time: the row itself fills half the register file)
+  }
+  // ---- top-p: the smallest key c with H(c) = sum of e over {key > c} < top_p * Z ----
+  unsigned cut = 1;   // kept: key >= cut
+  if (top_p < 1.f) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
+    if (lane == 0) red_m[wave] = kmax;
+    __syncthreads();
+    kmax = red_m[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) kmax = max(kmax, red_m[i]);
+    if (kmax != 0) {   // (uniform) something is kept
+      const float m = filter_unkey(kmax);
+      // H(t - 1): a thread's registers in index order in float, the wavefront's butterfly and the block's chain in double
+      // (y and e are computed again in every round: kept, either would take as many registers again as the row does, and the compiler,
+      //  left to itself, hoists them out of the search and spills - the empty statement hides that a key is the same in every round)
+      auto mass_from = [&](unsigned t) -> double {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+          asm volatile("" : "+v"(key[i]));
+          s += key[i] >= t ? __expf(filter_unkey(key[i]) - m) : 0.f;
+          if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+        const double w = score_wave_sum((double)s);
+        const double r = filter_block_sum<double>(w, red_s[round & 1], lane, wave);
+        ++round;
+        return r;
+      };
+      const double thr = (double)top_p * mass_from(1u);
+      unsigned c = 0;
+#pragma unroll 1
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned t = c | (1u << bit);
+        if (!(mass_from(t) < thr)) c = t;   // H(t - 1) >= top_p * Z: the answer lies at t or above
+      }
+      cut = max(c, 1u);
+    }
+  }
+  // ---- the perturbed arg-max over the kept ids ----
+  const unsigned p = (unsigned)a.stt->pos;
+  const unsigned k0 = sa.key[2 * b], k1 = sa.key[2 * b + 1], o0 = sa.off[2 * b], o1 = sa.off[2 * b + 1];
+  MaxIdx best{-INFINITY, 0x7fffffff};
+#pragma unroll
+  for (int q = 0; q < PER / 4; ++q) {
+    const bool any = key[4 * q] >= cut || key[4 * q + 1] >= cut || key[4 * q + 2] >= cut || key[4 * q + 3] >= cut;
+    if (any) {
+      const int v0 = (q * 1024 + filter_opaque(tid)) * 4;
+      Philox4 r{{0u, 0u, 0u, 0u}};
+      if (noisy) r = philox4x32_10((unsigned)v0 >> 2, p, o0, o1, k0, k1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (key[4 * q + j] >= cut) {
+          const float y = filter_unkey(key[4 * q + j]);
+          best = better(best, MaxIdx{noisy ? __fadd_rn(y, gumbel_of(r.w[j])) : y, v0 + j});
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  best = wave_best(best);
+  if (lane == 0) red_b[wave] = best;
+  __syncthreads();
+  if (tid == 0) {
+    best = red_b[0];
+    for (int w = 1; w < 16; ++w) best = better(best, red_b[w]);
+    fa.choice[b] = best.i == 0x7fffffff ? 0 : best.i;   // everything masked
+  }
+}
+
+__global__ __launch_bounds__(1024) void sample_choice_finish_kernel(FilterArgs fa) {
+  const SamplerArgs& a = fa.sm.s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int pos_now = a.stt->pos;              // (thread 0 advances it behind the barrier at the end)
+  for (int b = tid >> 6; b < a.B; b += 16) {  // wavefront w <- streams w, w+16, ...
+    int next_id = 0;
+    const SamplerMask k = sampler_mask(a, b);
+    if (lane == 0) {
+      const int cur_len = a.stt->pos + 1;
+      int* seq = a.seq + (long long)b * a.seq_ld;
+      if (k.in_prompt) {
+        next_id = seq[cur_len];
+        a.cur_ids[b] = next_id;
+      } else if (k.fin) {
+        seq[cur_len] = a.pad;
+        a.cur_ids[b] = a.pad;
+        next_id = a.pad;
+      } else {
+        const int choice = fa.choice[b];
+        seq[cur_len] = choice;
+        a.cur_ids[b] = choice;
+        next_id = choice;
+        if (a.timestamps && choice >= k.ts_begin) a.last_ts[b] = choice;
+        if (choice == a.eos) a.finished[b] = 1;
+      }
+    }
+    if (a.x_next) {   // (kernel-uniform) the token just appended is the next step's input at position pos + 1
+      const int id = __builtin_amdgcn_readfirstlane(next_id);   // lane 0's
+      if (a.dtype == 1) embed_row<bf16_t>(a, b, id, pos_now + 1, lane);
+      else if (a.dtype == 2) embed_row<f16_t>(a, b, id, pos_now + 1, lane);
+      else embed_row<float>(a, b, id, pos_now + 1, lane);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) a.stt->pos += 1;
+}
+
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
 }  // namespace
@@ -2212,6 +2444,23 @@ hipError_t launch_sample(const SampleArgs& a0, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1024), 0, st, a);  // also advances the position
+  return hipGetLastError();
+}
+
+hipError_t launch_sample_filtered(const FilterArgs& a0, hipStream_t st) {
+  const SamplerArgs& s = a0.sm.s;
+  if (s.B < 1 || s.B > 64 || s.V < 1 || s.V > kFilterMaxVocab || s.rows_streams != 0 || !s.suppress_bits || !a0.sm.inv_t || !a0.sm.key ||
+      !a0.sm.off || !a0.sm.noisy || !a0.sm.parts || !a0.top_k || !a0.top_p || !a0.choice)
+    return hipErrorInvalidValue;
+  FilterArgs a = a0;
+  a.sm.s.n_slices = 32;   // the slicing of launch_sampler, as launch_sample: the mass decision is the unfiltered call's
+  hipLaunchKernelGGL((sample_part_kernel<32, 4>), dim3(32, s.B), dim3(256), 0, st, a.sm);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sample_filter_kernel, dim3(s.B), dim3(1024), 0, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sample_choice_finish_kernel, dim3(1), dim3(1024), 0, st, a);  // also advances the position
   return hipGetLastError();
 }
 

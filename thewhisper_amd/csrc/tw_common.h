@@ -377,6 +377,25 @@ struct SampleArgs {
   SamplePartial* parts;       // [B][32] workspace between the two launches
 };
 hipError_t launch_sample(const SampleArgs& a, hipStream_t st);     // sample + pos advance (the bookkeeping of launch_sampler)
+// Top-k / top-p filtered draw (tw_generate_sample_filtered; k_decode.hip: sample_filter_kernel, sample_choice_finish_kernel).  THE RULE,
+// row b: x and the mass decision as above, S = the ids still unmasked.
+//   top_k[b] = k > 0: tau = the k-th largest x over S with multiplicity (-inf when |S| <= k), K = {v in S : x[v] >= tau} - ties at tau
+//     are all kept, the comparison is on the unscaled x; k == 0: K = S.
+//   0 < top_p[b] < 1, on K: y = __fmul_rn(x, inv_t) (the product the draw perturbs), m = max y, e = exp(y - m), Z = sum of e over K,
+//     G(v) = sum of e[u] over u in K with y[u] > y[v] (strict: equal values share their fate); v is kept iff G(v) < top_p * Z, so the
+//     maximum always is; top_p == 1: everything of K is kept.
+//   The token is the lowest id that attains the maximum of score(v) over the kept ids: the noise is the unfiltered call's.
+// Rows with noisy[b] == 0 ignore both filters (the arg-max is always kept).  The row lives in the registers of ONE workgroup of 1024
+// threads, kFilterPerThread values each: V <= kFilterMaxVocab.
+constexpr int kFilterPerThread = 64;
+constexpr int kFilterMaxVocab = 1024 * kFilterPerThread;
+struct FilterArgs {
+  SampleArgs sm;              // launch_sample's arguments: sample_part_kernel runs unchanged, its unscaled partials give the mass decision
+  const int* top_k;           // [B] 0: off
+  const float* top_p;         // [B] 1: off
+  int* choice;                // [B] workspace between the filter and the finish launch
+};
+hipError_t launch_sample_filtered(const FilterArgs& a, hipStream_t st);   // sample + pos advance, three launches
 // Scoring of GIVEN tokens (tw_score_tokens): rows mode only.  `s` carries what sampler_mask() needs - logits, V, B rows, seq / seq_ld,
 // stt (n_prompt = the begin index), the processor fields, begin_suppress, suppress_bits, rows_streams, row_pos0, row_lastts - and
 // nothing of the sampler's outputs.  Row r (stream r % rows_streams, position p = row_pos0 + r / rows_streams) with target

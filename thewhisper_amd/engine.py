@@ -30,6 +30,26 @@ def _stream_ptr(device: torch.device) -> C.c_void_p:
 FP8_DEFAULT = {"a8": "fp8a8", "a16": "fp8a16"}.get(os.environ.get("THEWHISPER_FP8", "").lower(), "fp8a16")
 
 
+def filter_rows(top_k, top_p, B: int):
+    """``generate_sample``'s ``top_k`` / ``top_p`` (None, a scalar or one value per row) as the library's per-row arrays, checked with
+    the library's rules: (int32 [B], float32 [B]), or None when every row is off - the call is then the unfiltered one."""
+    k = np.zeros(B, dtype=np.int64) if top_k is None else np.asarray(top_k)
+    p = np.ones(B, dtype=np.float32) if top_p is None else np.asarray(top_p, dtype=np.float32)
+    if k.dtype.kind not in "iu" or k.size not in (1, B):
+        raise ValueError(f"top_k must be an integer or one integer per row ({B}), got {top_k!r}")
+    if p.size not in (1, B):
+        raise ValueError(f"top_p must be a number or one number per row ({B}), got {top_p!r}")
+    k = np.broadcast_to(k.reshape(-1).astype(np.int64), (B,))
+    p = np.broadcast_to(p.reshape(-1), (B,))
+    if (k < 0).any():
+        raise ValueError(f"top_k must be >= 0 (0 = off), got {top_k!r}")
+    if not ((p > 0) & (p <= 1)).all():
+        raise ValueError(f"top_p must lie in (0, 1] (1 = off), got {top_p!r}")
+    if not (k > 0).any() and not (p < 1).any():
+        return None
+    return np.ascontiguousarray(np.minimum(k, 2 ** 31 - 1), dtype=np.int32), np.ascontiguousarray(p, dtype=np.float32)
+
+
 class WhisperEngine:
     """One MI355X context: weights + workspace + KV arenas for up to ``max_batch`` concurrent streams
     of ``T`` encoder frames (= 50 x chunk seconds)."""
@@ -397,14 +417,17 @@ class WhisperEngine:
                         max_length: int = 448, eos_id: int = 50257, pad_id: int = 50257, timestamps: bool = False,
                         no_timestamps_id: int = 50364, max_initial_timestamp_index: Optional[int] = 50,
                         begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = (), want_alignment: bool = False,
-                        n_forced: int = 0, n_draft: int = 0) -> Dict[str, np.ndarray]:
+                        n_forced: int = 0, n_draft: int = 0, top_k=None, top_p=None) -> Dict[str, np.ndarray]:
         """``generate_greedy`` with a draw from ``softmax(processed logits / temperature[b])`` per row (tw_generate_sample; the draw is
         defined in include/thewhisper.h).  ``temperature``, ``seed``, ``offset``: one value per row, or a scalar for every row.
         ``temperature[b] == 0``: the row is greedy; ``< 0``: the row sits the call out (``pad_id`` from the prompt on).  The noise is a
         function of (seed, offset, position, token id): a row's result does not depend on its slot or on its batch-mates.  ``n_forced`` /
-        ``n_draft`` are refused by the library."""
+        ``n_draft`` are refused by the library.  ``top_k`` / ``top_p`` (None, a scalar or one value per row; 0 / 1.0 = off): the draw is
+        from the top-k ids and, of those, the smallest set of the largest whose mass reaches ``top_p`` (tw_generate_sample_filtered,
+        where the rule is stated; ``top_k=50`` is HF's candidate set).  With both off the call is the unfiltered one."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         B, n0 = prompt.shape
+        filt = filter_rows(top_k, top_p, B)
         rows = [None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dt).reshape(-1), (B,)))
                 for x, dt in ((temperature, np.float32), (seed, np.uint64), (offset, np.uint64))]
         so = _cabi.tw_sample_opts()
@@ -416,9 +439,17 @@ class WhisperEngine:
         out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
         out_len = C.c_int32(0)
         sp = self._loop_stream()     # the decode stream, as the plain greedy call
-        rc = self.lib.tw_generate_sample(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
-                                         out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-        self._chk(rc, "tw_generate_sample")
+        if filt is None:
+            rc = self.lib.tw_generate_sample(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
+                                             out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+            self._chk(rc, "tw_generate_sample")
+        else:
+            fo = _cabi.tw_filter_opts()
+            fo.top_k = filt[0].ctypes.data_as(C.POINTER(C.c_int32))
+            fo.top_p = filt[1].ctypes.data_as(C.POINTER(C.c_float))
+            rc = self.lib.tw_generate_sample_filtered(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
+                                                      C.byref(fo), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+            self._chk(rc, "tw_generate_sample_filtered")
         self._release_held()
         L = int(out_len.value)
         return {"sequences": out[:, :L].astype(np.int64), "length": L}

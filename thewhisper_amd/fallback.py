@@ -5,8 +5,9 @@
 The measurements: the compression ratio of the token bytes (``zlib``, host), and ``avg_logprob`` / ``no_speech_prob`` of
 ``shortform.score_entries`` (scores of the PROCESSED logits at T = 1: what HF averages after rescaling by the temperature, :1958-1967).
 The draws are ``WhisperEngine.generate_sample``'s: a row's result at a given (seed, offset) does not depend on the rows decoded beside it,
-so rows that passed are FROZEN in later attempts (temperature < 0) instead of being cut out of the batch.  Deviations from HF (DESIGN.md
-section 6): no ``top_k = 50``, and the random numbers are not torch's.
+so rows that passed are FROZEN in later attempts (temperature < 0) instead of being cut out of the batch.  ``FallbackPolicy.top_k`` /
+``top_p`` narrow the candidate set of every sampled attempt (tw_generate_sample_filtered); they are off by default, as in openai/whisper's
+draw, and ``top_k=50`` reproduces HF's candidate set.  Deviation from HF: the random numbers are Philox's, not torch's.
 """
 from __future__ import annotations
 
@@ -22,14 +23,21 @@ from .shortform import score_entries
 
 @dataclasses.dataclass(frozen=True)
 class FallbackPolicy:
-    """HF's ``temperature`` tuple and thresholds (the defaults of the reference's long-form recipe), and the base seed of the draws."""
+    """HF's ``temperature`` tuple and thresholds (the defaults of the reference's long-form recipe), the base seed of the draws, and the
+    candidate set of the sampled attempts (``top_k`` / ``top_p``, None = off; ``top_k=50`` is what HF's ``generate`` resolves to)."""
     temperatures: Tuple[float, ...] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
     compression_ratio_threshold: Optional[float] = 1.35
     logprob_threshold: Optional[float] = -1.0
     no_speech_threshold: Optional[float] = None
     seed: int = 0
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
 
     def __post_init__(self):
+        if self.top_k is not None and (isinstance(self.top_k, bool) or int(self.top_k) != self.top_k or self.top_k < 0):
+            raise ValueError(f"top_k must be an integer >= 0 (0 or None = off), got {self.top_k!r}")
+        if self.top_p is not None and not (0 < float(self.top_p) <= 1):
+            raise ValueError(f"top_p must lie in (0, 1] (1 or None = off), got {self.top_p!r}")
         t = tuple(float(x) for x in self.temperatures)
         if not t or any(not math.isfinite(x) or x < 0 for x in t):
             raise ValueError(f"temperatures must be finite and >= 0, got {self.temperatures}")
@@ -87,7 +95,7 @@ def generate_with_fallback(engine, prompt: np.ndarray, greedy: Dict[str, Any], p
     every remaining row is kept as it is.  ``on_attempt(k, temperature, out, rows)``: called after attempt k with the engine's result
     and the rows accepted in it - the moment to take ``token_timestamps``, whose alignment rows belong to the LAST engine call.
     Returns one dict per row: ``sequence`` (the row of the accepting attempt, that attempt's length), ``temperature``, ``attempts``,
-    ``should_skip``, ``score`` (the ``score_entries`` entry)."""
+    ``should_skip``, ``score`` (the ``score_entries`` entry), ``top_k`` / ``top_p`` (the policy's)."""
     prompt = np.ascontiguousarray(prompt, dtype=np.int32)
     B, n_prompt = prompt.shape
     vocab = int(engine.vocab)
@@ -101,6 +109,8 @@ def generate_with_fallback(engine, prompt: np.ndarray, greedy: Dict[str, Any], p
     results: List[Optional[Dict[str, Any]]] = [None] * B
     pending = list(range(B))
     temps = policy.temperatures
+    # (handed on only when set: an engine stand-in without the two keywords keeps working with the default policy)
+    filters = {n: v for n, v in (("top_k", policy.top_k), ("top_p", policy.top_p)) if v is not None}
     for k, T in enumerate(temps):
         if k == 0 and first_call is not None:
             out = first_call()
@@ -109,7 +119,7 @@ def generate_with_fallback(engine, prompt: np.ndarray, greedy: Dict[str, Any], p
         else:
             t = np.full((B,), -1.0, dtype=np.float32)
             t[pending] = T
-            out = engine.generate_sample(prompt, t, seeds, offsets + np.uint64(k), **greedy)
+            out = engine.generate_sample(prompt, t, seeds, offsets + np.uint64(k), **greedy, **filters)
         seq = np.asarray(out["sequences"])
         # (all B rows, frozen ones included: a row's cross K/V live in the slot of its index, so the call cannot be cut down to the live rows)
         entries = score_entries(engine, seq, n_prompt, greedy, no_speech_id)
@@ -121,7 +131,7 @@ def generate_with_fallback(engine, prompt: np.ndarray, greedy: Dict[str, Any], p
                 still.append(b)
                 continue
             results[b] = {"sequence": seq[b].copy(), "temperature": float(T), "attempts": k + 1, "should_skip": bool(skip), "score": e,
-                          "needs_fallback": bool(needs)}
+                          "needs_fallback": bool(needs), "top_k": policy.top_k, "top_p": policy.top_p}
             accepted.append(b)
         if on_attempt is not None:
             on_attempt(k, float(T), out, accepted)

@@ -80,7 +80,8 @@ class AMDWhisperBackend:
         The call then ALWAYS runs the restated short-form loop; a backend whose call is not eligible for it (``job_codec()`` is None)
         raises ``ValueError`` rather than run without the option.  A draft (``draft_previous_tick``) applies to the first attempt only;
         not together with ``reuse_committed_prefix`` (a forced token is not redrawn).  ``last_fallback``: for the most recent call, one
-        ``{temperature, attempts}`` per seek iteration of every chunk."""
+        ``{temperature, attempts}`` per seek iteration of every chunk, with the policy's ``top_k`` / ``top_p`` beside them when it sets one
+        (``FallbackPolicy(top_k=50)``: the sampled attempts draw from HF's candidate set)."""
         from .asr_pipeline import ASRPipeline
 
         if torch_dtype is None:
@@ -425,6 +426,9 @@ class JobCodec:
                 o["stride"] = stride
             outs.append(o)
         job.scores = [e for w in job.works for e in w.scores]
-        job.fallback = [{"temperature": t, "attempts": a} for w in job.works for t, a in zip(w.temperatures, w.attempts)]
+        # (a policy that filters the candidate set: its top_k / top_p beside every entry)
+        pol = self.fallback
+        flt = {"top_k": pol.top_k, "top_p": pol.top_p} if pol is not None and (pol.top_k is not None or pol.top_p is not None) else {}
+        job.fallback = [{"temperature": t, "attempts": a, **flt} for w in job.works for t, a in zip(w.temperatures, w.attempts)]
         result = self.pipe.postprocess(outs, **self.post)
         return AMDWhisperBackend._to_tokens(result, job.audio_duration, job.buffer_start_time)

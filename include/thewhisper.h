@@ -199,6 +199,50 @@ int tw_decode_step(tw_ctx* ctx, int32_t B, const int32_t* ids_host, float* logit
 int tw_generate_greedy(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt,
                        const tw_greedy_opts* opts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
 
+/* tw_generate_greedy with a per-stream sequence bias ("hotword boosting").  Replaces: SequenceBiasLogitsProcessor
+ * (HF:generation/logits_process.py:1211-1319), which HF's generate builds at the head of its processor list
+ * (HF:generation/utils.py:1154-1155) so that Whisper's own processors see the biased scores.  HF takes one list per generate call; here
+ * every row (stream) of the call has its own, applied on the device inside the step.
+ *
+ * THE RULE.  Row b consumes position p and produces the token at p + 1.  h = the row's ids at positions 0 .. p, n = p + 1 of them: prompt,
+ * forced tokens and draft tokens included, as HF's input_ids.  x = the row's float32 logits as the model produced them.  A sequence s =
+ * t[0 .. L-1] with bias beta (finite float32) of row b is ACTIVE iff
+ *     L == 1,   or   L <= n  and  h[n - (L-1) + j] == t[j] for j = 0 .. L-2.
+ * (L <= n is HF's `len(sequence_ids) > input_ids.shape[1]: continue`: a sequence whose L-1 prefix is exactly the whole history has
+ * L == n + 1 and is NOT applied.)  For every id v that is the last token of at least one active sequence of the row,
+ *     total(v) = the float32 sum, starting from 0.0f, of the biases of the active sequences ending in v: the row's length-1 sequence for
+ *                v first (if it has one), then the longer ones in the order the caller listed them (HF: zeros + length_1_bias, then
+ *                `+=` in dict order),
+ *     x'[v] = x[v] + total(v)     one float32 add, HF's `scores + bias`;
+ * every other logit keeps its bits.  Everything else in the step reads x' and is otherwise unchanged, bit for bit: the suppress lists,
+ * begin-suppress, the min_new_tokens <eos> mask, the timestamp grammar, "the timestamp mass beats every text token", the lowest-id
+ * arg-max.  A masked id stays masked (-inf plus a finite value is -inf).  A row without sequences produces the unbiased call's tokens
+ * bit for bit, whatever the other rows carry; a row's result does not depend on its slot or on its batch-mates.
+ *
+ * bopts == NULL or n_seq == 0: the call IS tw_generate_greedy, launch for launch.  Otherwise a step issues one launch more (one
+ * workgroup per row; no atomics, no cross-thread sum: the order above is the order of the additions), captured step graphs are kept
+ * apart from the unbiased call's, n_forced and n_draft are honoured (the rows-mode launches of a draft's verification are biased the
+ * same way, so the result is the biased plain call's: same ids, same alignment rows), and tw_last_draft, tw_last_timings,
+ * want_alignment and tw_token_timestamps behave as after tw_generate_greedy.  The tables live in context-owned device memory, allocated
+ * by the first biased call of a context (a sibling owns its own) and freed by tw_destroy.
+ *
+ * TW_EINVAL in addition to tw_generate_greedy's, all before any work is enqueued (the context stays usable): row_off / seq_off that do
+ * not start at 0 or decrease, row_off[B] != n_seq, seq_off that does not strictly increase (an empty sequence), a sequence longer than
+ * TW_BIAS_MAX_SEQ_LEN, a token outside [0, vocab), a NaN or infinite bias, the same token sequence twice in one row, more than
+ * TW_BIAS_MAX_SEQS sequences or TW_BIAS_MAX_TOKENS tokens in the call, B > 64.  tw_generate_sample* take no bias. */
+#define TW_BIAS_MAX_SEQS 16384      /* sequences per call, all rows together */
+#define TW_BIAS_MAX_TOKENS 65536    /* tokens per call */
+#define TW_BIAS_MAX_SEQ_LEN 32      /* tokens per sequence */
+typedef struct tw_bias_opts {
+  int32_t        n_seq;     /* sequences of all rows together */
+  const int32_t* row_off;   /* host [B + 1]: row b owns sequences row_off[b] .. row_off[b+1]-1; a row may own none */
+  const int32_t* seq_off;   /* host [n_seq + 1]: tokens of sequence i = tokens[seq_off[i] .. seq_off[i+1]) */
+  const int32_t* tokens;    /* host */
+  const float*   bias;      /* host [n_seq] */
+} tw_bias_opts;
+int tw_generate_greedy_biased(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
+                              const tw_bias_opts* bopts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
+
 /* Temperature sampling on the device.  Replaces: GenerationMixin._sample with do_sample=True and a TemperatureLogitsWarper behind
  * Whisper's logits processors (HF:generation/utils.py:1293-1312, :2925-2931), as WhisperGenerationMixin.generate_with_fallback invokes it
  * for the temperatures behind 0 (HF:models/whisper/generation_whisper.py:970-1116; thewhisper_amd/fallback.py restates that ladder).

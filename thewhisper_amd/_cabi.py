@@ -47,6 +47,11 @@ class tw_filter_opts(C.Structure):
     _fields_ = [("top_k", C.POINTER(C.c_int32)), ("top_p", C.POINTER(C.c_float))]
 
 
+class tw_bias_opts(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("row_off", C.POINTER(C.c_int32)), ("seq_off", C.POINTER(C.c_int32)),
+                ("tokens", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float))]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -67,6 +72,8 @@ SYMBOLS = [
     ("tw_decode_step", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     ("tw_generate_greedy", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_generate_greedy_biased", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
+                                            C.POINTER(tw_bias_opts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),

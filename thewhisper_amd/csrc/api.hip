@@ -106,6 +106,9 @@ struct tw_ctx {
   int* row_choice = nullptr;     // [row_ids_cap]
   int* verify_state = nullptr;   // [2 + 64] device
   int* h_verify = nullptr;       // pinned: [2 + 64] read back | [1] reset value
+  // tw_generate_greedy_biased: the packed table of the call's sequences (tw_common.h: SeqBiasArgs) and its pinned staging, both of
+  // kSeqBiasTabWords words, allocated by the first biased call of the context
+  int* bias_tab = nullptr; int* h_bias = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
   size_t row_ids_cap = 0;
   // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
@@ -260,6 +263,7 @@ int tw_destroy(tw_ctx* c) {
   if (c->h_rows) (void)hipHostFree(c->h_rows);
   if (c->h_verify) (void)hipHostFree(c->h_verify);
   if (c->h_score) (void)hipHostFree(c->h_score);
+  if (c->h_bias) (void)hipHostFree(c->h_bias);
   for (int i = 0; i < 5; ++i) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
@@ -1053,8 +1057,9 @@ int prefill_core(tw_ctx* c, int B, const int* tok, int ld, int n_pos, hipStream_
 // position) is the loop's state after that token.  The host synchronises once per launch (it needs the decision to go on).
 // On return *p_next = p_acc + 1 and tok[.. + *p_next] holds those tokens.
 // *next_given = 1 when the tokens the round PRODUCED at *p_next are (for every stream) the guesses that stood there (p_next <= p_given).
+// ba != nullptr (tw_generate_greedy_biased): every launch's logits pass through launch_seq_bias before its sampler, rows mode.
 int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, int p_start, int p_end, int rows_cap, const SamplerArgs& sa0,
-                 hipStream_t st, int* p_next, int* n_launches, int p_given, int* next_given) {
+                 hipStream_t st, int* p_next, int* n_launches, int p_given, int* next_given, const SeqBiasArgs* ba) {
   const int n_pos = p_end - p_start + 1;
   if (n_pos < 1 || B > rows_cap) return fail(c, TW_EINVAL, "verify: bad round [%d, %d] for %d streams", p_start, p_end, B);
   if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "verify: %d positions x %d streams exceed the row table", n_pos, B);
@@ -1085,6 +1090,11 @@ int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, 
     SamplerArgs sa = sa0;
     sa.B = l * B; sa.rows_streams = B; sa.row_pos0 = p0; sa.row_lastts = c->row_lastts + off; sa.row_choice = c->row_choice + off;
     sa.row_last_pos = p_end; sa.row_is_last = (p0 + l > p_end) ? 1 : 0; sa.verify_state = c->verify_state;
+    if (ba) {
+      SeqBiasArgs b = *ba;
+      b.rows = l * B; b.rows_streams = B; b.row_pos0 = p0;
+      HIPCHK(c, launch_seq_bias(b, st));
+    }
     HIPCHK(c, launch_sampler_rows(sa, st));
     HIPCHK(c, hipMemcpyAsync(hv, c->verify_state, sizeof(int) * (2 + B), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -1103,6 +1113,74 @@ int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, 
     }
   }
   return fail(c, TW_EHIP, "verify: the round ended without a decision");
+}
+
+// words of the packed sequence-bias table at its capacities: header | grp_off | grp_tok | seq_off | bias | tokens
+constexpr size_t kSeqBiasTabWords = kSeqBiasHeader + 2 * (size_t)TW_BIAS_MAX_SEQS + 2 * ((size_t)TW_BIAS_MAX_SEQS + 1) + TW_BIAS_MAX_TOKENS;
+
+// Checks a tw_bias_opts (every TW_EINVAL of tw_generate_greedy_biased) and packs it into the table seq_bias_kernel reads (tw_common.h:
+// SeqBiasArgs): per stream the sequences grouped by last token, a group's length-1 member first, then the caller's order; groups in
+// the order their last token first appears.  Host work only.
+int pack_seq_bias(tw_ctx* c, int B, const tw_bias_opts* bo, std::vector<int>& tab) {
+  const char* fn = "tw_generate_greedy_biased";
+  const int S = bo->n_seq;
+  if (S < 0 || S > TW_BIAS_MAX_SEQS) return fail(c, TW_EINVAL, "%s: %d sequences (at most %d)", fn, S, TW_BIAS_MAX_SEQS);
+  if (!bo->row_off || !bo->seq_off || !bo->tokens || !bo->bias) return fail(c, TW_EINVAL, "%s: null array in tw_bias_opts", fn);
+  if (bo->row_off[0] != 0 || bo->row_off[B] != S) return fail(c, TW_EINVAL, "%s: row_off must run from 0 to n_seq", fn);
+  for (int b = 0; b < B; ++b)
+    if (bo->row_off[b + 1] < bo->row_off[b]) return fail(c, TW_EINVAL, "%s: row_off decreases at row %d", fn, b);
+  if (bo->seq_off[0] != 0) return fail(c, TW_EINVAL, "%s: seq_off must start at 0", fn);
+  for (int i = 0; i < S; ++i) {
+    const long long L = (long long)bo->seq_off[i + 1] - bo->seq_off[i];
+    if (L < 1 || L > TW_BIAS_MAX_SEQ_LEN) return fail(c, TW_EINVAL, "%s: sequence %d has %lld tokens (1 .. %d)", fn, i, L, TW_BIAS_MAX_SEQ_LEN);
+    if (bo->seq_off[i + 1] > TW_BIAS_MAX_TOKENS) return fail(c, TW_EINVAL, "%s: more than %d tokens", fn, TW_BIAS_MAX_TOKENS);
+    if (!std::isfinite(bo->bias[i])) return fail(c, TW_EINVAL, "%s: the bias of sequence %d is NaN or infinite", fn, i);
+  }
+  const int n_tok = bo->seq_off[S];
+  for (int i = 0; i < n_tok; ++i)
+    if (bo->tokens[i] < 0 || bo->tokens[i] >= c->V) return fail(c, TW_EINVAL, "%s: token %d outside the vocabulary", fn, bo->tokens[i]);
+  std::vector<int> strm(65, 0), grp_off(1, 0), grp_tok, seq_off(1, 0), tokens;
+  std::vector<float> bias;
+  for (int b = 0; b < B; ++b) {
+    std::set<std::vector<int>> seen;
+    std::map<int, size_t> group_of;                 // last token -> index into members
+    std::vector<std::vector<int>> members;          // per group: sequence indices in summation order
+    std::vector<int> last_of;
+    for (int i = bo->row_off[b]; i < bo->row_off[b + 1]; ++i) {
+      const int* t = bo->tokens + bo->seq_off[i];
+      const int L = bo->seq_off[i + 1] - bo->seq_off[i];
+      if (!seen.insert(std::vector<int>(t, t + L)).second) return fail(c, TW_EINVAL, "%s: row %d lists sequence %d twice", fn, b, i);
+      auto it = group_of.find(t[L - 1]);
+      if (it == group_of.end()) {
+        it = group_of.emplace(t[L - 1], members.size()).first;
+        members.emplace_back();
+        last_of.push_back(t[L - 1]);
+      }
+      std::vector<int>& m = members[it->second];
+      if (L == 1) m.insert(m.begin(), i); else m.push_back(i);
+    }
+    strm[b] = (int)grp_tok.size();
+    for (size_t g = 0; g < members.size(); ++g) {
+      grp_tok.push_back(last_of[g]);
+      for (int i : members[g]) {
+        tokens.insert(tokens.end(), bo->tokens + bo->seq_off[i], bo->tokens + bo->seq_off[i + 1]);
+        seq_off.push_back((int)tokens.size());
+        bias.push_back(bo->bias[i]);
+      }
+      grp_off.push_back((int)bias.size());
+    }
+  }
+  for (int b = B; b < 65; ++b) strm[b] = (int)grp_tok.size();
+  tab.assign(kSeqBiasHeader, 0);
+  for (int b = 0; b < 65; ++b) tab[kSeqBiasStreamOff + b] = strm[b];
+  auto append = [&](int slot, const int* p, size_t n) { tab[slot] = (int)tab.size(); tab.insert(tab.end(), p, p + n); };
+  append(0, grp_off.data(), grp_off.size());
+  append(1, grp_tok.data(), grp_tok.size());
+  append(2, seq_off.data(), seq_off.size());
+  append(3, reinterpret_cast<const int*>(bias.data()), bias.size());
+  append(4, tokens.data(), tokens.size());
+  if (tab.size() > kSeqBiasTabWords) return fail(c, TW_EINVAL, "%s: the packed table exceeds its capacity", fn);   // (cannot happen)
+  return TW_OK;
 }
 
 int reset_state(tw_ctx* c, int n_prompt, hipStream_t st) {
@@ -1145,10 +1223,11 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
 // The generation loop of tw_generate_greedy and tw_generate_sample.  so == nullptr: the greedy call, launch for launch what it has always
 // issued.  so != nullptr (validated by tw_generate_sample: no forced / draft tokens, finite temperatures, a live row): every step's
 // sampler is launch_sample; rows with temperature < 0 start finished.  fo != nullptr (validated by tw_generate_sample_filtered, which
-// hands it on only when some sampled row has a filter on): every step's sampler is launch_sample_filtered.
+// hands it on only when some sampled row has a filter on): every step's sampler is launch_sample_filtered.  bo != nullptr
+// (tw_generate_greedy_biased, greedy only, n_seq > 0): launch_seq_bias runs in front of every sampler launch, rows mode included.
 static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
-                         const tw_filter_opts* fo, int32_t* out_ids, int32_t* out_len, void* stream) {
-  const char* fn = fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
+                         const tw_filter_opts* fo, const tw_bias_opts* bo, int32_t* out_ids, int32_t* out_len, void* stream) {
+  const char* fn = bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
   if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
   if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
@@ -1168,6 +1247,13 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   if (max_len > c->P) max_len = c->P;
   if (max_len <= n_prompt) return fail(c, TW_EINVAL, "nothing to generate (max_len %d <= n_prompt %d)", max_len, n_prompt);
   const int out_ld = o->max_length > 0 ? o->max_length : max_len;
+  const bool biased = bo != nullptr;
+  std::vector<int> bias_tab;   // the call's packed sequence table (checked here, with the other refusals; uploaded with the initial state)
+  if (biased) {
+    if (B > 64) return fail(c, TW_EINVAL, "%s: %d streams (1..64)", fn, B);
+    int r = pack_seq_bias(c, B, bo, bias_tab);
+    if (r != TW_OK) return r;
+  }
   c->dec_key_bound = max_len;   // per step: the 64-key bucket of the position (below)
   hipStream_t st = pick_stream(c, stream);
   const int P = c->P;
@@ -1216,6 +1302,12 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       if (n_forced > 0 && o->timestamps && t > o->no_timestamps_id) neg[b] = t;
     }
   }
+  if (biased) {   // device table and pinned staging: allocated by the first biased call of the context, freed in tw_destroy
+    if (!c->bias_tab) ALLOC(c, c->bias_tab, sizeof(int) * kSeqBiasTabWords, false);
+    if (!c->h_bias) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_bias), sizeof(int) * kSeqBiasTabWords));
+    memcpy(c->h_bias, bias_tab.data(), sizeof(int) * bias_tab.size());
+    HIPCHK(c, hipMemcpyAsync(c->bias_tab, c->h_bias, sizeof(int) * bias_tab.size(), hipMemcpyHostToDevice, st));
+  }
   HIPCHK(c, hipMemcpyAsync(c->seq, hseq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->cur_ids, first, sizeof(int) * B, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->finished, zeros, sizeof(int) * B, hipMemcpyHostToDevice, st));
@@ -1254,6 +1346,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   sa.no_ts_id = o->no_timestamps_id; sa.max_initial_ts = o->max_initial_timestamp_index;
   sa.begin_suppress = c->begin_suppress_dev; sa.n_begin_suppress = o->n_begin_suppress;
   sa.suppress_bits = c->suppress_bits; sa.partials = c->sampler_partials;
+  SeqBiasArgs ba{};   // the table lives in context-owned device memory: one captured graph serves every list
+  ba.logits = c->logits; ba.V = c->V; ba.rows = B; ba.seq = c->seq; ba.seq_ld = P; ba.finished = c->finished; ba.stt = c->stt; ba.tab = c->bias_tab;
   // the embedding of the token a step has chosen is written by the sampler's last launch (k_decode.hip: embed_row), so a step is
   // layers + logits + sampler; only the FIRST step of the call needs its input row from a launch of its own
   c->last_draft[0] = n_draft * B; c->last_draft[1] = c->last_draft[2] = c->last_draft[3] = 0;
@@ -1276,7 +1370,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       const int rows = rounds == 0 ? std::min(cap, std::max(first_rows, B)) : std::min(cap, std::max(retry_rows, 4 * B));
       const int pe = rounds == 0 ? p_end : std::min(p_end, pos + std::max(1, rows / B) - 1);
       int pn = 0, next_given = 0;
-      int r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, &c->last_draft[2], p_end, &next_given);
+      int r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, &c->last_draft[2], p_end, &next_given, biased ? &ba : nullptr);
       if (r != TW_OK) return r;
       ++rounds;
       // guesses this round confirmed: the given tokens at positions <= p_acc that were compared, and the token the round produced
@@ -1296,14 +1390,18 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  // (last field: the sampler flavour - greedy, sampling, filtered sampling: a graph of one is never replayed for a call of another)
+  // (last field: the sampler flavour - greedy, biased greedy, sampling, filtered sampling: a graph of one is never replayed for a call of another)
   snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, fo ? 'f' : so ? 's' : 'g');
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
   SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
   sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
   FilterArgs fla{};   // ... and every top-k / top-p
   fla.top_k = c->filter_top_k; fla.top_p = c->filter_top_p; fla.choice = c->filter_choice;
   auto sample_step = [&]() -> hipError_t {
+    if (biased) {
+      hipError_t e = launch_seq_bias(ba, st);
+      if (e != hipSuccess) return e;
+    }
     if (!so) return launch_sampler(sa, st);
     sma.s = sa;
     if (!fo) return launch_sample(sma, st);
@@ -1444,7 +1542,15 @@ int tw_generate_greedy(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_pr
                        int32_t* out_ids, int32_t* out_len, void* stream) {
   if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy: null argument");
   TW_ON_DEVICE(c);
-  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, out_ids, out_len, stream);
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_greedy_biased(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_bias_opts* bo,
+                              int32_t* out_ids, int32_t* out_len, void* stream) {
+  if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy_biased: null argument");
+  TW_ON_DEVICE(c);
+  // nothing to add: the call IS tw_generate_greedy, launch for launch
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, (bo && bo->n_seq != 0) ? bo : nullptr, out_ids, out_len, stream);
 }
 
 // tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter
@@ -1476,7 +1582,7 @@ static int generate_sample_checked(const char* fn, tw_ctx* c, int32_t B, const i
   }
   if (filtered && c->V > kFilterMaxVocab)
     return fail(c, TW_EINVAL, "%s: the filter kernel holds %d ids, the vocabulary has %d", fn, kFilterMaxVocab, c->V);
-  return generate_loop(c, B, prompt, n_prompt, o, so, filtered ? fo : nullptr, out_ids, out_len, stream);
+  return generate_loop(c, B, prompt, n_prompt, o, so, filtered ? fo : nullptr, nullptr, out_ids, out_len, stream);
 }
 
 int tw_generate_sample(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,

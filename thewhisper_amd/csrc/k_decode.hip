@@ -2168,6 +2168,51 @@ __global__ __launch_bounds__(1024) void sample_choice_finish_kernel(FilterArgs f
   if (tid == 0) a.stt->pos += 1;
 }
 
+// Per-stream sequence bias (tw_generate_greedy_biased; the rule is stated in include/thewhisper.h): one launch in front of the step's
+// sampler that edits the float32 logits in place.  One workgroup per row of the launch (a stream at the device position, or - rows
+// mode - stream r % rs at position row_pos0 + r / rs, as sampler_mask derives it).  The stream's sequences arrive grouped by last
+// token (SeqBiasArgs: the packed table); a thread owns whole groups, walks a group's members in table order - the length-1 member,
+// then the caller's order - and adds the active ones into ONE float32 register starting from 0.0f, then does one load, one add and one
+// store of the logit.  No atomics and no cross-thread reduction: the order of the sum, hence its bits, is the table's.
+__global__ __launch_bounds__(256) void seq_bias_kernel(SeqBiasArgs a) {
+  const int r = blockIdx.x;
+  int stream, p;
+  tw_row_of(r, a.rows_streams, a.rows_streams > 0 ? a.row_pos0 : a.stt->pos, stream, p);
+  const int* tab = a.tab;
+  const int g0 = tab[kSeqBiasStreamOff + stream], g1 = tab[kSeqBiasStreamOff + stream + 1];
+  if (g0 == g1) return;                                   // a row without sequences
+  const int n = p + 1;                                    // ids of the history: positions 0 .. p
+  if (n < a.stt->n_prompt) return;                        // still consuming its prompt: nothing is sampled
+  if (a.rows_streams == 0 && a.finished[r] != 0) return;  // finished: the row receives pad_id whatever the logits say
+  const int* grp_off = tab + tab[0];
+  const int* grp_tok = tab + tab[1];
+  const int* seq_off = tab + tab[2];
+  const float* bias = reinterpret_cast<const float*>(tab + tab[3]);
+  const int* tokens = tab + tab[4];
+  const int* h = a.seq + (long long)stream * a.seq_ld;
+  float* lg = a.logits + (long long)r * a.V;
+  for (int g = g0 + (int)threadIdx.x; g < g1; g += 256) {
+    float total = 0.0f;
+    bool any = false;
+    const int s1 = grp_off[g + 1];
+    for (int s = grp_off[g]; s < s1; ++s) {
+      const int t0 = seq_off[s], L = seq_off[s + 1] - t0;
+      bool active = L == 1;
+      if (!active && L <= n) {
+        active = true;
+        const int* tail = h + (n - (L - 1));
+        for (int j = 0; j < L - 1; ++j)
+          if (tail[j] != tokens[t0 + j]) { active = false; break; }
+      }
+      if (active) { total += bias[s]; any = true; }
+    }
+    if (any) {
+      const int v = grp_tok[g];
+      lg[v] = lg[v] + total;
+    }
+  }
+}
+
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
 }  // namespace
@@ -2482,6 +2527,14 @@ hipError_t launch_suppress_bitmap(const int* list, int n, unsigned* bits, int V,
   hipError_t e = hipMemsetAsync(bits, 0, (size_t)((V + 31) / 32) * 4, st);
   if (e != hipSuccess || n <= 0) return e;
   hipLaunchKernelGGL(suppress_bitmap_kernel, dim3((n + 255) / 256), dim3(256), 0, st, list, n, bits, V);
+  return hipGetLastError();
+}
+
+hipError_t launch_seq_bias(const SeqBiasArgs& a, hipStream_t st) {
+  if (a.rows < 1 || a.rows > 64 || !a.logits || !a.seq || !a.stt || !a.tab || a.rows_streams < 0 ||
+      (a.rows_streams == 0 ? !a.finished : a.rows % a.rows_streams != 0))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seq_bias_kernel, dim3(a.rows), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

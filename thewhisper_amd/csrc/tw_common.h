@@ -411,6 +411,27 @@ struct ScoreArgs {
   int ns_id, ns_pos; float* out_ns;
 };
 hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t st);
+// Per-stream sequence bias (tw_generate_greedy_biased; the rule is in include/thewhisper.h; k_decode.hip: seq_bias_kernel): one launch in
+// front of launch_sampler / launch_sampler_rows that adds to logits[row][v], in place, the float32 total of the row's ACTIVE sequences
+// ending in v.  `tab` is the packed table of the call in context-owned device memory (int32 words, api.hip packs it), CSR, stream ->
+// groups (one per last token) -> sequences -> tokens:
+//   tab[0 .. 4]                         word offsets of grp_off, grp_tok, seq_off, bias, tokens
+//   tab[kSeqBiasStreamOff + s], [+ s+1] groups of stream s (64 streams + 1)
+//   grp_off[g], grp_off[g + 1]          sequences of group g, in the order their biases are summed: the length-1 member first, then
+//                                       the caller's order;  grp_tok[g] = the group's last token
+//   seq_off[i], seq_off[i + 1]          tokens of sequence i;  bias[i] its float32 bias
+// The pointer is the same for every call of a context, so one captured step graph serves every list.
+constexpr int kSeqBiasStreamOff = 8;
+constexpr int kSeqBiasHeader = 80;      // words in front of the CSR arrays (offsets | stream table | padding)
+struct SeqBiasArgs {
+  float* logits; int V; int rows;       // [rows][V]
+  const int* seq; int seq_ld;           // [streams][seq_ld] token history (SamplerArgs::seq)
+  const int* finished;                  // [streams] (ordinary step only)
+  const DecState* stt;
+  int rows_streams; int row_pos0;       // rows mode as SamplerArgs: row r = stream r % rows_streams at position row_pos0 + r / rows_streams
+  const int* tab;
+};
+hipError_t launch_seq_bias(const SeqBiasArgs& a, hipStream_t st);
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st);     // pos += n only (teacher-forced stepping, prefill)
 
 // A11: alignment rows -> token timestamps

@@ -50,6 +50,55 @@ def filter_rows(top_k, top_p, B: int):
     return np.ascontiguousarray(np.minimum(k, 2 ** 31 - 1), dtype=np.int32), np.ascontiguousarray(p, dtype=np.float32)
 
 
+_F32_MAX = float(np.finfo(np.float32).max)
+
+
+def sequence_bias_dict(sequence_bias) -> Dict[Tuple[int, ...], float]:
+    """HF's ``sequence_bias`` - a list of ``[[token ids], bias]`` or a dict ``{tuple of token ids: bias}`` - as the dict
+    ``SequenceBiasLogitsProcessor._convert_list_arguments_into_dict`` makes of it: a later duplicate of a list overwrites the bias and
+    keeps the first one's place.  None or empty: the empty dict."""
+    if not sequence_bias:
+        return {}
+    items = sequence_bias.items() if isinstance(sequence_bias, dict) else [(x[0], x[1]) for x in sequence_bias]
+    out: Dict[Tuple[int, ...], float] = {}
+    for ids, bias in items:
+        key = tuple(int(t) for t in ids)
+        if not key or any(t < 0 for t in key):
+            raise ValueError(f"sequence_bias: every sequence is a non-empty list of token ids >= 0, got {ids!r}")
+        bias = float(bias)
+        if not abs(bias) <= _F32_MAX:      # (NaN fails the comparison too)
+            raise ValueError(f"sequence_bias: the bias of {ids!r} must be a finite float32, got {bias!r}")
+        out[key] = bias
+    return out
+
+
+def pack_sequence_bias(rows, B: int) -> Optional[Dict[str, np.ndarray]]:
+    """The per-row lists of a call (``rows[b]``: HF's list or dict form, or None / empty for a row without one) as the arrays of
+    ``tw_bias_opts``: ``row_off`` int32 [B + 1], ``seq_off`` int32 [n_seq + 1], ``tokens`` int32, ``bias`` float32 [n_seq]; row b owns
+    sequences ``row_off[b] .. row_off[b + 1] - 1`` in the order of its dict (the order the library sums the biases of one last token
+    in, a length-1 sequence first).  None when no row lists anything: the call is then the unbiased one."""
+    if len(rows) != B:
+        raise ValueError(f"sequence_bias_rows: {len(rows)} lists for {B} rows")
+    row_off, seq_off, tokens, bias = [0], [0], [], []
+    for r in rows:
+        for key, val in sequence_bias_dict(r).items():
+            tokens.extend(key)
+            seq_off.append(len(tokens))
+            bias.append(val)
+        row_off.append(len(bias))
+    if not bias:
+        return None
+    return {"row_off": np.asarray(row_off, dtype=np.int32), "seq_off": np.asarray(seq_off, dtype=np.int32),
+            "tokens": np.asarray(tokens, dtype=np.int32), "bias": np.asarray(bias, dtype=np.float32)}
+
+
+def merge_sequence_bias(first, second) -> Dict[Tuple[int, ...], float]:
+    """Two lists for one row as one dict: ``first``'s entries keep their places, a sequence listed in both takes ``second``'s bias."""
+    out = sequence_bias_dict(first)
+    out.update(sequence_bias_dict(second))
+    return out
+
+
 class WhisperEngine:
     """One MI355X context: weights + workspace + KV arenas for up to ``max_batch`` concurrent streams
     of ``T`` encoder frames (= 50 x chunk seconds)."""
@@ -385,13 +434,23 @@ class WhisperEngine:
         want_alignment: bool = False,
         n_forced: int = 0,
         n_draft: int = 0,
+        sequence_bias=None,
+        sequence_bias_rows=None,
     ) -> Dict[str, np.ndarray]:
-        """``n_forced``: the last ``n_forced`` tokens of every prompt row are forced OUTPUT tokens (they count as generated; a
+        """``sequence_bias``: HF's ``sequence_bias`` (list or dict form) for every row; ``sequence_bias_rows``: one such list per row
+        (None for a row without one) - not both.  The rule is tw_generate_greedy_biased's (include/thewhisper.h): HF's
+        ``SequenceBiasLogitsProcessor`` ahead of Whisper's processors, per row, honoured under ``n_forced`` and ``n_draft``.
+        ``n_forced``: the last ``n_forced`` tokens of every prompt row are forced OUTPUT tokens (they count as generated; a
         batched prefill processes them - tw_greedy_opts::n_forced); the returned sequences contain them like generated ones.
         ``n_draft``: the last ``n_draft`` tokens of every prompt row are GUESSES of the output (tw_greedy_opts::n_draft): verified in
         batched launches, the call returns what it returns without them; ``draft`` in the result says how many were confirmed."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         B, n0 = prompt.shape
+        if sequence_bias is not None and sequence_bias_rows is not None:
+            raise ValueError("sequence_bias (every row) and sequence_bias_rows (per row): give one of the two")
+        if sequence_bias is not None:
+            sequence_bias_rows = [sequence_bias] * B
+        packed = pack_sequence_bias(list(sequence_bias_rows), B) if sequence_bias_rows is not None else None
         o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
                                      min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
         out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
@@ -399,10 +458,19 @@ class WhisperEngine:
         # (calls with a forced prefix stay on the caller's stream: their batched prefill - launches of up to 64 rows - wants the whole
         #  chip; measured on the reuse path's short calls: 16.1 ms per tick there, 19.9 on the 160-CU stream)
         sp = self._loop_stream() if int(n_forced) == 0 and int(n_draft) == 0 else self._sp()
-        rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
-                                         out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
-                                         sp)
-        self._chk(rc, "tw_generate_greedy")
+        if packed is None:
+            rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
+                                             out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
+                                             sp)
+            self._chk(rc, "tw_generate_greedy")
+        else:
+            bo = _cabi.tw_bias_opts()
+            bo.n_seq = int(packed["bias"].size)
+            bo.row_off, bo.seq_off, bo.tokens = (packed[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("row_off", "seq_off", "tokens"))
+            bo.bias = packed["bias"].ctypes.data_as(C.POINTER(C.c_float))
+            rc = self.lib.tw_generate_greedy_biased(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(bo),
+                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+            self._chk(rc, "tw_generate_greedy_biased")
         self._release_held()   # the call returns after synchronising its stream, which is ordered after the encoder stage
         L = int(out_len.value)
         res = {"sequences": out[:, :L].astype(np.int64), "length": L}

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 from transformers import WhisperConfig, WhisperForConditionalGeneration
 from transformers.generation.logits_process import (
+    SequenceBiasLogitsProcessor,
     SuppressTokensAtBeginLogitsProcessor,
     SuppressTokensLogitsProcessor,
     WhisperTimeStampLogitsProcessor,
@@ -79,6 +80,7 @@ class _EngineGreedyMixin(GenerationMixin):
                              "construct ASRPipeline with a matching batch_size")
         n_prompt = int(decoder_input_ids.shape[1])
         opts = self._parse_logits_processors(logits_processor, n_prompt)
+        bias = self._sequence_bias(gc, logits_processor)
         max_target = int(self.config.max_target_positions)
         if getattr(gc, "max_new_tokens", None) is not None:
             max_len = n_prompt + int(gc.max_new_tokens)
@@ -101,6 +103,8 @@ class _EngineGreedyMixin(GenerationMixin):
         prompt = decoder_input_ids.detach().to("cpu", torch.int32).numpy()
         greedy_kw = dict(max_new_tokens=max_len - n_prompt, min_new_tokens=min_new, max_length=max_target, eos_id=int(eos),
                          pad_id=int(pad), want_alignment=want_align, **opts)
+        if bias:
+            greedy_kw["sequence_bias"] = bias
         probe = getattr(self, "_plan_probe", None)
         if probe is not None:   # a call that is learning its short-form plan (shortform.py): what was the engine asked to do?
             probe.append({"prompt": prompt.copy(), "greedy": dict(greedy_kw),
@@ -142,6 +146,30 @@ class _EngineGreedyMixin(GenerationMixin):
             raise NotImplementedError("not supported by the MI355X greedy engine: " + ", ".join(bad))
 
     @staticmethod
+    def _sequence_bias(gc, processors) -> Optional[Dict[Tuple[int, ...], float]]:
+        """HF's ``sequence_bias`` of the call as the dict ``SequenceBiasLogitsProcessor`` holds: from ``generation_config.sequence_bias``
+        (HF builds that processor at the head of its list, HF:generation/utils.py:1154-1155, so Whisper's processors see the biased
+        scores - the order the engine applies) or from one such processor in a custom list, which must not stand behind the
+        ``WhisperTimeStampLogitsProcessor`` (the timestamp rule would then read unbiased scores)."""
+        from .engine import sequence_bias_dict
+
+        found, seen_ts = [], False
+        for p in processors or []:
+            if isinstance(p, WhisperTimeStampLogitsProcessor):
+                seen_ts = True
+            elif isinstance(p, SequenceBiasLogitsProcessor):
+                if seen_ts:
+                    raise NotImplementedError("a SequenceBiasLogitsProcessor behind the WhisperTimeStampLogitsProcessor: the MI355X engine "
+                                              "applies the bias ahead of Whisper's processors, as generation_config.sequence_bias does")
+                found.append(p.sequence_bias)
+        gc_bias = getattr(gc, "sequence_bias", None)
+        if gc_bias:
+            found.append(gc_bias)
+        if len(found) > 1:
+            raise NotImplementedError("more than one sequence bias (generation_config.sequence_bias and / or several processors)")
+        return sequence_bias_dict(found[0]) if found else None
+
+    @staticmethod
     def _parse_logits_processors(processors, n_prompt: int) -> Dict[str, Any]:
         opts: Dict[str, Any] = dict(timestamps=False, begin_suppress=(), suppress=(), no_timestamps_id=0,
                                     max_initial_timestamp_index=None)
@@ -158,6 +186,8 @@ class _EngineGreedyMixin(GenerationMixin):
                 opts["timestamps"] = True
                 opts["no_timestamps_id"] = int(p.no_timestamps_token_id)
                 opts["max_initial_timestamp_index"] = p.max_initial_timestamp_index
+            elif isinstance(p, SequenceBiasLogitsProcessor):
+                pass      # read by _sequence_bias
             else:
                 raise NotImplementedError(f"logits processor {type(p).__name__} is not implemented on the MI355X engine")
         return opts
@@ -242,13 +272,13 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
-                "max_new_tokens", "min_new_tokens", "max_length", "temperature", "return_dict_in_generate"}
+                "max_new_tokens", "min_new_tokens", "max_length", "temperature", "return_dict_in_generate", "sequence_bias"}
     _GC_FIELDS = ("max_new_tokens", "max_length", "min_new_tokens", "min_length", "eos_token_id", "pad_token_id", "suppress_tokens",
                   "begin_suppress_tokens", "no_timestamps_token_id", "max_initial_timestamp_index", "return_timestamps", "task",
                   "language", "num_beams", "do_sample", "temperature", "no_speech_threshold", "logprob_threshold",
                   "compression_ratio_threshold", "condition_on_prev_tokens", "prompt_condition_type", "forced_decoder_ids",
                   "is_multilingual", "return_dict_in_generate", "force_unique_generate_call", "num_return_sequences",
-                  "repetition_penalty", "no_repeat_ngram_size", "decoder_start_token_id", "prev_sot_token_id")
+                  "repetition_penalty", "no_repeat_ngram_size", "decoder_start_token_id", "prev_sot_token_id", "sequence_bias")
 
     def _plan_key(self, kwargs) -> Optional[Tuple]:
         """Hashable fingerprint of everything that shapes a short-form call, or None if the call is not eligible for the

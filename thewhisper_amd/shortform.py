@@ -62,7 +62,7 @@ class ChunkWork:
     """Decoding state of one <= chunk_length_s piece of audio (one row of a ``generate`` batch)."""
 
     __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass", "scores",
-                 "temperatures", "attempts", "chunk_index")
+                 "temperatures", "attempts", "chunk_index", "bias")
 
     def __init__(self, feats: torch.Tensor, num_frames: Optional[int], tag: Any = None):
         # SURVEY.md section 8f-3 (opt-in, streaming.py): output tokens of the FIRST seek iteration that are already known - they
@@ -79,6 +79,9 @@ class ChunkWork:
         self.temperatures: List[float] = []
         self.attempts: List[int] = []
         self.chunk_index = 0
+        # optional per-chunk ``sequence_bias`` (HF's list or dict form): a session's own phrase list.  A pass hands the engine one list
+        # per row, the plan-level list first (``WhisperEngine.generate_greedy(sequence_bias_rows=...)``); None = the plan's alone
+        self.bias: Any = None
         self.feats = feats                      # [n_mels, frames] log-mel (device tensor); frames = 2 * T for short-form
         self.num_frames = num_frames            # frames of real audio (attention_mask.sum), None if no mask was given
         self.max_frames = int(feats.shape[-1])  # HF:...:1769 - short-form: the padded feature length, not the audio length
@@ -287,6 +290,18 @@ class Pass:
         self.engine.adopt_cross_kv(side_engine, side_slot0, n_new, len(self.works))
         self.works.extend(works)
 
+    def _greedy_kw(self) -> Dict[str, Any]:
+        """``plan.greedy`` itself when no chunk of the pass carries a bias (exactly the engine call of a pass without the feature), else
+        a copy whose ``sequence_bias_rows`` holds, per row, the plan-level list followed by the chunk's own."""
+        if not any(w.bias for w in self.works):
+            return self.plan.greedy
+        from .engine import merge_sequence_bias
+
+        kw = dict(self.plan.greedy)
+        base = kw.pop("sequence_bias", None)
+        kw["sequence_bias_rows"] = [merge_sequence_bias(base, w.bias) for w in self.works]
+        return kw
+
     def run(self, kept_columns: Optional[Sequence[int]] = None) -> None:
         """``kept_columns``: alignment-matrix columns per row as HF would keep them for the BATCH these rows are part of
         (``generate_shortform``); None = every row is a ``generate`` call of its own (the hub: one request = one call of the
@@ -316,13 +331,17 @@ class Pass:
             prompt = np.concatenate([prompt, np.stack([np.asarray(w.draft, dtype=np.int32) for w in works])], axis=1)
         if self.fallback is not None:
             return self._run_with_fallback(prompt, n_forced, n_draft, kept_columns)
+        if self.score and (plan.greedy.get("sequence_bias") or any(w.bias for w in works)):
+            raise ValueError("a sequence bias and token scores do not go together (the re-scoring pass does not know the bias: its "
+                             "log-probabilities would be those of the unbiased distribution)")
+        greedy_kw = self._greedy_kw()
         t0 = time.perf_counter()
         if n_forced:
-            out = engine.generate_greedy(prompt, n_forced=n_forced, **plan.greedy)
+            out = engine.generate_greedy(prompt, n_forced=n_forced, **greedy_kw)
         elif n_draft:
-            out = engine.generate_greedy(prompt, n_draft=n_draft, **plan.greedy)
+            out = engine.generate_greedy(prompt, n_draft=n_draft, **greedy_kw)
         else:
-            out = engine.generate_greedy(prompt, **plan.greedy)
+            out = engine.generate_greedy(prompt, **greedy_kw)
         self.greedy_s = time.perf_counter() - t0        # the engine call (blocks until the loop has finished); the rest of run() is host work
         self._keep.clear()
         seq = torch.from_numpy(np.ascontiguousarray(out["sequences"])).to(torch.long)
@@ -361,6 +380,9 @@ class Pass:
         engine, plan, works, policy = self.engine, self.plan, self.works, self.fallback
         if n_forced:
             raise ValueError("forced output prefixes and the temperature fallback do not go together (a forced token is not redrawn)")
+        if plan.greedy.get("sequence_bias") or any(w.bias for w in works):
+            raise ValueError("a sequence bias and the temperature fallback do not go together (the sampler and the re-scoring pass do not "
+                             "know the bias)")
         B, n_prompt = len(works), plan.n_prompt
         base = prompt[:, :n_prompt]
         row_ts: List[Optional[torch.Tensor]] = [None] * B

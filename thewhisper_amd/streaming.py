@@ -42,6 +42,8 @@ class AMDWhisperBackend:
         resample_kernel=None,
         token_scores: bool = False,
         temperature_fallback=None,
+        hotwords=None,
+        hotword_boost: Optional[float] = None,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -81,7 +83,16 @@ class AMDWhisperBackend:
         raises ``ValueError`` rather than run without the option.  A draft (``draft_previous_tick``) applies to the first attempt only;
         not together with ``reuse_committed_prefix`` (a forced token is not redrawn).  ``last_fallback``: for the most recent call, one
         ``{temperature, attempts}`` per seek iteration of every chunk, with the policy's ``top_k`` / ``top_p`` beside them when it sets one
-        (``FallbackPolicy(top_k=50)``: the sampled attempts draw from HF's candidate set)."""
+        (``FallbackPolicy(top_k=50)``: the sampled attempts draw from HF's candidate set).
+
+        ``hotwords`` (opt-in; a list of phrases) with ``hotword_boost`` (required with it, no default; in NATURAL-LOG UNITS ON THE
+        LOGITS: a boost of ``b`` multiplies a token's odds by ``exp(b)`` at the steps where it applies): the decoder is pushed towards
+        the phrases by the on-device sequence bias (tw_generate_greedy_biased; ``hotwords.sequence_bias_for`` turns the phrases into
+        sequences, every prefix of a phrase boosted once the tokens before it were produced).  ``set_hotwords(phrases, boost)`` changes
+        the list between calls.  With hotwords set the call ALWAYS runs the restated short-form loop; a backend whose call is not
+        eligible for it raises ``ValueError``.  ``draft_previous_tick`` stays on: the biased call returns the same ids whatever the
+        draft.  Not together with ``temperature_fallback``, ``token_scores`` or ``reuse_committed_prefix``: the sampler and the
+        re-scoring pass do not know the bias."""
         from .asr_pipeline import ASRPipeline
 
         if torch_dtype is None:
@@ -123,6 +134,33 @@ class AMDWhisperBackend:
             raise ValueError("temperature_fallback and reuse_committed_prefix do not go together (a forced token is not redrawn)")
         self.last_fallback: List[Dict[str, Any]] = []
         self._no_speech_id: Any = False           # not looked up yet
+        self.hotwords: List[str] = []
+        self.hotword_boost: Optional[float] = None
+        self._hotword_bias: Optional[Dict[Any, float]] = None     # what every chunk of a call carries (shortform.ChunkWork.bias)
+        if hotwords is not None or hotword_boost is not None:
+            self.set_hotwords(hotwords, hotword_boost)
+
+    def set_hotwords(self, phrases, boost: Optional[float]) -> None:
+        """The phrases the decoder is pushed towards from the next call on, ``boost`` in natural-log units on the logits (see
+        ``__init__``); ``set_hotwords(None, None)`` switches the option off."""
+        phrases = [] if phrases is None else list(phrases)
+        if not phrases:
+            if boost is not None:
+                raise ValueError("hotword_boost without hotwords")
+            self.hotwords, self.hotword_boost, self._hotword_bias = [], None, None
+            return
+        if boost is None:
+            raise ValueError("hotwords need hotword_boost (natural-log units on the logits; there is no default)")
+        for name in ("temperature_fallback", "token_scores", "reuse_committed_prefix"):
+            if getattr(self, name, None):
+                raise ValueError(f"hotwords and {name} do not go together (the sampler and the re-scoring pass do not know the bias)")
+        from .hotwords import sequence_bias_for
+
+        tok = getattr(self.asr_pipeline, "tokenizer", None)
+        if tok is None:
+            raise ValueError("hotwords need the pipeline's tokenizer")
+        self._hotword_bias = sequence_bias_for(tok, phrases, float(boost))
+        self.hotwords, self.hotword_boost = phrases, float(boost)
 
     def to_engine_rate(self, audio, sample_rate: int):
         """``(audio, sample_rate)`` as the engine wants it: a buffer at another rate (or int16 / multi-channel) goes through
@@ -170,10 +208,13 @@ class AMDWhisperBackend:
 
     def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
         audio, sample_rate = self.to_engine_rate(audio, sample_rate)
-        if self.reuse_committed_prefix or self.draft_previous_tick or self.temperature_fallback is not None:
+        if self.reuse_committed_prefix or self.draft_previous_tick or self.temperature_fallback is not None or self._hotword_bias:
             words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate))
             if words is not None:
                 return words
+            if self._hotword_bias:
+                raise ValueError("hotwords need the restated short-form loop, and this backend's call is not eligible for it "
+                                 "(job_codec() is None)")
             if self.temperature_fallback is not None:
                 raise ValueError("temperature_fallback needs the restated short-form loop, and this backend's call is not eligible for it "
                                  "(job_codec() is None)")
@@ -235,7 +276,7 @@ class AMDWhisperBackend:
             self._reuse_codec = codec
         codec = self._reuse_codec
         self.reuse_stats["calls"] += 1
-        job = codec.open(audio, buffer_start_time, sample_rate)
+        job = codec.open(audio, buffer_start_time, sample_rate)      # (the hotword bias travels on the works: JobCodec.open)
         eng = self.asr_pipeline.model.engine
         if len(job.works) != 1:
             self._last = None
@@ -280,7 +321,7 @@ class AMDWhisperBackend:
     def transcribe_many(self, requests, batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """Several streams' rolling buffers in ONE pipeline call: [(audio, buffer_start_time, sample_rate), ...].
         HF collates the chunks of different buffers into batched engine calls; per-stream results are unchanged."""
-        if self.temperature_fallback is not None:      # (HF's batched call knows nothing of the option: one short-form call per request)
+        if self.temperature_fallback is not None or self._hotword_bias:      # (HF's batched call knows nothing of the options: one short-form call per request)
             out, log = [], []
             for a, t0, sr in requests:
                 out.append(self.transcribe(a, t0, sr))
@@ -383,13 +424,16 @@ class JobCodec:
         b = self.backend
         mode = (b.reuse_committed_prefix, b.draft_previous_tick)     # (the ORDINARY call: the reuse / draft paths bypass HF's generate)
         policy = getattr(b, "temperature_fallback", None)            # (... and so does the temperature fallback)
+        bias = getattr(b, "_hotword_bias", None)                     # (... and the hotword bias: a per-chunk list, not part of the plan)
         b.reuse_committed_prefix = b.draft_previous_tick = False
         b.temperature_fallback = None
+        b._hotword_bias = None
         try:
             b.transcribe(np.zeros(b.sample_rate, dtype=np.float32), 0.0, b.sample_rate)
         finally:
             b.reuse_committed_prefix, b.draft_previous_tick = mode
             b.temperature_fallback = policy
+            b._hotword_bias = bias
         plan = model.last_plan
         if plan is None or not plan.return_token_timestamps or not plan.return_segments:
             return False
@@ -409,6 +453,9 @@ class JobCodec:
             nf = int(am.sum()) if am is not None else None
             works.append(ChunkWork(feats[0], nf))
             works[-1].chunk_index = len(works) - 1
+            # AMDWhisperBackend(hotwords=...): every chunk carries the backend's list, whoever builds the passes (this backend's own
+            # loop or a hub that opens the jobs itself); read per job, so set_hotwords takes effect from the next buffer on
+            works[-1].bias = getattr(self.backend, "_hotword_bias", None)
             meta.append((item["is_last"], item.get("stride")))
         if not works:
             raise ValueError("empty audio buffer")

@@ -1296,6 +1296,10 @@ __global__ void suppress_bitmap_kernel(const int* __restrict__ list, int n, unsi
 //    "timestamp mass beats every text token" rule, appends the token, and thread 0 advances the position afterwards.
 // 32 slices of <= 4 x 512 logits per stream (one stream would otherwise put the whole vocabulary on 8 CUs: 10 us of a turbo step's
 // 220; at 16 streams 512 short workgroups also beat 128 long ones, see launch_sampler)
+// The temperature sampler, the filtered draw and the scoring pass (below) are other compositions of the same pieces, each stated once:
+// the mask of one id (sampler_masked_at), the slicing and the slice's requests (vocab_slice, slice_load), the timestamp sum of a slice
+// (slice_ts_sum, block4_sum), the merge of a row's slices with the mass decision (merge_slices) and the append of the step's tokens
+// (finish_step).
 constexpr int SAMPLER_NS_MAX = 32;
 
 struct SamplerMask {  // dynamic part of the mask: uniform scalars derived from the decoding state
@@ -1344,52 +1348,100 @@ __device__ __forceinline__ SamplerMask sampler_mask(const SamplerArgs& a, int b)
   return k;
 }
 
+// Whisper's logits processors for one id (HF:generation/logits_process.py:1816-2047): is v masked?  word = suppress_bits[v >> 5]
+__device__ __forceinline__ bool sampler_masked_at(const SamplerArgs& a, const SamplerMask& k, int v, unsigned word) {
+  bool masked = ((word >> (v & 31)) & 1u) != 0;
+  if (k.mask_eos && v == a.eos) masked = true;
+  if (a.timestamps && v == a.no_ts_id) masked = true;
+  if (v >= k.b_lo && v < k.b_hi) masked = true;
+  if (v >= k.c_lo && v < k.c_hi) masked = true;
+  if (v < k.d_hi) masked = true;
+  if (v >= k.e_lo) masked = true;
+  if (k.first)
+    for (int i = 0; i < a.n_begin_suppress; ++i) masked |= (v == a.begin_suppress[i]);
+  return masked;
+}
+
+// The slice [v0, v1) of the vocabulary that workgroup `part` of NS owns: even length ceil(V / 2 NS) * 2.  vec_ok: thread t holds the
+// pairs (v, v + 1), v = v0 + (it * 256 + t) * 2, it < IT, in registers (vector path); otherwise the slice is walked id by id (scalar path)
+struct VocabSlice { int v0, v1; bool vec_ok; };
+template <int NS, int IT>
+__device__ __forceinline__ VocabSlice vocab_slice(int V, int part) {
+  const int chunk = ((V + 2 * NS - 1) / (2 * NS)) * 2;
+  const int v0 = part * chunk;
+  return VocabSlice{v0, min(v0 + chunk, V), (chunk <= IT * 512) && ((V & 1) == 0) && V >= 2};
+}
+// the vector path's requests: clamped into the row, so they can be issued whatever vec_ok says; the pair (v, v + 1) shares one bitmap word
+template <int IT>
+__device__ __forceinline__ void slice_load(const SamplerArgs& a, const float* lg, const VocabSlice& sl, int tid, float (&s0)[IT],
+                                           float (&s1)[IT], unsigned (&wb)[IT]) {
+  const int v_last = max(a.V - 2, 0) & ~1;
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int v = min(sl.v0 + (it * 256 + tid) * 2, v_last);
+    const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
+    s0[it] = x2.x;
+    s1[it] = x2.y;
+    wb[it] = a.suppress_bits[v >> 5];
+  }
+}
+
+// the block's sum of one value per thread (256 threads): wavefront reduction, then the four wavefronts in index order through LDS
+__device__ __forceinline__ float block4_sum(float x, float* red, int lane, int wave) {
+  x = wave_sum(x);
+  if (lane == 0) red[wave] = x;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// sum of exp(x - m) over the slice's unmasked timestamp ids, m = the slice's best timestamp logit; s0 / s1: the slice AFTER the mask
+// (-inf: masked or outside).  A thread adds its registers in `it` order.
+template <int IT>
+__device__ __forceinline__ float slice_ts_sum(const SamplerArgs& a, const SamplerMask& k, const VocabSlice& sl, const float* lg, int tid,
+                                              const float (&s0)[IT], const float (&s1)[IT], float m, float* red) {
+  float sum = 0.f;
+  if (a.timestamps && m > -INFINITY) {
+    if (sl.vec_ok) {
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        const int v = sl.v0 + (it * 256 + tid) * 2;
+        if (v < sl.v1) {
+          if (v >= k.ts_begin) sum += expf(s0[it] - m);
+          if (v + 1 >= k.ts_begin) sum += expf(s1[it] - m);
+        }
+      }
+    } else {
+      for (int v = max(sl.v0, k.ts_begin) + tid; v < sl.v1; v += 256)
+        sum += sampler_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? 0.f : expf(lg[v] - m);
+    }
+  }
+  return block4_sum(sum, red, tid & 63, tid >> 6);
+}
+
 template <int SAMPLER_NS, int SAMPLER_IT>
 __global__ __launch_bounds__(256) void sampler_part_kernel(SamplerArgs a) {
   __shared__ MaxIdx red_text[4], red_ts[4];
   __shared__ float red_sum[4];
   const int part = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int V = a.V;
-  const float* lg = a.logits + (long long)b * V;
-  const int chunk = ((V + 2 * SAMPLER_NS - 1) / (2 * SAMPLER_NS)) * 2;  // even slice length
-  const int v0 = part * chunk, v1 = min(v0 + chunk, V);
-  const bool vec_ok = (chunk <= SAMPLER_IT * 512) && ((V & 1) == 0) && V >= 2;
-  const int v_last = max(V - 2, 0) & ~1;
+  const float* lg = a.logits + (long long)b * a.V;
+  const VocabSlice sl = vocab_slice<SAMPLER_NS, SAMPLER_IT>(a.V, part);
+  const int v0 = sl.v0, v1 = sl.v1;
   float s0[SAMPLER_IT], s1[SAMPLER_IT];
   unsigned wb[SAMPLER_IT];
-#pragma unroll
-  for (int it = 0; it < SAMPLER_IT; ++it) {  // unconditional (clamped) requests; the pair (v, v+1) shares one bitmap word
-    const int v = min(v0 + (it * 256 + tid) * 2, v_last);
-    const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
-    s0[it] = x2.x;
-    s1[it] = x2.y;
-    wb[it] = a.suppress_bits[v >> 5];
-  }
+  slice_load(a, lg, sl, tid, s0, s1, wb);   // in front of everything else: the addresses depend on kernel arguments only
   __builtin_amdgcn_sched_barrier(0);
   const SamplerMask k = sampler_mask(a, b);
-  auto masked_at = [&](int v, unsigned word) -> bool {
-    bool masked = ((word >> (v & 31)) & 1u) != 0;
-    if (k.mask_eos && v == a.eos) masked = true;
-    if (a.timestamps && v == a.no_ts_id) masked = true;
-    if (v >= k.b_lo && v < k.b_hi) masked = true;
-    if (v >= k.c_lo && v < k.c_hi) masked = true;
-    if (v < k.d_hi) masked = true;
-    if (v >= k.e_lo) masked = true;
-    if (k.first)
-      for (int i = 0; i < a.n_begin_suppress; ++i) masked |= (v == a.begin_suppress[i]);
-    return masked;
-  };
   // ---- pass 1: best text token, best timestamp token of the slice ----
   MaxIdx bt{-INFINITY, 0x7fffffff}, bs{-INFINITY, 0x7fffffff};
-  if (vec_ok) {
+  if (sl.vec_ok) {
 #pragma unroll
     for (int it = 0; it < SAMPLER_IT; ++it) {
       const int v = v0 + (it * 256 + tid) * 2;
       const bool in = v < v1;
       const int vc = in ? v : 0;
-      s0[it] = (in && !masked_at(vc, wb[it])) ? s0[it] : -INFINITY;
-      s1[it] = (in && !masked_at(vc + 1, wb[it])) ? s1[it] : -INFINITY;
+      s0[it] = (in && !sampler_masked_at(a, k, vc, wb[it])) ? s0[it] : -INFINITY;
+      s1[it] = (in && !sampler_masked_at(a, k, vc + 1, wb[it])) ? s1[it] : -INFINITY;
       if (in) {
         MaxIdx c0{s0[it], v}, c1{s1[it], v + 1};
         if (v < k.ts_begin) bt = better(bt, c0); else bs = better(bs, c0);
@@ -1398,7 +1450,7 @@ __global__ __launch_bounds__(256) void sampler_part_kernel(SamplerArgs a) {
     }
   } else {
     for (int v = v0 + tid; v < v1; v += 256) {
-      MaxIdx c{masked_at(v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v};
+      MaxIdx c{sampler_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v};
       if (v < k.ts_begin) bt = better(bt, c); else bs = better(bs, c);
     }
   }
@@ -1409,35 +1461,16 @@ __global__ __launch_bounds__(256) void sampler_part_kernel(SamplerArgs a) {
   bt = red_text[0];
   bs = red_ts[0];
   for (int w = 1; w < 4; ++w) { bt = better(bt, red_text[w]); bs = better(bs, red_ts[w]); }
-  // ---- pass 2: sum of exp(x - slice max) over the slice's timestamp tokens ----
-  float sum = 0.f;
-  if (a.timestamps && bs.v > -INFINITY) {
-    if (vec_ok) {
-#pragma unroll
-      for (int it = 0; it < SAMPLER_IT; ++it) {
-        const int v = v0 + (it * 256 + tid) * 2;
-        if (v < v1) {
-          if (v >= k.ts_begin) sum += expf(s0[it] - bs.v);
-          if (v + 1 >= k.ts_begin) sum += expf(s1[it] - bs.v);
-        }
-      }
-    } else {
-      for (int v = max(v0, k.ts_begin) + tid; v < v1; v += 256)
-        sum += masked_at(v, a.suppress_bits[v >> 5]) ? 0.f : expf(lg[v] - bs.v);
-    }
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red_sum[wave] = sum;
-  __syncthreads();
+  // ---- pass 2: the slice's timestamp sum ----
+  const float sum = slice_ts_sum(a, k, sl, lg, tid, s0, s1, bs.v, red_sum);
   if (tid == 0) {
     SamplerPartial o;
     o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i;
-    o.sum = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
+    o.sum = sum;
     a.partials[b * SAMPLER_NS_MAX + part] = o;
   }
 }
 
-// wavefront b <- stream b; thread 0 advances the position once every wavefront has used it
 // the next step's input row of stream b (A6: HF:models/whisper/modeling_whisper.py:733-771), by one wavefront: 16-byte vectors of the
 // token row and the positional row, added in float32, rounded once, stored where tw_xt_index puts elements 8v .. 8v+7 (E per vector)
 template <typename T>
@@ -1457,32 +1490,43 @@ __device__ __forceinline__ void embed_row(const SamplerArgs& a, int b, int id, i
   }
 }
 
-// merge of the vocabulary slices of row b by one wavefront (all 64 lanes): the token HF's processors + argmax pick, in every lane
-__device__ __forceinline__ int sampler_merge(const SamplerArgs& a, int b, int lane) {
-  SamplerPartial p = a.partials[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
+// Merge of the vocabulary slices of row b by one wavefront, in every lane: the row's best text and timestamp token over the unmasked
+// logits and the "timestamp mass beats every text token" decision (log-sum-exp merge of the slices' timestamp sums).  P: SamplerPartial
+// or SamplePartial, which begin with the same five fields.
+struct SliceMerge { MaxIdx bt, bs; bool force_ts; };
+template <typename P>
+__device__ __forceinline__ SliceMerge merge_slices(const SamplerArgs& a, const P* parts, int b, int lane) {
+  const P p = parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
   const bool on = lane < a.n_slices;
-  MaxIdx bt{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, bs{on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff};
-  const float my_m = bs.v;
-  bt = wave_best(bt);
-  bs = wave_best(bs);
-  float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - bs.v) : 0.f;  // log-sum-exp merge of the slices
+  SliceMerge m{{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, {on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff}, false};
+  const float my_m = m.bs.v;
+  m.bt = wave_best(m.bt);
+  m.bs = wave_best(m.bs);
+  const float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - m.bs.v) : 0.f;
   const float tot = wave_sum(part_sum);
-  bool force_ts = false;
-  if (a.timestamps && bs.v > -INFINITY) force_ts = (bs.v + logf(tot)) > bt.v;
-  int choice;
-  if (force_ts) choice = bs.i;
-  else choice = (bs.v > bt.v) ? bs.i : bt.i;
+  if (a.timestamps && m.bs.v > -INFINITY) m.force_ts = (m.bs.v + logf(tot)) > m.bt.v;
+  return m;
+}
+
+// the token HF's processors + argmax pick for row b, in every lane
+__device__ __forceinline__ int sampler_merge(const SamplerArgs& a, int b, int lane) {
+  const SliceMerge m = merge_slices(a, a.partials, b, lane);
+  int choice = (m.force_ts || m.bs.v > m.bt.v) ? m.bs.i : m.bt.i;
   if (choice == 0x7fffffff) choice = 0;  // everything masked: torch.argmax of all -inf is 0
   return choice;
 }
 
-__global__ __launch_bounds__(1024) void sampler_finish_kernel(SamplerArgs a) {
+// The last launch of a step, whichever sampler ran: ONE workgroup, wavefront w takes streams w, w + 16, ...; choice_of(b, lane) yields
+// the stream's sampled token in every lane.  Lane 0 appends (a prompt token while the prompt lasts, pad_id once finished), the wavefront
+// writes the next step's input row, and thread 0 advances the position once every wavefront has used it.
+template <typename ChoiceOf>
+__device__ __forceinline__ void finish_step(const SamplerArgs& a, ChoiceOf choice_of) {
   const int tid = threadIdx.x, lane = tid & 63;
-  const int pos_now = a.stt->pos;              // (thread 0 advances it behind the barrier at the end)
-  for (int b = tid >> 6; b < a.B; b += 16) {  // wavefront w <- streams w, w+16, ...
+  const int pos_now = a.stt->pos;
+  for (int b = tid >> 6; b < a.B; b += 16) {
     int next_id = 0;
     const SamplerMask k = sampler_mask(a, b);
-    const int choice = sampler_merge(a, b, lane);
+    const int choice = choice_of(b, lane);
     if (lane == 0) {
       const int cur_len = a.stt->pos + 1;
       int* seq = a.seq + (long long)b * a.seq_ld;
@@ -1510,6 +1554,10 @@ __global__ __launch_bounds__(1024) void sampler_finish_kernel(SamplerArgs a) {
   }
   __syncthreads();
   if (tid == 0) a.stt->pos += 1;
+}
+
+__global__ __launch_bounds__(1024) void sampler_finish_kernel(SamplerArgs a) {
+  finish_step(a, [&](int b, int lane) { return sampler_merge(a, b, lane); });
 }
 
 // Rows mode (draft-and-verify; SamplerArgs): every row's token, the first position at which a stream's token differs from the token the
@@ -1573,15 +1621,13 @@ __global__ __launch_bounds__(1024) void sampler_rows_finish_kernel(SamplerArgs a
 }
 
 // Temperature sampling (tw_generate_sample, api.hip; the draw is defined at SampleArgs, tw_common.h): the greedy sampler's two launches
-// with Gumbel noise on the scaled logits, as kernels of their own so that the greedy sampler's stay as they are.
+// with Gumbel noise on the scaled logits.
 //  * sample_part_kernel: the slicing, the register-resident slice and the vector / scalar paths of sampler_part_kernel.  Per slice: the
 //    greedy partials of the UNSCALED logits (best text, best timestamp, sum exp(x - slice max) over timestamps: what the mass rule is
 //    decided on) and the best perturbed text and timestamp (value, id).  One Philox4x32-10 block serves the ids 4j .. 4j + 3, so a
 //    thread's pair (v, v + 1), v even, costs one block; the block and the two logf per logit are VALU work behind the logit requests.
-//  * sample_finish_kernel: merges the unscaled partials in sampler_merge's order (a mass decision equals the greedy one bit for bit on
-//    equal logits); mass rule fired: the best perturbed timestamp, else the better of the two perturbed maxima (lower id on a tie);
-//    then sampler_finish_kernel's bookkeeping, line for line.
-// The mask is score_masked_at: ONE restatement of sampler_part_kernel's mask serves the scoring pass and the sampling kernels.
+//  * sample_finish_kernel: merge_slices on the unscaled partials (a mass decision equals the greedy one bit for bit on equal logits);
+//    mass rule fired: the best perturbed timestamp, else the better of the two perturbed maxima (lower id on a tie); then finish_step.
 struct Philox4 { unsigned w[4]; };
 __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
 #pragma unroll
@@ -1598,7 +1644,6 @@ __device__ __forceinline__ float gumbel_of(unsigned w) {
   const float u = (float)((w >> 9) * 2u + 1u) * 5.9604644775390625e-08f;   // 2^-24; the integer is odd and below 2^24: exact
   return -logf(-logf(u));
 }
-__device__ __forceinline__ bool score_masked_at(const SamplerArgs& a, const SamplerMask& k, int v, unsigned word);   // (below: the scoring pass's)
 
 template <int SAMPLER_NS, int SAMPLER_IT>
 __global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
@@ -1607,22 +1652,12 @@ __global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
   const SamplerArgs& a = sa.s;
   const int part = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int V = a.V;
-  const float* lg = a.logits + (long long)b * V;
-  const int chunk = ((V + 2 * SAMPLER_NS - 1) / (2 * SAMPLER_NS)) * 2;  // even slice length
-  const int v0 = part * chunk, v1 = min(v0 + chunk, V);
-  const bool vec_ok = (chunk <= SAMPLER_IT * 512) && ((V & 1) == 0) && V >= 2;
-  const int v_last = max(V - 2, 0) & ~1;
+  const float* lg = a.logits + (long long)b * a.V;
+  const VocabSlice sl = vocab_slice<SAMPLER_NS, SAMPLER_IT>(a.V, part);
+  const int v0 = sl.v0, v1 = sl.v1;
   float s0[SAMPLER_IT], s1[SAMPLER_IT];
   unsigned wb[SAMPLER_IT];
-#pragma unroll
-  for (int it = 0; it < SAMPLER_IT; ++it) {  // unconditional (clamped) requests; the pair (v, v+1) shares one bitmap word
-    const int v = min(v0 + (it * 256 + tid) * 2, v_last);
-    const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
-    s0[it] = x2.x;
-    s1[it] = x2.y;
-    wb[it] = a.suppress_bits[v >> 5];
-  }
+  slice_load(a, lg, sl, tid, s0, s1, wb);   // in front of everything else, as in sampler_part_kernel
   __builtin_amdgcn_sched_barrier(0);
   const SamplerMask k = sampler_mask(a, b);
   const unsigned p = (unsigned)a.stt->pos;
@@ -1633,14 +1668,14 @@ __global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
   auto perturbed = [&](float x, unsigned w) -> float { return noisy ? __fadd_rn(__fmul_rn(x, inv_t), gumbel_of(w)) : x; };
   // ---- pass 1: best text / timestamp of the slice, unscaled and perturbed ----
   MaxIdx bt{-INFINITY, 0x7fffffff}, bs{-INFINITY, 0x7fffffff}, pt{-INFINITY, 0x7fffffff}, ps{-INFINITY, 0x7fffffff};
-  if (vec_ok) {
+  if (sl.vec_ok) {
 #pragma unroll
     for (int it = 0; it < SAMPLER_IT; ++it) {
       const int v = v0 + (it * 256 + tid) * 2;
       const bool in = v < v1;
       const int vc = in ? v : 0;
-      s0[it] = (in && !score_masked_at(a, k, vc, wb[it])) ? s0[it] : -INFINITY;
-      s1[it] = (in && !score_masked_at(a, k, vc + 1, wb[it])) ? s1[it] : -INFINITY;
+      s0[it] = (in && !sampler_masked_at(a, k, vc, wb[it])) ? s0[it] : -INFINITY;
+      s1[it] = (in && !sampler_masked_at(a, k, vc + 1, wb[it])) ? s1[it] : -INFINITY;
       if (in) {
         MaxIdx c0{s0[it], v}, c1{s1[it], v + 1};
         MaxIdx q0 = c0, q1 = c1;
@@ -1656,7 +1691,7 @@ __global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
     }
   } else {
     for (int v = v0 + tid; v < v1; v += 256) {
-      MaxIdx c{score_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v};
+      MaxIdx c{sampler_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v};
       MaxIdx q = c;
       if (noisy) {
         const Philox4 r = philox4x32_10((unsigned)v >> 2, p, o0, o1, k0, k1);
@@ -1674,93 +1709,33 @@ __global__ __launch_bounds__(256) void sample_part_kernel(SampleArgs sa) {
   __syncthreads();
   bt = red[0][0]; bs = red[1][0]; pt = red[2][0]; ps = red[3][0];
   for (int w = 1; w < 4; ++w) { bt = better(bt, red[0][w]); bs = better(bs, red[1][w]); pt = better(pt, red[2][w]); ps = better(ps, red[3][w]); }
-  // ---- pass 2: sum of exp(x - slice max) over the slice's timestamp tokens (unscaled: sampler_part_kernel's, operation for operation) ----
-  float sum = 0.f;
-  if (a.timestamps && bs.v > -INFINITY) {
-    if (vec_ok) {
-#pragma unroll
-      for (int it = 0; it < SAMPLER_IT; ++it) {
-        const int v = v0 + (it * 256 + tid) * 2;
-        if (v < v1) {
-          if (v >= k.ts_begin) sum += expf(s0[it] - bs.v);
-          if (v + 1 >= k.ts_begin) sum += expf(s1[it] - bs.v);
-        }
-      }
-    } else {
-      for (int v = max(v0, k.ts_begin) + tid; v < v1; v += 256)
-        sum += score_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? 0.f : expf(lg[v] - bs.v);
-    }
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red_sum[wave] = sum;
-  __syncthreads();
+  // ---- pass 2: the slice's timestamp sum, on the unscaled logits ----
+  const float sum = slice_ts_sum(a, k, sl, lg, tid, s0, s1, bs.v, red_sum);
   if (tid == 0) {
     SamplePartial o;
     o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i;
-    o.sum = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
+    o.sum = sum;
     o.pt_v = pt.v; o.pt_i = pt.i; o.ps_v = ps.v; o.ps_i = ps.i;
     o.pad_[0] = o.pad_[1] = o.pad_[2] = 0;
     sa.parts[b * SAMPLER_NS_MAX + part] = o;
   }
 }
 
-// merge of the vocabulary slices of row b by one wavefront (all 64 lanes): the mass decision on the unscaled partials in sampler_merge's
-// order and operations, the token from the perturbed ones
+// the token of row b, in every lane: the mass decision on the unscaled partials, the token from the perturbed ones
 __device__ __forceinline__ int sample_merge(const SampleArgs& sa, int b, int lane) {
   const SamplerArgs& a = sa.s;
-  SamplePartial p = sa.parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
+  const SamplePartial p = sa.parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
   const bool on = lane < a.n_slices;
-  MaxIdx bt{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, bs{on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff};
   MaxIdx pt{on ? p.pt_v : -INFINITY, on ? p.pt_i : 0x7fffffff}, ps{on ? p.ps_v : -INFINITY, on ? p.ps_i : 0x7fffffff};
-  const float my_m = bs.v;
-  bt = wave_best(bt);
-  bs = wave_best(bs);
   pt = wave_best(pt);
   ps = wave_best(ps);
-  float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - bs.v) : 0.f;  // log-sum-exp merge of the slices
-  const float tot = wave_sum(part_sum);
-  bool force_ts = false;
-  if (a.timestamps && bs.v > -INFINITY) force_ts = (bs.v + logf(tot)) > bt.v;
-  int choice = force_ts ? ps.i : better(pt, ps).i;   // (text ids lie below timestamp ids: a tie goes to the text token)
+  int choice = merge_slices(a, sa.parts, b, lane).force_ts ? ps.i : better(pt, ps).i;   // (text ids lie below timestamp ids: a tie goes to the text token)
   if (choice == 0x7fffffff) choice = 0;  // everything masked
   return choice;
 }
 
 __global__ __launch_bounds__(1024) void sample_finish_kernel(SampleArgs sa) {
-  const SamplerArgs& a = sa.s;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int pos_now = a.stt->pos;              // (thread 0 advances it behind the barrier at the end)
-  for (int b = tid >> 6; b < a.B; b += 16) {  // wavefront w <- streams w, w+16, ...
-    int next_id = 0;
-    const SamplerMask k = sampler_mask(a, b);
-    const int choice = sample_merge(sa, b, lane);
-    if (lane == 0) {
-      const int cur_len = a.stt->pos + 1;
-      int* seq = a.seq + (long long)b * a.seq_ld;
-      if (k.in_prompt) {
-        next_id = seq[cur_len];
-        a.cur_ids[b] = next_id;
-      } else if (k.fin) {
-        seq[cur_len] = a.pad;
-        a.cur_ids[b] = a.pad;
-        next_id = a.pad;
-      } else {
-        seq[cur_len] = choice;
-        a.cur_ids[b] = choice;
-        next_id = choice;
-        if (a.timestamps && choice >= k.ts_begin) a.last_ts[b] = choice;
-        if (choice == a.eos) a.finished[b] = 1;
-      }
-    }
-    if (a.x_next) {   // (kernel-uniform) the token just appended is the next step's input at position pos + 1
-      const int id = __builtin_amdgcn_readfirstlane(next_id);   // lane 0's
-      if (a.dtype == 1) embed_row<bf16_t>(a, b, id, pos_now + 1, lane);
-      else if (a.dtype == 2) embed_row<f16_t>(a, b, id, pos_now + 1, lane);
-      else embed_row<float>(a, b, id, pos_now + 1, lane);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) a.stt->pos += 1;
+  finish_step(sa.s, [&](int b, int lane) { return sample_merge(sa, b, lane); });
 }
 
 // Scoring (tw_score_tokens, api.hip): log-softmax of the GIVEN next token of every row of a rows-mode launch, twice - over the raw
@@ -1771,21 +1746,7 @@ __global__ __launch_bounds__(1024) void sample_finish_kernel(SampleArgs sa) {
 //  * score_finish_kernel: one workgroup, wavefront r merges the 32 slices of row r in double precision by a fixed butterfly, applies the
 //    "timestamp mass beats every text token" rule (text drops out of the masked normaliser), and lane 0 stores both numbers.
 // The slicing and the merge order are compile-time constants: a row's numbers do not depend on the other rows of its launch.
-// score_masked_at is sampler_part_kernel's mask, spelled out a second time so that the sampler's kernels stay as they are.
 constexpr int SCORE_NS = 32;
-
-__device__ __forceinline__ bool score_masked_at(const SamplerArgs& a, const SamplerMask& k, int v, unsigned word) {
-  bool masked = ((word >> (v & 31)) & 1u) != 0;
-  if (k.mask_eos && v == a.eos) masked = true;
-  if (a.timestamps && v == a.no_ts_id) masked = true;
-  if (v >= k.b_lo && v < k.b_hi) masked = true;
-  if (v >= k.c_lo && v < k.c_hi) masked = true;
-  if (v < k.d_hi) masked = true;
-  if (v >= k.e_lo) masked = true;
-  if (k.first)
-    for (int i = 0; i < a.n_begin_suppress; ++i) masked |= (v == a.begin_suppress[i]);
-  return masked;
-}
 
 // the block's value of three per-thread values: wavefront reduction, then the four wavefronts in a fixed order through LDS
 template <bool MAX>
@@ -1808,29 +1769,21 @@ __global__ __launch_bounds__(256) void score_part_kernel(ScoreArgs sa) {
   const SamplerArgs& a = sa.s;
   const int part = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int V = a.V;
-  const float* lg = a.logits + (long long)b * V;
-  const int chunk = ((V + 2 * SCORE_NS - 1) / (2 * SCORE_NS)) * 2;  // even slice length
-  const int v0 = part * chunk, v1 = min(v0 + chunk, V);
-  const bool vec_ok = (chunk <= SCORE_IT * 512) && ((V & 1) == 0) && V >= 2;
-  const int v_last = max(V - 2, 0) & ~1;
+  const float* lg = a.logits + (long long)b * a.V;
+  const VocabSlice sl = vocab_slice<SCORE_NS, SCORE_IT>(a.V, part);
+  const int v0 = sl.v0, v1 = sl.v1;
+  const bool vec_ok = sl.vec_ok;
   float s0[SCORE_IT], s1[SCORE_IT];
   unsigned wb[SCORE_IT];
-  if (vec_ok) {
-#pragma unroll
-    for (int it = 0; it < SCORE_IT; ++it) {  // unconditional (clamped) requests; the pair (v, v+1) shares one bitmap word
-      const int v = min(v0 + (it * 256 + tid) * 2, v_last);
-      const float2 x2 = *reinterpret_cast<const float2*>(lg + v);
-      s0[it] = x2.x;
-      s1[it] = x2.y;
-      wb[it] = a.suppress_bits[v >> 5];
-    }
-  }
+  // Only where the slice is read from registers, and not pinned in front of the mask's scalar loads by a sched_barrier as in the two
+  // sampler kernels: this pass runs once per call, not once per step, and its scalar path reads every logit twice whatever is requested
+  // here - the requests it would never use are spared instead.
+  if (vec_ok) slice_load(a, lg, sl, tid, s0, s1, wb);
   const SamplerMask k = sampler_mask(a, b);
   // ---- pass 1: the three maxima (0 raw, 1 unmasked text, 2 unmasked timestamps); cls = the set an element's exp goes to (-1 none) ----
   float m[3] = {-INFINITY, -INFINITY, -INFINITY};
   int cls0[SCORE_IT], cls1[SCORE_IT];
-  auto classify = [&](int v, unsigned word) -> int { return score_masked_at(a, k, v, word) ? -1 : (v < k.ts_begin ? 1 : 2); };
+  auto classify = [&](int v, unsigned word) -> int { return sampler_masked_at(a, k, v, word) ? -1 : (v < k.ts_begin ? 1 : 2); };
   if (vec_ok) {
 #pragma unroll
     for (int it = 0; it < SCORE_IT; ++it) {
@@ -1927,7 +1880,7 @@ __global__ __launch_bounds__(1024) void score_finish_kernel(ScoreArgs sa) {
         const double M = fmax(xM, tM);
         if (M > -INFINITY) lse_m = M + log((xM > -INFINITY ? xS * exp(xM - M) : 0.0) + (tM > -INFINITY ? tS * exp(tM - M) : 0.0));
       }
-      const bool t_masked = score_masked_at(a, k, t, a.suppress_bits[t >> 5]) || (force_ts && t < k.ts_begin);
+      const bool t_masked = sampler_masked_at(a, k, t, a.suppress_bits[t >> 5]) || (force_ts && t < k.ts_begin);
       const long long o = (long long)stream * sa.out_ld + p + 1;
       sa.out_raw[o] = (float)(z - lse_raw);
       sa.out_masked[o] = t_masked ? -INFINITY : (float)(z - lse_m);
@@ -1936,12 +1889,11 @@ __global__ __launch_bounds__(1024) void score_finish_kernel(ScoreArgs sa) {
   }
 }
 
-// Top-k / top-p filtered draw (tw_generate_sample_filtered, api.hip; the rule is stated at FilterArgs, tw_common.h): three launches, as
-// kernels of their own so that the temperature sampler's stay as they are.
-//  * sample_part_kernel, unchanged: its unscaled partials carry the mass decision; its perturbed partials are not read.
+// Top-k / top-p filtered draw (tw_generate_sample_filtered, api.hip; the rule is stated at FilterArgs, tw_common.h): three launches.
+//  * sample_part_kernel, as it is: its unscaled partials carry the mass decision; its perturbed partials are not read.
 //  * sample_filter_kernel: ONE workgroup of 1024 threads per row, the row in registers (kFilterPerThread values per thread, as keys: the
-//    order-preserving integer image of the float, -0 folded onto +0).  Every wavefront repeats sample_merge's mass decision from the
-//    partials; the mask is score_masked_at plus "text out" when the rule fired.  tau: the largest key t with count(key >= t) >= k, bit
+//    order-preserving integer image of the float, -0 folded onto +0).  Every wavefront takes the mass decision from the partials
+//    (merge_slices); the mask is sampler_masked_at plus "text out" when the rule fired.  tau: the largest key t with count(key >= t) >= k, bit
 //    by bit from the top (32 rounds, one block count each).  The keys of x then give way to the keys of y = x * inv_t of the ids kept so
 //    far (0: dropped).  Top-p: the smallest key c with sum of exp(y - m) over {key > c} below top_p * Z, by the same search (32 rounds,
 //    one block sum each); a thread's sum runs over its registers in float in a fixed order, the block's over the threads in double in a
@@ -1949,7 +1901,7 @@ __global__ __launch_bounds__(1024) void score_finish_kernel(ScoreArgs sa) {
 //    block per four consecutive ids, computed only where one of them is kept) and one choice[b] store.
 //    The slice, the trees and the searches are compile-time shapes: a row's token depends on its logits, its state and its row of the
 //    per-row arrays alone.  Rows still in the prompt, finished rows and rows that sit the call out leave at once.
-//  * sample_choice_finish_kernel: sample_finish_kernel's bookkeeping, line for line, on choice[b].
+//  * sample_choice_finish_kernel: finish_step on choice[b].
 __device__ __forceinline__ unsigned filter_key(float x) {
   const unsigned u = __float_as_uint(x == 0.f ? 0.f : x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -1961,22 +1913,6 @@ constexpr unsigned kFilterNegInfKey = 0x007fffffu;   // filter_key(-inf): masked
 __device__ __forceinline__ int filter_opaque(int x) {
   asm volatile("" : "+v"(x));
   return x;
-}
-
-// sample_merge's mass decision (its order and operations on the unscaled partials), in every lane
-__device__ __forceinline__ bool sample_mass_fired(const SampleArgs& sa, int b, int lane) {
-  const SamplerArgs& a = sa.s;
-  SamplePartial p = sa.parts[b * SAMPLER_NS_MAX + min(lane, a.n_slices - 1)];
-  const bool on = lane < a.n_slices;
-  MaxIdx bt{on ? p.bt_v : -INFINITY, on ? p.bt_i : 0x7fffffff}, bs{on ? p.bs_v : -INFINITY, on ? p.bs_i : 0x7fffffff};
-  const float my_m = bs.v;
-  bt = wave_best(bt);
-  bs = wave_best(bs);
-  float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - bs.v) : 0.f;  // log-sum-exp merge of the slices
-  const float tot = wave_sum(part_sum);
-  bool force_ts = false;
-  if (a.timestamps && bs.v > -INFINITY) force_ts = (bs.v + logf(tot)) > bt.v;
-  return force_ts;
 }
 
 // the block's sum of one value per wavefront (already reduced over the wavefront), wavefronts in index order; `red` alternates between
@@ -2005,7 +1941,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(FilterArgs fa) {
   const SamplerMask k = sampler_mask(a, b);
   if (k.in_prompt || k.fin) return;   // (uniform over the workgroup) the finish kernel does not read choice[b] of such a row
   const float* lg = a.logits + (long long)b * V;
-  const bool force_ts = sample_mass_fired(sa, b, lane);
+  const bool force_ts = merge_slices(a, sa.parts, b, lane).force_ts;
   const bool noisy = sa.noisy[b] != 0;
   const float inv_t = sa.inv_t[b];
   const int top_k = noisy ? fa.top_k[b] : 0;
@@ -2029,7 +1965,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(FilterArgs fa) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int v = v0 + j;
-        const bool out = v >= V || score_masked_at(a, k, min(v, V - 1), word) || (force_ts && v < k.ts_begin);
+        const bool out = v >= V || sampler_masked_at(a, k, min(v, V - 1), word) || (force_ts && v < k.ts_begin);
         key[4 * q + j] = out ? kFilterNegInfKey : filter_key(__uint_as_float(key[4 * q + j]));
       }
     }
@@ -2132,40 +2068,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(FilterArgs fa) {
 }
 
 __global__ __launch_bounds__(1024) void sample_choice_finish_kernel(FilterArgs fa) {
-  const SamplerArgs& a = fa.sm.s;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int pos_now = a.stt->pos;              // (thread 0 advances it behind the barrier at the end)
-  for (int b = tid >> 6; b < a.B; b += 16) {  // wavefront w <- streams w, w+16, ...
-    int next_id = 0;
-    const SamplerMask k = sampler_mask(a, b);
-    if (lane == 0) {
-      const int cur_len = a.stt->pos + 1;
-      int* seq = a.seq + (long long)b * a.seq_ld;
-      if (k.in_prompt) {
-        next_id = seq[cur_len];
-        a.cur_ids[b] = next_id;
-      } else if (k.fin) {
-        seq[cur_len] = a.pad;
-        a.cur_ids[b] = a.pad;
-        next_id = a.pad;
-      } else {
-        const int choice = fa.choice[b];
-        seq[cur_len] = choice;
-        a.cur_ids[b] = choice;
-        next_id = choice;
-        if (a.timestamps && choice >= k.ts_begin) a.last_ts[b] = choice;
-        if (choice == a.eos) a.finished[b] = 1;
-      }
-    }
-    if (a.x_next) {   // (kernel-uniform) the token just appended is the next step's input at position pos + 1
-      const int id = __builtin_amdgcn_readfirstlane(next_id);   // lane 0's
-      if (a.dtype == 1) embed_row<bf16_t>(a, b, id, pos_now + 1, lane);
-      else if (a.dtype == 2) embed_row<f16_t>(a, b, id, pos_now + 1, lane);
-      else embed_row<float>(a, b, id, pos_now + 1, lane);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) a.stt->pos += 1;
+  finish_step(fa.sm.s, [&](int b, int) { return fa.choice[b]; });   // (read, but not used, for a row the filter kernel left early)
 }
 
 // Per-stream sequence bias (tw_generate_greedy_biased; the rule is stated in include/thewhisper.h): one launch in front of the step's

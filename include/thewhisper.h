@@ -243,6 +243,38 @@ typedef struct tw_bias_opts {
 int tw_generate_greedy_biased(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
                               const tw_bias_opts* bopts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
 
+/* tw_generate_greedy for rows whose prompts differ in length ("ragged prompts"): the batch is LEFT-padded to one length n_prompt, as HF
+ * batches Whisper's previous-text prompts (HF:models/whisper/generation_whisper.py:1709-1772 pads decoder_input_ids on the left and passes
+ * decoder_attention_mask = ids != pad), and n_pad_host[b] says how many leading entries of row b are padding.
+ *
+ * THE RULE.  Row b's first n_pad[b] prompt entries are padding: their token values (any valid id) are ignored and returned as given.
+ * Row b at absolute position p >= n_pad[b] is at ROW POSITION q = p - n_pad[b]: it takes pos_emb[q], its self-attention K / V go to cache
+ * slot q, and it attends slots 0 .. q.  At p < n_pad[b] the row idles: it is treated as row position 0 - it writes slot 0, which the real
+ * position 0 overwrites later, and attends that one key - and nothing ever reads what it computes.  Everything else keeps ABSOLUTE
+ * positions: the sequence buffer, the begin index (n_prompt, common to all rows), the suppress lists, begin-suppress, the min_new_tokens
+ * <eos> mask, the timestamp grammar (it reads history from n_prompt on only), the alignment rows (recorded at absolute p, so
+ * tw_token_timestamps and tw_get_alignment work unchanged), out_len_host, tw_last_timings and the step count.
+ *
+ * CONSEQUENCE.  Row b's generated ids and its alignment rows at p >= n_prompt are bit for bit what tw_generate_greedy produces for that
+ * row ALONE when it is given the row's n_prompt - n_pad[b] real tokens as its prompt, the same max_new_tokens and min_new_tokens, and
+ * max_length - n_pad[b]: per row every kernel sees exactly the data layout of the alone call, and the self-attention's result does not
+ * depend on the 64-key bucket the host picks for a step.  A row's result does not depend on its slot, its batch-mates or their padding.
+ * This is NOT HF's arithmetic for a padded batch: HF's generate builds no decoder position ids from the mask, so a padded row keeps
+ * absolute positions there and its result depends on how long its batch-mates' prompts are ("Ragged decoder prompts"); it IS
+ * HF's result for the row at batch size 1.
+ *
+ * n_pad_host == NULL or all zeros: the call IS tw_generate_greedy, launch for launch.  Otherwise the prompt is consumed one position per
+ * step as there, a step issues one launch more (the embedding of a ragged step is a launch of its own; the embedding, the K / V cache
+ * write and the self attention are instantiations of their own, every other launch is the plain step's), and captured step graphs are
+ * kept apart from the plain call's.  Every context dtype is supported with the same equality, TW_BF16_MXFP8 (W8A8) included.  The table
+ * lives in context-owned device memory, allocated by the first padded call of a context (a sibling owns its own) and freed by tw_destroy.
+ *
+ * TW_EINVAL in addition to tw_generate_greedy's, all before any work is enqueued (the context stays usable): a negative n_pad[b],
+ * n_pad[b] >= n_prompt (a row needs one real token), n_forced or n_draft set in a padded call, B > 64.  tw_generate_greedy_biased,
+ * tw_generate_sample* and tw_score_tokens take no padding. */
+int tw_generate_greedy_ragged(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
+                              const int32_t* n_pad_host /* [B] */, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
+
 /* Temperature sampling on the device.  Replaces: GenerationMixin._sample with do_sample=True and a TemperatureLogitsWarper behind
  * Whisper's logits processors (HF:generation/utils.py:1293-1312, :2925-2931), as WhisperGenerationMixin.generate_with_fallback invokes it
  * for the temperatures behind 0 (HF:models/whisper/generation_whisper.py:970-1116; thewhisper_amd/fallback.py restates that ladder).

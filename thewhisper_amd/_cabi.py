@@ -74,6 +74,8 @@ SYMBOLS = [
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_greedy_biased", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
                                             C.POINTER(tw_bias_opts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_generate_greedy_ragged", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),

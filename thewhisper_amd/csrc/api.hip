@@ -109,6 +109,9 @@ struct tw_ctx {
   // tw_generate_greedy_biased: the packed table of the call's sequences (tw_common.h: SeqBiasArgs) and its pinned staging, both of
   // kSeqBiasTabWords words, allocated by the first biased call of the context
   int* bias_tab = nullptr; int* h_bias = nullptr;
+  // tw_generate_greedy_ragged: the per-stream padding lengths [64] the ragged kernels read (tw_common.h: tw_row_pos) and their pinned
+  // staging, allocated by the first ragged call of the context
+  int* n_pad_tab = nullptr; int* h_n_pad = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
   size_t row_ids_cap = 0;
   // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
@@ -264,6 +267,7 @@ int tw_destroy(tw_ctx* c) {
   if (c->h_verify) (void)hipHostFree(c->h_verify);
   if (c->h_score) (void)hipHostFree(c->h_score);
   if (c->h_bias) (void)hipHostFree(c->h_bias);
+  if (c->h_n_pad) (void)hipHostFree(c->h_n_pad);
   for (int i = 0; i < 5; ++i) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
@@ -945,11 +949,15 @@ bool getenv_off_fuse() {
 // so a row's logits are bit for bit what the one-position step would have produced (k_decode.hip: one reduction order for every B)
 // record_alignment = false: the cross attention is launched with Ha = 0 and no slot table, so the alignment rows an earlier
 // tw_generate_greedy recorded stay as they are (tw_score_tokens); its output does not depend on it
+// n_pad != nullptr (device, [64]): a step of tw_generate_greedy_ragged (ordinary step only) - the embedding, the K / V^T scatter of the QKV
+// launch and the self attention are the ragged instantiations (tw_common.h: tw_row_pos); every other launch is the plain step's
 int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = nullptr, bool embed = true, bool rows_logits = false,
-                bool record_alignment = true) {
+                bool record_alignment = true, const int* n_pad = nullptr) {
   const int d = c->d, H = c->H, F = c->ffn, T = c->T, P = c->P, dt = c->dtype;
   const size_t e = c->esz;
-  if (embed) HIPCHK(c, launch_embed(dt, rs > 0 ? ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
+  if (n_pad && (rs != 0 || !embed)) return fail(c, TW_EINVAL, "decode_core: a ragged step is an ordinary step with its own embedding");
+  if (n_pad) HIPCHK(c, launch_embed_ragged(dt, c->cur_ids, c->stt, n_pad, c->tok_emb, c->dec_pos, c->dx0, B, d, st));
+  else if (embed) HIPCHK(c, launch_embed(dt, rs > 0 ? ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
   void* xin = c->dx0;
   void* xmid = c->dx1;
   const int Pp = (P + 63) / 64 * 64;
@@ -969,9 +977,11 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = n
       a.y = c->dq; a.ldy = d; a.kcache = sk; a.vcache = sv; a.cache_bstride = (long long)Pp * d; a.cache_hstride = (long long)Pp * 64; a.d_model = d; a.stt = c->stt;
       a.u = fq_on ? c->du : nullptr;
       a.rows_streams = rs;
+      a.n_pad = n_pad;
       HIPCHK(c, launch_gemv(dt, a, st));
     }
-    HIPCHK(c, launch_dec_self_attn(dt, c->dq, sk, sv, Pp, c->datt, B, H, c->dec_key_bound > 0 ? c->dec_key_bound : P, c->stt, rs, st));
+    if (n_pad) HIPCHK(c, launch_dec_self_attn_ragged(dt, c->dq, sk, sv, Pp, c->datt, B, H, c->dec_key_bound > 0 ? c->dec_key_bound : P, c->stt, n_pad, st));
+    else HIPCHK(c, launch_dec_self_attn(dt, c->dq, sk, sv, Pp, c->datt, B, H, c->dec_key_bound > 0 ? c->dec_key_bound : P, c->stt, rs, st));
     {
       GemvArgs a{};
       a.x = c->datt; a.ldx = d; a.W = L.wo; a.wscale = L.s_o; a.a16 = c->a16; a.tr = L.tr_o; a.bias = L.bo; a.N = (fq_on ? 2 : 1) * d; a.K = d; a.B = B;
@@ -1225,9 +1235,14 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
 // sampler is launch_sample; rows with temperature < 0 start finished.  fo != nullptr (validated by tw_generate_sample_filtered, which
 // hands it on only when some sampled row has a filter on): every step's sampler is launch_sample_filtered.  bo != nullptr
 // (tw_generate_greedy_biased, greedy only, n_seq > 0): launch_seq_bias runs in front of every sampler launch, rows mode included.
+// n_pad != nullptr (tw_generate_greedy_ragged, which validated it: plain greedy only, no forced / draft tokens, some row padded): every
+// step is a ragged step (decode_core) that embeds its own input, so the sampler writes no next input row.
 static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
-                         const tw_filter_opts* fo, const tw_bias_opts* bo, int32_t* out_ids, int32_t* out_len, void* stream) {
-  const char* fn = bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
+                         const tw_filter_opts* fo, const tw_bias_opts* bo, int32_t* out_ids, int32_t* out_len, void* stream,
+                         const int32_t* n_pad = nullptr) {
+  const char* fn = n_pad ? "tw_generate_greedy_ragged" : bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
+  const bool ragged = n_pad != nullptr;
+  if (ragged && (so || fo || bo || o->n_forced != 0 || o->n_draft != 0)) return fail(c, TW_EINVAL, "%s: padding goes with the plain greedy call only", fn);
   if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
   if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
@@ -1308,6 +1323,12 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     memcpy(c->h_bias, bias_tab.data(), sizeof(int) * bias_tab.size());
     HIPCHK(c, hipMemcpyAsync(c->bias_tab, c->h_bias, sizeof(int) * bias_tab.size(), hipMemcpyHostToDevice, st));
   }
+  if (ragged) {   // the same for the padding lengths (the staging is not touched again before this call's stream synchronisation)
+    if (!c->n_pad_tab) ALLOC(c, c->n_pad_tab, sizeof(int) * 64, true);
+    if (!c->h_n_pad) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_n_pad), sizeof(int) * 64));
+    for (int b = 0; b < 64; ++b) c->h_n_pad[b] = b < B ? n_pad[b] : 0;
+    HIPCHK(c, hipMemcpyAsync(c->n_pad_tab, c->h_n_pad, sizeof(int) * 64, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(c, hipMemcpyAsync(c->seq, hseq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->cur_ids, first, sizeof(int) * B, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->finished, zeros, sizeof(int) * B, hipMemcpyHostToDevice, st));
@@ -1385,14 +1406,16 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     c->last_draft[3] = rounds;
     s_start = pos;
   }
-  sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = c->dx0; sa.d = c->d; sa.dtype = c->dtype;
-  HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
+  sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = ragged ? nullptr : c->dx0; sa.d = c->d; sa.dtype = c->dtype;
+  const int* pad_tab = ragged ? c->n_pad_tab : nullptr;
+  if (!ragged) HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  // (last field: the sampler flavour - greedy, biased greedy, sampling, filtered sampling: a graph of one is never replayed for a call of another)
+  // (last field: the sampler flavour - greedy, biased greedy, sampling, filtered sampling - or 'r', a ragged greedy call, whose steps are
+  //  other launches: a graph of one is never replayed for a call of another)
   snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, ragged ? 'r' : biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
   SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
   sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
   FilterArgs fla{};   // ... and every top-k / top-p
@@ -1426,7 +1449,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     int r = TW_OK;
     hipError_t es = hipSuccess;
     for (int i = 0; i < n && r == TW_OK && es == hipSuccess; ++i) {
-      r = decode_core(c, B, st, 0, nullptr, false);
+      r = decode_core(c, B, st, 0, nullptr, ragged, false, true, pad_tab);
       if (r == TW_OK) es = sample_step();
     }
     hipError_t ee = hipStreamEndCapture(st, &g);
@@ -1476,7 +1499,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       HIPCHK(c, hipGraphLaunch(ex, st));
     } else {
       c->dec_key_bound = kb;
-      int r = decode_core(c, B, st, 0, nullptr, false);
+      int r = decode_core(c, B, st, 0, nullptr, ragged, false, true, pad_tab);
       if (r != TW_OK) return r;
       HIPCHK(c, sample_step());
     }
@@ -1551,6 +1574,27 @@ int tw_generate_greedy_biased(tw_ctx* c, int32_t B, const int32_t* prompt, int32
   TW_ON_DEVICE(c);
   // nothing to add: the call IS tw_generate_greedy, launch for launch
   return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, (bo && bo->n_seq != 0) ? bo : nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_greedy_ragged(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const int32_t* n_pad,
+                              int32_t* out_ids, int32_t* out_len, void* stream) {
+  const char* fn = "tw_generate_greedy_ragged";
+  if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "%s: null argument", fn);
+  TW_ON_DEVICE(c);
+  bool padded = false;
+  if (B > 64) return fail(c, TW_EINVAL, "%s: %d streams (1..64)", fn, B);
+  if (n_pad) {
+    for (int b = 0; b < B; ++b) {
+      if (n_pad[b] < 0 || n_pad[b] >= n_prompt)   // (a row needs one real token)
+        return fail(c, TW_EINVAL, "%s: n_pad[%d] = %d outside [0, n_prompt = %d)", fn, b, n_pad[b], n_prompt);
+      padded |= n_pad[b] > 0;
+    }
+  }
+  // nothing padded: the call IS tw_generate_greedy, launch for launch
+  if (!padded) return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream);
+  if (o->n_forced != 0 || o->n_draft != 0)
+    return fail(c, TW_EINVAL, "%s: n_forced %d / n_draft %d: forced and draft tokens do not go with padded rows", fn, o->n_forced, o->n_draft);
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream, n_pad);
 }
 
 // tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter

@@ -108,7 +108,8 @@ __device__ __forceinline__ f32x4_t sk_mfma<float>(const u32x4_t& w, const u32x4_
 
 // Epilogue flavours (compile-time: a runtime-uniform branch around a load makes hipcc wait for EVERY outstanding load at
 // the join, which serialises the whole prologue - see the ordering note below).
-enum : int { SK_STORE = 0, SK_RES = 1, SK_GELU = 2, SK_KV = 3, SK_F32 = 4 };
+enum : int { SK_STORE = 0, SK_RES = 1, SK_GELU = 2, SK_KV = 3, SK_F32 = 4,
+             SK_KV_RAG = 5 };   // SK_KV of a ragged step (tw_common.h: tw_row_pos): the K / V^T scatter goes to the stream's ROW position
 
 template <typename T>
 __device__ __forceinline__ u32x4_t sk_load_w(const T* p) {  // weights are read exactly once per step: non-temporal
@@ -282,7 +283,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   // so the activation and weight requests leave without waiting for a scalar load; everything else (epilogue operands, outputs)
   // stays in the GemvArgs block behind them - a struct is never preloaded - and arrives while those requests are in flight.
   static_assert(!W8 || ElemTraits<T>::kCode == 1, "MXFP8 weights go with bf16 activations");
-  static_assert(TR == 16 || (!MULTI && EPI != SK_KV && EPI != SK_F32), "narrow tiles: plain / residual / GELU projections only");
+  static_assert(TR == 16 || (!MULTI && EPI != SK_KV && EPI != SK_KV_RAG && EPI != SK_F32), "narrow tiles: plain / residual / GELU projections only");
   static_assert(!W8 || TR == 16 || TR == 8, "MXFP8 weights: 16- or 8-row tiles");
   static_assert(!A16 || W8, "A16 is a flavour of the MXFP8-weight kernel");
   static_assert(!W8 || CG == 1 || A16, "several stream groups with MXFP8 weights: W8A16 only");
@@ -511,7 +512,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   // here, behind the operand requests that are already on their way
   asm volatile("" ::"s"(bias), "s"(res), "s"(gw_p), "s"(cb_p), "s"(a.gelu), "s"(ldy), "s"(d_model), "s"(cache_bstride), "s"(cache_hstride), "s"(y),
                "s"(y_f32), "s"(kcache), "s"(vcache), "s"(stt), "s"(u_p), "s"(nsplit), "s"(stats_p), "s"(rows_streams));
-  if (EPI == SK_KV) cur_pos = stt->pos;
+  if (EPI == SK_KV || EPI == SK_KV_RAG) cur_pos = stt->pos;
   load_epi(tile0, e_c, e_gw, e_res);
   __builtin_amdgcn_sched_barrier(0);  // ... nor hoist arithmetic between the requests
 
@@ -705,7 +706,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
         if (tile < n_tiles && n < N && jg < B && i < TR) {
           if (EPI == SK_F32) {
             y_f32[(long long)jg * N + n] = v;
-          } else if (EPI == SK_KV) {
+          } else if (EPI == SK_KV || EPI == SK_KV_RAG) {
             // 0: query -> y, 1: key -> K cache, 2: value -> V^T cache, 3: cross query ahead   (one predicated store; compares and a
             // host-side per-head stride instead of the 32- and 64-bit divisions by run-time values this epilogue used to carry: ~0.3 us)
             const int seg = (n >= d_model) + (n >= 2 * d_model) + (n >= 3 * d_model);
@@ -715,6 +716,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
             } else {
               int srow, prow;   // rows mode (prefill): row jg is stream jg % rs at position cur_pos + jg / rs
               tw_row_of(jg, rows_streams, cur_pos, srow, prow);
+              if (EPI == SK_KV_RAG) { srow = jg; prow = tw_row_pos(cur_pos, a.n_pad[jg]); }   // ragged step: row = stream (jg < B <= 64)
               const long long hb = (long long)srow * cache_bstride + (long long)hh * cache_hstride;  // (stream, head)
               T* dst = seg == 0 ? y + (long long)jg * ldy + n
                                 : (seg == 1 ? kcache + hb + tw_kf_index<T>(prow, cc) : vcache + hb + tw_vtf_index<T>(prow, cc));
@@ -1201,6 +1203,25 @@ __global__ __launch_bounds__(NW * 64) void dec_self_attn_kernel(const T* __restr
   // the host guarantees pos < key_bound (a multiple of 64, <= rows): the requests do not wait for `pos`
   attn_mfma_block<T, NW, SINGLE>(q + ((long long)b * H + h) * 64, kc + base, vc + base, n_keys, key_bound, sc, red,
                                 out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64);  // fragment-major, groups of 16 streams
+}
+
+// The same for a ragged step (tw_common.h: tw_row_pos): stream b sees the keys [0, q] of its ROW position q <= pos < key_bound, so the
+// requests cover them; the keys between q and the bucket's end are masked like the ones behind pos in the kernel above, and the
+// result does not depend on the bucket (attn_mfma_block: masked keys contribute exact zeros).  The table pointer stands behind the
+// leading arguments, which are the plain kernel's.
+template <typename T, bool SINGLE, int NW>
+__global__ __launch_bounds__(NW * 64) void dec_self_attn_ragged_kernel(const T* __restrict__ q, const T* __restrict__ kc,
+                                                                        const T* __restrict__ vc, int rows, int H, int key_bound,
+                                                                        T* __restrict__ out, const DecState* __restrict__ stt,
+                                                                        const int* __restrict__ n_pad) {
+  __shared__ float sc[512];
+  __shared__ float red[2 * 4 + 4 * 64];
+  asm volatile("" ::"s"(q), "s"(kc), "s"(vc), "s"(rows), "s"(H), "s"(key_bound));
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int n_keys = tw_row_pos(stt->pos, n_pad[b]) + 1;
+  const long long base = ((long long)b * H + h) * rows * 64;
+  attn_mfma_block<T, NW, SINGLE>(q + ((long long)b * H + h) * 64, kc + base, vc + base, n_keys, key_bound, sc, red,
+                                out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64);
 }
 
 template <typename T, bool SINGLE, bool FQ>
@@ -2147,7 +2168,12 @@ static hipError_t sk_go(const GemvArgs& a, dim3 grid, size_t lds1, hipStream_t s
     SK_GO(true, SK_F32);
   } else if (a.kcache) {
     if (!ln || a.res || a.gelu) return hipErrorInvalidValue;
-    SK_GO(true, SK_KV);
+    if (a.n_pad) {   // ragged step: an instantiation of its own, the plain call's launch is untouched
+      if (a.rows_streams != 0) return hipErrorInvalidValue;
+      SK_GO(true, SK_KV_RAG);
+    } else {
+      SK_GO(true, SK_KV);
+    }
   } else if (a.gelu) {
     if (!ln || a.res) return hipErrorInvalidValue;
     SK_GO(true, SK_GELU);
@@ -2311,6 +2337,23 @@ hipError_t launch_dec_self_attn(int dtype, const void* q, const void* kc, const 
   const int nw = kb <= 64 ? 1 : (kb <= 128 ? 2 : 4);
 #define SA_GO(TT, SV, NWV) hipLaunchKernelGGL((dec_self_attn_kernel<TT, SV, NWV>), dim3(H, B), dim3(NWV * 64), 0, st, (const TT*)q, \
                                               (const TT*)kc, (const TT*)vc, rows, H, kb, (TT*)out, stt, rows_streams)
+#define SA_PICK(TT) do { if (nw == 1) SA_GO(TT, true, 1); else if (nw == 2) SA_GO(TT, true, 2); else if (single) SA_GO(TT, true, 4); \
+                         else SA_GO(TT, false, 4); } while (0)
+  if (dtype == 1) SA_PICK(bf16_t); else if (dtype == 2) SA_PICK(f16_t); else SA_PICK(float);
+#undef SA_PICK
+#undef SA_GO
+  return hipGetLastError();
+}
+
+hipError_t launch_dec_self_attn_ragged(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H,
+                                       int key_bound, const DecState* stt, const int* n_pad, hipStream_t st) {
+  // the bucket is the plain launch's, picked from the ABSOLUTE position: a row position is never behind it
+  int kb = (key_bound + 63) / 64 * 64;
+  if (rows % 64 != 0 || rows > 512 || kb > rows || !n_pad || B < 1 || B > 64) return hipErrorInvalidValue;
+  const bool single = kb <= 256;
+  const int nw = kb <= 64 ? 1 : (kb <= 128 ? 2 : 4);
+#define SA_GO(TT, SV, NWV) hipLaunchKernelGGL((dec_self_attn_ragged_kernel<TT, SV, NWV>), dim3(H, B), dim3(NWV * 64), 0, st, (const TT*)q, \
+                                              (const TT*)kc, (const TT*)vc, rows, H, kb, (TT*)out, stt, n_pad)
 #define SA_PICK(TT) do { if (nw == 1) SA_GO(TT, true, 1); else if (nw == 2) SA_GO(TT, true, 2); else if (single) SA_GO(TT, true, 4); \
                          else SA_GO(TT, false, 4); } while (0)
   if (dtype == 1) SA_PICK(bf16_t); else if (dtype == 2) SA_PICK(f16_t); else SA_PICK(float);

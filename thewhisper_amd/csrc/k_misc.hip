@@ -171,6 +171,18 @@ __global__ void embed_kernel(const int* __restrict__ ids, const DecState* __rest
     x[(long long)(b >> 4) * 16 * d + tw_xt_index<T>(b & 15, i)] = (T)((float)tok[(long long)id * d + i] + (float)pos[(long long)p * d + i]);
 }
 
+// Ragged prompts (tw_generate_greedy_ragged; the rule is in include/thewhisper.h): stream b takes the positional row of its ROW
+// position (tw_row_pos), not of the step's absolute position.  One launch at the head of every ragged step: the sampler of such a
+// call writes no next input row (SamplerArgs::x_next = null), it knows absolute positions only.
+template <typename T>
+__global__ void embed_ragged_kernel(const int* __restrict__ ids, const DecState* __restrict__ stt, const int* __restrict__ n_pad,
+                                    const T* __restrict__ tok, const T* __restrict__ pos, T* __restrict__ x, int d) {
+  const int b = blockIdx.x;
+  const int id = ids[b];
+  const int q = tw_row_pos(stt->pos, n_pad[b]);
+  for (int i = threadIdx.x; i < d; i += blockDim.x)
+    x[(long long)(b >> 4) * 16 * d + tw_xt_index<T>(b & 15, i)] = (T)((float)tok[(long long)id * d + i] + (float)pos[(long long)q * d + i]);
+}
 
 }  // namespace
 
@@ -231,5 +243,12 @@ hipError_t launch_interp_positions(int dd, int sd, const void* src, void* dst, i
 hipError_t launch_embed(int dtype, const int* ids, const DecState* stt, const void* tok, const void* pos, void* x,
                         int B, int d, int rows_streams, hipStream_t st) {
   TW_DISPATCH3(dtype, T, hipLaunchKernelGGL(embed_kernel<T>, dim3(B), dim3(256), 0, st, ids, stt, (const T*)tok, (const T*)pos, (T*)x, B, d, rows_streams));
+  return hipGetLastError();
+}
+
+hipError_t launch_embed_ragged(int dtype, const int* ids, const DecState* stt, const int* n_pad, const void* tok, const void* pos,
+                               void* x, int B, int d, hipStream_t st) {
+  if (!n_pad || B < 1 || B > 64) return hipErrorInvalidValue;
+  TW_DISPATCH3(dtype, T, hipLaunchKernelGGL(embed_ragged_kernel<T>, dim3(B), dim3(256), 0, st, ids, stt, n_pad, (const T*)tok, (const T*)pos, (T*)x, d));
   return hipGetLastError();
 }

@@ -261,6 +261,15 @@ __device__ __forceinline__ void tw_row_of(int r, int rs, int pos, int& stream, i
 // x[b] = tok_emb[ids[b]] + pos_emb[pos]   (rows mode: pos_emb[pos + b / rows_streams])
 hipError_t launch_embed(int dtype, const int* ids, const DecState* stt, const void* tok, const void* pos, void* x,
                         int B, int d, int rows_streams, hipStream_t st);
+// Ragged prompts (tw_generate_greedy_ragged; THE RULE is in include/thewhisper.h): the first n_pad[b] prompt entries of stream b are
+// padding, and the stream at absolute position p is at ROW position q = p - n_pad[b] - its positional row, its self-attention cache slot
+// and its key range [0, q] - or idles at row position 0 while p < n_pad[b].  n_pad: int32 [64] in context-owned device memory.  Only
+// the three kernels that read a stream's own position take the table, each as an instantiation of its own (embed_ragged_kernel, the
+// RAG flavours of skinny_mfma_kernel's SK_KV epilogue and of dec_self_attn_kernel): the launches of every other call are as before.
+__device__ __forceinline__ int tw_row_pos(int p, int n_pad) { return p > n_pad ? p - n_pad : 0; }
+// x[b] = tok_emb[ids[b]] + pos_emb[tw_row_pos(pos, n_pad[b])]   (ordinary step only)
+hipError_t launch_embed_ragged(int dtype, const int* ids, const DecState* stt, const int* n_pad, const void* tok, const void* pos,
+                               void* x, int B, int d, hipStream_t st);
 // y[b, n] = epi( LN?(x[b,:]) . W[n,:] + bias[n] )  for b < B <= 16.
 struct GemvArgs {
   const void* x; int ldx;        // [16, K] input (T), fragment-major (tw_xt_index); ldx unused
@@ -289,6 +298,8 @@ struct GemvArgs {
   //    the consumer of u applies the folded LayerNorm with them.
   float* u; int nsplit; float* stats;
   int rows_streams;  // rows mode (tw_row_of): > 0 = number of streams the B rows cycle through; only the K / V^T scatter uses it
+  const int* n_pad;  // ragged prompts (tw_row_pos), QKV launch of an ordinary step only: non-null selects the RAG instantiation, whose K / V^T
+                     // scatter goes to the stream's ROW position.  Last member: every other member keeps its offset in the argument block
 };
 hipError_t launch_gemv(int dtype, const GemvArgs& a, hipStream_t st);
 // row-major [N][K] -> the fragment-major layout launch_gemv reads (k_decode.hip); dst holds ceil(N/16)*16 rows
@@ -303,6 +314,9 @@ hipError_t launch_fold_ln(int dtype, void* W, const void* Wsrc, const void* g, c
 // key_bound: host-known upper bound of pos+1 for this call; <= 256 selects the single-round-trip kernel
 hipError_t launch_dec_self_attn(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H,
                                 int key_bound, const DecState* stt, int rows_streams, hipStream_t st);
+// ragged prompts (ordinary step only): stream b sees the keys [0, tw_row_pos(pos, n_pad[b])]; key_bound bounds the ABSOLUTE position
+hipError_t launch_dec_self_attn_ragged(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H,
+                                       int key_bound, const DecState* stt, const int* n_pad, hipStream_t st);
 // cross attention over cached encoder K/V: ck/cv per (stream, head) Tp keys fragment-major; out fragment-major; align rows:
 // for head h with align_slot[h] >= 0 write the softmax row to align[((b*Ha + slot)*P + pos)*T + t]
 // ksc / vsc non-null: ck / cv are the fp8 caches above (bf16 contexts only), these their per-key scale bytes [B][H][Tp]

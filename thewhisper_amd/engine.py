@@ -99,6 +99,36 @@ def merge_sequence_bias(first, second) -> Dict[Tuple[int, ...], float]:
     return out
 
 
+def pack_ragged_prompts(prompts, pad_id: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Prompts of different lengths (a list of 1-D id sequences, none empty) as one LEFT-padded batch, the way HF batches Whisper's
+    previous-text prompts: ``(prompt int32 [B, n], n_pad int32 [B])`` with n = the longest length and ``prompt[b, n_pad[b]:]`` = row b."""
+    rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+    if not rows or any(r.size == 0 for r in rows):
+        raise ValueError("pack_ragged_prompts: at least one prompt, and every prompt needs one token")
+    n = max(r.size for r in rows)
+    out = np.full((len(rows), n), int(pad_id), dtype=np.int32)
+    n_pad = np.zeros(len(rows), dtype=np.int32)
+    for b, r in enumerate(rows):
+        n_pad[b] = n - r.size
+        out[b, n - r.size:] = r
+    return out, n_pad
+
+
+def ragged_n_pad(n_pad, B: int, n_forced: int = 0, n_draft: int = 0, biased: bool = False) -> Optional[np.ndarray]:
+    """``generate_greedy``'s ``n_pad`` as the library's int32 [B] (None when nothing was given).  Padding does not go with forced
+    tokens, drafts or a sequence bias; the values themselves are the library's to check (tw_generate_greedy_ragged: 0 <= n_pad < n_prompt)."""
+    if n_pad is None:
+        return None
+    arr = np.asarray(n_pad)
+    if arr.ndim != 1 or arr.size != B or arr.dtype.kind not in "iu":
+        raise ValueError(f"n_pad must be one integer per row ({B}), got {n_pad!r}")
+    if int(n_forced) or int(n_draft) or biased:
+        raise ValueError("n_pad does not go together with n_forced, n_draft or sequence_bias / sequence_bias_rows")
+    if (np.abs(arr.astype(np.int64)) > 2 ** 31 - 1).any():
+        raise ValueError(f"n_pad does not fit int32: {n_pad!r}")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
 class WhisperEngine:
     """One MI355X context: weights + workspace + KV arenas for up to ``max_batch`` concurrent streams
     of ``T`` encoder frames (= 50 x chunk seconds)."""
@@ -436,8 +466,12 @@ class WhisperEngine:
         n_draft: int = 0,
         sequence_bias=None,
         sequence_bias_rows=None,
+        n_pad=None,
     ) -> Dict[str, np.ndarray]:
-        """``sequence_bias``: HF's ``sequence_bias`` (list or dict form) for every row; ``sequence_bias_rows``: one such list per row
+        """``n_pad``: one integer per row - the first ``n_pad[b]`` entries of prompt row b are LEFT padding (tw_generate_greedy_ragged, where
+        the rule is stated: the row is decoded as if alone with its real tokens; the returned rows keep their padding).  Not together
+        with ``n_forced``, ``n_draft`` or a sequence bias.
+        ``sequence_bias``: HF's ``sequence_bias`` (list or dict form) for every row; ``sequence_bias_rows``: one such list per row
         (None for a row without one) - not both.  The rule is tw_generate_greedy_biased's (include/thewhisper.h): HF's
         ``SequenceBiasLogitsProcessor`` ahead of Whisper's processors, per row, honoured under ``n_forced`` and ``n_draft``.
         ``n_forced``: the last ``n_forced`` tokens of every prompt row are forced OUTPUT tokens (they count as generated; a
@@ -446,6 +480,7 @@ class WhisperEngine:
         batched launches, the call returns what it returns without them; ``draft`` in the result says how many were confirmed."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         B, n0 = prompt.shape
+        pads = ragged_n_pad(n_pad, B, n_forced, n_draft, sequence_bias is not None or sequence_bias_rows is not None)
         if sequence_bias is not None and sequence_bias_rows is not None:
             raise ValueError("sequence_bias (every row) and sequence_bias_rows (per row): give one of the two")
         if sequence_bias is not None:
@@ -458,7 +493,12 @@ class WhisperEngine:
         # (calls with a forced prefix stay on the caller's stream: their batched prefill - launches of up to 64 rows - wants the whole
         #  chip; measured on the reuse path's short calls: 16.1 ms per tick there, 19.9 on the 160-CU stream)
         sp = self._loop_stream() if int(n_forced) == 0 and int(n_draft) == 0 else self._sp()
-        if packed is None:
+        if pads is not None:
+            rc = self.lib.tw_generate_greedy_ragged(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
+                                                    pads.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+            self._chk(rc, "tw_generate_greedy_ragged")
+        elif packed is None:
             rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
                                              out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
                                              sp)
@@ -479,6 +519,16 @@ class WhisperEngine:
             self._chk(self.lib.tw_last_draft(self.ctx, *[C.byref(x) for x in v]), "tw_last_draft")
             res["draft"] = {"offered": int(v[0].value), "accepted": int(v[1].value), "launches": int(v[2].value), "rounds": int(v[3].value)}
         return res
+
+    def generate_greedy_ragged(self, prompts, *, pad_id: int = 50257, **kw) -> Dict[str, np.ndarray]:
+        """``generate_greedy`` for prompts of different lengths (a list of 1-D id sequences), in ONE call: the rows are left-padded with
+        ``pad_id`` (``pack_ragged_prompts``) and decoded by the ragged rule - each as if it were alone.  ``sequences``: a list with one
+        int64 array per row, the row's prompt and what it generated WITHOUT the padding; ``n_pad``: int32 [B]; ``length``: the common
+        padded length.  Keywords as ``generate_greedy`` (``n_forced``, ``n_draft`` and a sequence bias are refused)."""
+        prompt, n_pad = pack_ragged_prompts(prompts, pad_id)
+        res = self.generate_greedy(prompt, pad_id=pad_id, n_pad=n_pad, **kw)
+        seq = res["sequences"]
+        return {"sequences": [seq[b, int(n_pad[b]):] for b in range(seq.shape[0])], "n_pad": n_pad, "length": res["length"]}
 
     # ---- temperature sampling ----------------------------------------------------------------
     def generate_sample(self, prompt: np.ndarray, temperature, seed, offset=None, *, max_new_tokens: int = 128, min_new_tokens: int = 0,

@@ -51,6 +51,25 @@ def _default_engine_factory(dims, T, max_batch, dtype, alignment_heads, device_i
     return WhisperEngine(dims, T, max_batch=max_batch, dtype=dtype, alignment_heads=alignment_heads, device=device_index)
 
 
+def decoder_mask_n_pad(mask, B: int, n_prompt: int) -> Optional[Tuple[int, ...]]:
+    """HF's ``decoder_attention_mask`` [B, n_prompt] of a generate call as the engine's per-row padding lengths.  All ones: None (nothing
+    is padded; HF's long-form ``condition_on_prev_tokens`` sets such a mask even at batch size 1).  Left padding - zeros, then ones, as
+    HF batches previous-text prompts - : the number of zeros per row.  Anything else (a zero behind a one, a row without a real
+    token, another shape) is a ``ValueError``: the engine has no rule for it."""
+    m = np.asarray(mask.detach().to("cpu").numpy() if isinstance(mask, torch.Tensor) else mask)
+    if m.shape != (B, n_prompt):
+        raise ValueError(f"decoder_attention_mask of shape {tuple(m.shape)} for decoder_input_ids of shape {(B, n_prompt)}")
+    on = m != 0
+    if on.all():
+        return None
+    n_pad = (~on).sum(axis=1)
+    if (on != (np.arange(n_prompt)[None, :] >= n_pad[:, None])).any():
+        raise ValueError("decoder_attention_mask: only left padding (zeros, then ones) is supported - a row has a zero behind a one")
+    if (n_pad >= n_prompt).any():
+        raise ValueError("decoder_attention_mask: a row without a real token")
+    return tuple(int(x) for x in n_pad)
+
+
 class _EngineGreedyMixin(GenerationMixin):
     """Replaces ``GenerationMixin.generate`` (-> ``_sample``, HF:generation/utils.py:2783-2946) for the one
     configuration Whisper transcription uses: greedy, num_beams=1, short-form segment in, token ids out."""
@@ -96,6 +115,19 @@ class _EngineGreedyMixin(GenerationMixin):
                 raise NotImplementedError("multiple eos_token_id values")
             eos = eos[0]
         pad = gc.pad_token_id if gc.pad_token_id is not None else eos
+        n_pad = None
+        if kwargs.get("decoder_attention_mask") is not None:
+            n_pad = decoder_mask_n_pad(kwargs["decoder_attention_mask"], B, n_prompt)
+        if n_pad is not None:
+            if not getattr(self, "ragged_decoder_prompts", False):
+                raise NotImplementedError(
+                    "a left-padded decoder_attention_mask is honoured only with model.ragged_decoder_prompts = True: the MI355X engine decodes "
+                    "a padded row as that row alone (HF's batch-1 result for it), NOT with HF's arithmetic for a padded batch, which keeps "
+                    "absolute positions so that a row's result depends on its batch-mates' prompt lengths")
+            if getattr(self, "score_sink", None) is not None:
+                raise ValueError("token scores (score_sink) and a padded decoder_attention_mask do not go together: re-scoring takes no padding")
+            if bias:
+                raise ValueError("sequence_bias and a padded decoder_attention_mask do not go together")
 
         eng.encode(inputs)
         eng.cross_kv(B)
@@ -105,6 +137,8 @@ class _EngineGreedyMixin(GenerationMixin):
                          pad_id=int(pad), want_alignment=want_align, **opts)
         if bias:
             greedy_kw["sequence_bias"] = bias
+        if n_pad is not None:
+            greedy_kw["n_pad"] = n_pad
         probe = getattr(self, "_plan_probe", None)
         if probe is not None:   # a call that is learning its short-form plan (shortform.py): what was the engine asked to do?
             probe.append({"prompt": prompt.copy(), "greedy": dict(greedy_kw),
@@ -133,7 +167,7 @@ class _EngineGreedyMixin(GenerationMixin):
             bad.append("custom stopping_criteria")
         if prefix_allowed_tokens_fn is not None:
             bad.append("prefix_allowed_tokens_fn")
-        for k in ("assistant_model", "encoder_outputs", "decoder_attention_mask", "streamer", "past_key_values"):
+        for k in ("assistant_model", "encoder_outputs", "streamer", "past_key_values"):   # (decoder_attention_mask: decoder_mask_n_pad)
             if kwargs.get(k) is not None:
                 bad.append(k)
         if getattr(gc, "repetition_penalty", None) not in (None, 1.0):
@@ -269,6 +303,10 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
     #: opt-in (streaming.py, token_scores): {"entries": list, "no_speech_id": id or None} - every greedy call made while it is set
     #: appends its token scores (shortform.score_entries) to ``entries``; None = nothing is scored
     score_sink: Optional[Dict[str, Any]] = None
+    #: opt-in: honour a LEFT-PADDED ``decoder_attention_mask`` (rows with prompts of different lengths in one generate call) by the ragged
+    #: rule of tw_generate_greedy_ragged - every row is decoded as if it were alone, which is HF's batch-1 result for it and NOT HF's
+    #: result for the padded batch (HF keeps absolute positions there; DESIGN.md, "Ragged decoder prompts").  An all-ones mask needs no opt-in.
+    ragged_decoder_prompts: bool = False
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
@@ -352,6 +390,8 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         if not recs:
             return None
         g0, p0 = recs[0]["greedy"], recs[0]["prompt"][0]
+        if any("n_pad" in r["greedy"] for r in recs):
+            return None   # padded rows: the plan tiles ONE prompt over the batch
         for r in recs:   # every inner call of the seek loop must have been the same request, every row the same prompt
             if r["greedy"] != g0 or r["dict"] != recs[0]["dict"] or r["prompt"].shape[1] != len(p0) or (r["prompt"] != p0[None]).any():
                 return None

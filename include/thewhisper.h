@@ -115,7 +115,13 @@ typedef struct tw_greedy_opts {
                                     and the logits processors of every row; the draft is accepted up to the first position where
                                     some stream's arg-max differs from its guess, that arg-max becomes the token there, the rest of
                                     the draft is offered again behind it, and the one-token-per-step loop takes over where nothing
-                                    more is confirmed.  Sound because a row's result does not depend on the other rows of its launch
+                                    more is confirmed.  A draft holds no <eos> (TW_EINVAL), so a stream whose arg-max is <eos> always
+                                    ends its round; whatever stands behind that position in ANY stream's draft is then dropped - no
+                                    further round is offered once a stream has finished - and the one-token loop goes on from there:
+                                    the finished stream receives pad_id, the others are decoded step by step, out_len is set by the last
+                                    <eos> as in the plain call.  Guesses that run on behind a stream's end (a previous tick that was
+                                    longer than this one) therefore cost time, never a token.
+                                    Sound because a row's result does not depend on the other rows of its launch
                                     (one reduction order for every launch width, k_decode.hip).  Begin index = n_prompt - n_draft.
                                     Not together with n_forced.  0 = off.  tw_last_draft reports what was accepted. */
 } tw_greedy_opts;

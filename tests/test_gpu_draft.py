@@ -7,6 +7,9 @@
 * tw_greedy_opts::n_draft (draft-and-verify, SURVEY.md 8f-3): whatever is offered as a draft - the true continuation, a corrupted
   one, rubbish - the call returns what it returns without it: ids against the oracle's `greedy_generate` (strict f32) and ids,
   alignment rows and token timestamps against the engine's own plain call (every dtype), with the expected number of confirmed tokens;
+* the same with drafts that run on BEHIND a stream's <eos> while other streams go on (`test_draft_past_eos_*`, on tests/eos_model.py, a
+  micro model with decoder layers whose rows end at different steps and some never): the finished row is padded, the length is set by
+  the last <eos>, and every case first shows on the engine's own plain call that its rows end where the case needs them to;
 * `AMDWhisperBackend(draft_previous_tick=True)` on the reference scheduler's call sequence: every call's words identical to the
   plain backend's."""
 import numpy as np
@@ -14,6 +17,7 @@ import pytest
 import torch
 
 from oracle import whisper_oracle as wo
+from tests import eos_model as em
 from tests.util import PROMPT, clips, dims_variant, make_engine
 
 pytestmark = pytest.mark.gpu
@@ -281,10 +285,15 @@ def test_config3_trace_at_the_real_width_draft_ids_equal_plain_ids(dtype, layers
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16", "f16", "fp8a16", "fp8a8"])
 def test_draft_fuzz_random_drafts_never_change_the_result(dtype):
-    """Property test of `n_draft` on the micro model: 60 random situations per dtype - 1 ... 16 streams, 6 ... 90 new tokens, fixed or
-    free length (<eos> allowed early), timestamp grammar on or off, a suppress list or none, drafts of random length whose tokens are
-    corrupted at a random rate (0 = the true continuation ... 1 = rubbish, sometimes in one stream only) - and in every one of them the
-    call returns the plain call's ids, length, alignment rows and token timestamps; graph replay on and off."""
+    """Property test of `n_draft`, graph replay on and off, on two micro models.
+    make_weights(micro, 0): 60 random situations per dtype - 1 ... 16 streams, 6 ... 90 new tokens, <eos> masked up to the full length or
+    not (no row of this model emits <eos> within 90 tokens either way, so both are fixed-length runs and the draft stops short of nothing),
+    timestamp grammar on or off, a suppress list or none, drafts of random length whose tokens are corrupted at a random rate (0 = the
+    true continuation ... 1 = rubbish, sometimes in one stream only).
+    tests/eos_model.py (rows end at different steps, some never): 40 more - 1 ... 16 of its clips, 16 ... 40 new tokens, free length, a
+    setting of its table; the draft's length is drawn up to the LONGEST row's end (max_new - 2 where a row never ends), with filler that
+    is not <eos> behind each shorter row's end, corrupted as above.  At least 10 of them have a row ending inside the drafted span.
+    In every situation the call returns the plain call's ids, length, alignment rows and token timestamps."""
     dims = wo.PRESETS["micro"]
     w = wo.make_weights(dims, 0)
     heads = [(1, 0), (1, 1)]
@@ -335,6 +344,51 @@ def test_draft_fuzz_random_drafts_never_change_the_result(dtype):
     finally:
         for e in engines.values():
             e.close()
+    # ---- the model whose rows end: the draft runs past them ----
+    n_engaged, n_past = _fuzz_past_eos(dtype)
+    print(f"\nfuzz {dtype}, rows that end: {n_engaged} situations, {n_past} with a row ending inside the drafted span")
+    assert n_engaged >= 40 and n_past >= 10, (n_engaged, n_past)
+
+
+def _fuzz_past_eos(dtype):
+    engines = {(es, g): make_engine(*em.model(es), T=em.T, max_batch=16, dtype=dtype, heads=em.HEADS, use_graph=g)
+               for es in sorted({es for es, _ in em.SETTINGS}) for g in (True, False)}
+    n_engaged = n_past = 0
+    try:
+        pcm = em.audio(range(16))
+        rng = np.random.default_rng(em.FUZZ_EOS_SEED[dtype] + 1000)          # filler and corruption: these draws may depend on results
+        for case, sit in enumerate(em.fuzz_eos_situations(dtype)):
+            eng = engines[(sit["es"], sit["graph"])]
+            sel, B, max_new = list(sit["sel"]), len(sit["sel"]), sit["max_new"]
+            eng.encode(eng.logmel(torch.from_numpy(pcm[sel]).cuda(), out_dtype=torch.float32)); eng.cross_kv(B)
+            kw = em.engine_kw(sit["timestamps"], max_new)
+            prompt = em.prompt(sel)
+            full = eng.generate_greedy(prompt, **kw)
+            L, seq = full["length"], full["sequences"]
+            nf = [2 * em.T] * B
+            al = eng.get_alignment(B, L - 1)
+            ts = eng.token_timestamps(B, em.N_PROMPT, L, nf)
+            gen = np.concatenate([seq[:, em.N_PROMPT:], np.full((B, max_new), em.EOS)], axis=1)[:, :max_new]
+            steps = em.eos_steps(gen)
+            nd, past = em.fuzz_eos_draft_length(steps, max_new, sit["u"])
+            if nd < 1:
+                continue
+            draft = em.filled_draft(gen, nd, rng, repeat_last=sit["repeat"])
+            for b in (range(B) if not sit["one_row"] else [int(rng.integers(0, B))]):
+                for j in range(nd):
+                    if rng.random() < sit["rate"]:
+                        draft[b, j] = int(rng.integers(0, em.EOS))
+            out = eng.generate_greedy(np.concatenate([prompt, draft], axis=1), n_draft=nd, **kw)
+            what = f"{dtype} case {case}: {sit} rows end after {steps} nd={nd}"
+            assert out["length"] == L and np.array_equal(out["sequences"], seq), (what, out["draft"])
+            assert np.array_equal(eng.get_alignment(B, L - 1), al), what
+            assert np.array_equal(eng.token_timestamps(B, em.N_PROMPT, L, nf), ts), what
+            n_engaged += 1
+            n_past += int(past)
+    finally:
+        for e in engines.values():
+            e.close()
+    return n_engaged, n_past
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
@@ -372,3 +426,174 @@ def test_batch_composition_fuzz_at_the_real_width(dtype):
                 assert np.array_equal(lg[slot], alone[c][1][0]), f"{dtype}: clip {c} in slot {slot} of a {B}-clip pass: logits differ"
     finally:
         eng.close()
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# drafts that run past a stream's <eos> (tests/eos_model.py: a micro model with decoder layers whose rows end at different steps)
+# --------------------------------------------------------------------------------------------------------------------
+def _past_eos_variants(gen, max_new, rng):
+    """name -> draft [B, n] (one length for all rows, no <eos>), from the plain call's generated tokens `gen`:
+      (a)  every row's true continuation up to the LONGEST row's <eos> step (max_new - 2 where a row never ends), filler - random
+           text ids - behind each shorter row's end; (a') the same with the row's own last tokens repeated as filler;
+      (b)  (a) with one token of the longest row corrupted BEFORE any row's <eos>: retry rounds are running when the short row ends;
+      (c)  (a) with one token of the longest row corrupted BEHIND the short rows' ends;
+      (d)  right for every row up to the earliest <eos> step, rubbish behind it in all rows."""
+    steps = em.eos_steps(gen)
+    n = em.draft_span(gen, max_new)
+    first = min(s for s in steps if s is not None)
+    long_row = int(np.argmax([max_new if s is None else s for s in steps]))
+    long_end = n if steps[long_row] is None else min(n, steps[long_row])
+    a = em.filled_draft(gen, n, rng)
+    out = {"(a) true continuations, random filler": a, "(a') true continuations, own last tokens repeated": em.filled_draft(gen, n, rng, repeat_last=True)}
+    if len(steps) > 1:
+        assert 1 <= first < long_end - 1, (steps, n)
+        out["(b) one token wrong before the first <eos>"] = em.corrupt(a, long_row, first // 2)
+        out["(c) one token wrong behind the short rows' ends"] = em.corrupt(a, long_row, long_end - 1)
+    d = a.copy()
+    d[:, first:] = rng.integers(0, em.EOS, size=d[:, first:].shape)
+    out["(d) right up to the first <eos>, rubbish behind"] = d
+    return out
+
+
+def _drafts_past_eos(eng, b, what, strict_f32, bias=False):
+    """One batch of tests/eos_model.py on `eng`: the plain call, its premise (which rows end where - asserted on the ENGINE's result),
+    then every draft variant and a second plain call: length, ids (pad included), alignment rows and token timestamps are the plain
+    call's.  Returns {variant: tw_last_draft figures}."""
+    B = len(b.sel)
+    pcm = em.audio(b.sel)
+    prompt = em.prompt(b.sel)
+    kw = em.engine_kw(b.timestamps)
+    mel = eng.logmel(torch.from_numpy(pcm).cuda(), out_dtype=torch.float32)
+    eng.encode(mel); eng.cross_kv(B)
+    if bias:            # the list is derived from the UNBIASED run; the reference is the biased plain call
+        kw["sequence_bias_rows"] = em.bias_rows(eng.generate_greedy(prompt, **kw)["sequences"][:, em.N_PROMPT:], b.es, b.timestamps)
+    full = eng.generate_greedy(prompt, **kw)
+    L, seq = full["length"], full["sequences"]
+    nf = [2 * em.T] * B
+    al = eng.get_alignment(B, L - 1)
+    ts = eng.token_timestamps(B, em.N_PROMPT, L, nf)
+    gen = seq[:, em.N_PROMPT:]
+    steps = em.eos_steps(gen)
+    print(f"\n{what}: rows end after {['-' if s is None else s for s in steps]} tokens, length {L}")
+    em.check_batch(b, steps)
+    longest = max(em.MAX_NEW if s is None else s + 1 for s in steps)
+    assert L == em.N_PROMPT + min(em.MAX_NEW, longest), (what, "the length is set by the last <eos>", L, steps)
+    for r, s in zip(gen, steps):
+        assert s is None or (r[s:] == em.EOS).all(), (what, "a finished row is not padded")
+    if strict_f32:
+        if bias:
+            from tests import bias_judge as bj
+            dims, w = em.model(b.es)
+            om = wo.OracleWhisper(dims, w, T=em.T)
+            ref = bj.biased_greedy(om, om.encode(wo.log_mel(pcm, dims.n_mels)), prompt, em.options(b.timestamps), kw["sequence_bias_rows"])["sequences"]
+            assert em.eos_steps(ref[:, em.N_PROMPT:]) == [em.BIAS_CASE[(b.es, b.timestamps)][1], None], what
+        else:
+            ref = em.oracle_run(b.es, b.timestamps, b.sel)
+            assert steps == b.steps(), what
+        assert np.array_equal(seq, ref), what
+    figures = {}
+    drafts = _past_eos_variants(gen, em.MAX_NEW, np.random.default_rng(11))
+    for name, draft in drafts.items():
+        out = eng.generate_greedy(np.concatenate([prompt, draft], axis=1), n_draft=draft.shape[1], **kw)
+        w_ = f"{what}: draft = {name} ({draft.shape[1]} tokens)"
+        dr = out["draft"]
+        print(f"  {name}: {dr}")
+        assert out["length"] == L, (w_, out["length"], L, dr)
+        assert np.array_equal(out["sequences"], seq), (w_, dr, [(r, out["sequences"][r].tolist(), seq[r].tolist()) for r in range(B) if not np.array_equal(out["sequences"][r], seq[r])][:2])
+        assert np.array_equal(eng.get_alignment(B, L - 1), al), w_
+        assert np.array_equal(eng.token_timestamps(B, em.N_PROMPT, L, nf), ts), w_
+        assert dr["offered"] == draft.shape[1] * B and dr["launches"] >= 1 and dr["rounds"] >= 1, (w_, dr)
+        figures[name] = dr
+    assert figures, what
+    again = eng.generate_greedy(prompt, **kw)
+    assert again["length"] == L and np.array_equal(again["sequences"], seq), what
+    assert np.array_equal(eng.get_alignment(B, L - 1), al) and np.array_equal(eng.token_timestamps(B, em.N_PROMPT, L, nf), ts), what
+    return figures
+
+
+def _eos_engines(settings, B, dtype, graph):
+    """One engine per <eos> scale among `settings` (the model differs), closed by the caller."""
+    return {es: make_engine(*em.model(es), T=em.T, max_batch=B, dtype=dtype, heads=em.HEADS, use_graph=graph) for es in sorted({es for es, _ in settings})}
+
+
+def _run_past_eos(prefix, B, dtype, graph, settings=None, **kw):
+    settings = em.SETTINGS if settings is None else settings
+    engines = _eos_engines(settings, B, dtype, graph)
+    try:
+        for es, ts_on in settings:
+            b = em.batch(f"{prefix}-es{es}-ts{int(ts_on)}") if prefix != "b5" else em.batch("b5-all-end")
+            _drafts_past_eos(engines[es], b, f"{b.name} {dtype} graph={graph}", strict_f32=(dtype == "f32"), **kw)
+    finally:
+        for e in engines.values():
+            e.close()
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_draft_past_eos_two_rows_one_ends_one_never(graph):
+    """The smallest shape in which a draft is pending while a row reaches <eos>: clips 5 and 2 - row 0 ends after 6, 12 or 18 tokens,
+    row 1 never - in strict f32 (plain ids = the oracle's).  Whatever stands behind row 0's end in its draft, the call returns the plain
+    call's length, ids with row 0 padded, alignment rows and token timestamps."""
+    _run_past_eos("b2", 2, "f32", graph)
+
+
+def test_draft_past_eos_every_row_ends_at_another_step():
+    """Clips 0, 1, 3, 4, 5 at <eos> scale 2.5: every row ends, each at another step, so the call's length is set by the last <eos>
+    (17 tokens), not by max_new_tokens - with a draft as without."""
+    _run_past_eos("b5", 5, "f32", True, settings=[(2.5, True)])
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16", "fp8a16", "fp8a8"])
+def test_draft_past_eos_sixteen_rows_in_every_dtype(dtype):
+    """Clips 0 .. 15 (fp8a8's cap of 16 rows: one position per verify launch).  The reference is the engine's own plain call in that
+    type, and the premise - at least two different end steps, the earliest not before 3 tokens, some row that never ends - is
+    asserted on it."""
+    _run_past_eos("b16", 16, dtype, True)
+
+
+def test_draft_past_eos_twenty_rows():
+    """More than one group of 16 rows, three positions per first-round launch (bf16, the engine's own plain call as reference)."""
+    _run_past_eos("b20", 20, "bf16", True)
+
+
+def test_draft_past_eos_with_a_sequence_bias():
+    """tw_generate_greedy_biased promises the same under n_draft: one short sequence on the row that ends, none on the other (strict
+    f32; the biased plain call is the reference and equals the numpy statement of the rule, where the row ends after 32, 9 and 23 tokens)."""
+    _run_past_eos("b2", 2, "f32", True, bias=True)
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_draft_past_eos_one_row_ends_inside_the_verify_rounds(graph):
+    """(e) B = 1: the true continuation followed by 1, 5 and 20 filler tokens behind the row's <eos> step - the call ends inside the
+    verify rounds.  Every token before <eos> is confirmed, by at least one round."""
+    engines = _eos_engines(em.SETTINGS, 1, "f32", graph)
+    try:
+        for es, ts_on in em.SETTINGS:
+            b = em.batch(f"b1-es{es}-ts{int(ts_on)}")
+            eng = engines[es]
+            kw = em.engine_kw(ts_on)
+            prompt = em.prompt(b.sel)
+            eng.encode(eng.logmel(torch.from_numpy(em.audio(b.sel)).cuda(), out_dtype=torch.float32)); eng.cross_kv(1)
+            full = eng.generate_greedy(prompt, **kw)
+            L, seq = full["length"], full["sequences"]
+            assert np.array_equal(seq, em.oracle_run(es, ts_on, b.sel))
+            s = em.eos_steps(seq[:, em.N_PROMPT:])[0]
+            print(f"\n{b.name} graph={graph}: the row ends after {s} tokens, length {L}")
+            assert s == b.steps()[0] and s >= 3 and L == em.N_PROMPT + s + 1
+            al, ts = eng.get_alignment(1, L - 1), eng.token_timestamps(1, em.N_PROMPT, L, [2 * em.T])
+            rng = np.random.default_rng(13)
+            for k in (1, 5, 20):
+                for repeat in (False, True):
+                    draft = em.filled_draft(np.concatenate([seq[:, em.N_PROMPT:], np.full((1, 20), em.EOS)], axis=1), s + k, rng, repeat_last=repeat)
+                    out = eng.generate_greedy(np.concatenate([prompt, draft], axis=1), n_draft=s + k, **kw)
+                    what = f"{b.name} graph={graph}: {k} filler tokens behind <eos>, repeat={repeat}"
+                    dr = out["draft"]
+                    print(f"  {k} filler tokens (repeat={repeat}): {dr}")
+                    assert out["length"] == L and np.array_equal(out["sequences"], seq), (what, dr)
+                    assert np.array_equal(eng.get_alignment(1, L - 1), al), what
+                    assert np.array_equal(eng.token_timestamps(1, em.N_PROMPT, L, [2 * em.T]), ts), what
+                    assert dr["offered"] == s + k and dr["accepted"] == s and dr["rounds"] >= 1, (what, dr)
+            again = eng.generate_greedy(prompt, **kw)
+            assert again["length"] == L and np.array_equal(again["sequences"], seq)
+    finally:
+        for e in engines.values():
+            e.close()

@@ -136,3 +136,55 @@ def test_forced_and_draft_calls_are_judged_ok_and_equal_the_plain_call(graph):
             assert v2.judged == v.judged and v2.count("ok") + v2.count("undecided") == v2.judged
     finally:
         eng.close()
+
+
+@pytest.mark.parametrize("pad", ["eos", 5])
+def test_drafts_behind_a_finished_row_are_judged_ok_and_equal_the_plain_call(pad):
+    """tw_greedy_opts::n_draft with drafts that run past a row's <eos>, on case v127-b6: by the oracle (tests/test_eos_model.py) rows 1, 3
+    and 4 end after 9 tokens and rows 0, 2 and 5 never.  Every row's true continuation up to max_new - 2 with filler that is not <eos>
+    behind the finished rows' ends, and the same with one token of a row that goes on corrupted behind those ends: the plain call's
+    sequences, no step judged wrong, and in rows 1, 3 and 4 it is the padding rule that decides steps (the arg-max there is not pad).
+    pad = 5: this model answers <eos> with <eos>, so with pad_id = eos_id (the case as it stands) a call that decoded a finished row on
+    would return the same ids; with another pad_id it does not."""
+    import dataclasses
+
+    from tests import eos_model as em
+    built = sj.build_case(sj.case_by_name("v127-b6"))
+    c = built.case
+    pad = c.eos if pad == "eos" else int(pad)
+    kw = dict(built.kw, pad_id=pad)
+    opt = dataclasses.replace(built.opt, pad=pad)
+    eng = _engine(built)
+    try:
+        plain = eng.generate_greedy(built.prompt, **kw)["sequences"]
+        lg = _replay(eng, plain)
+        v = sj.judge(lg, plain, N_PROMPT, opt)
+        _check_verdict(built, v, f"plain v127-b6 pad={pad}")
+        gen = plain[:, N_PROMPT:]
+        steps = em.eos_steps(gen, c.eos)
+        print(f"v127-b6: rows end after {['-' if s is None else s for s in steps]} tokens")
+        assert steps == [None, 9, None, 9, 9, None], steps
+        for b in (1, 3, 4):
+            assert (gen[b, 10:] == pad).all()
+        padded = {b for _, b in v.decisive["pad_after_eos"]}
+        assert {1, 3, 4} <= padded, ("pad_after_eos never decisive in a finished row", sorted(padded))
+        n = em.draft_span(gen, c.max_new, c.eos)
+        assert n == c.max_new - 2
+        a = em.filled_draft(gen, n, np.random.default_rng(17), eos=c.eos)
+        calls = {"(a) true continuations, filler behind the finished rows": a,
+                 "(c) one token of row 0 wrong behind the finished rows' ends": em.corrupt(a, 0, 9 + (n - 9) // 2, c.eos)}
+        for what, draft in calls.items():
+            out = eng.generate_greedy(np.concatenate([built.prompt, draft], axis=1).astype(np.int32), n_draft=n, **kw)
+            print(f"  {what}: {out['draft']}")
+            assert out["draft"]["offered"] == n * c.B and out["draft"]["rounds"] >= 1
+            lg2 = _replay(eng, out["sequences"])           # judged on its own before it is compared: a token behind <eos> is `wrong`
+            v2 = sj.judge(lg2, out["sequences"], N_PROMPT, opt)
+            _check_verdict(built, v2, what)
+            assert np.array_equal(out["sequences"], plain), (what, out["draft"])
+            assert np.array_equal(lg2, lg), what
+            assert v2.judged == v.judged and v2.count("ok") + v2.count("undecided") == v2.judged
+            assert {1, 3, 4} <= {b for _, b in v2.decisive["pad_after_eos"]}, what
+        again = eng.generate_greedy(built.prompt, **kw)["sequences"]
+        assert np.array_equal(again, plain)
+    finally:
+        eng.close()

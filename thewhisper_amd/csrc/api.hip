@@ -1378,7 +1378,12 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     //      last round stopped.  Round 1 takes everything that was offered (prompt included: its positions have to be processed anyway);
     //      after a rejection the REST of the draft is offered again at the same positions (a changed timestamp or word usually leaves
     //      the text behind it as it was), in launches of one group of rows - such a launch costs about what one step costs and
-    //      yields at least the one token a step yields - until a round confirms nothing or the draft is used up. ----
+    //      yields at least the one token a step yields - until a round confirms nothing or the draft is used up.
+    //      The rounds also end as soon as ANY stream's token at `pos` is <eos>: rows mode has no finished rows (sampler_mask samples
+    //      every row, sampler_rows_finish_kernel rewrites every finished flag), so another round would feed that <eos> as an input
+    //      and decode the stream on.  At this exit the device state is the loop's - finished[] is set for exactly the streams
+    //      that hold <eos> at `pos`, since no earlier round ended on one - and the ordinary loop pads those rows from here;
+    //      the other streams' remaining guesses are dropped. ----
     constexpr int first_rows = 64, retry_rows = 16, max_rounds = 16;   // rows of round 1 / of a retry launch, rounds per call
     const int cap = std::min((c->w8 && !c->a16) ? 16 : 64, c->row_cap);   // W8A8 quantises activations per group of 16 rows: one group per launch
     if (B > cap) return fail(c, TW_EINVAL, "n_draft: %d streams exceed the %d rows of a launch", B, cap);
@@ -1400,8 +1405,13 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       c->last_draft[1] += std::max(0, confirmed) * B;
       pos = pn;
       draft_all_done = true;
-      for (int b = 0; b < B; ++b) draft_all_done &= pos >= n_begin && hseq[(size_t)b * P + pos] == o->eos_id;
-      if (draft_all_done || pos > p_end - 1 || pos >= max_len - 1 || rounds >= max_rounds || (rounds > 1 && confirmed <= 0)) break;
+      bool any_done = false;
+      for (int b = 0; b < B; ++b) {
+        const bool done = pos >= n_begin && hseq[(size_t)b * P + pos] == o->eos_id;
+        draft_all_done &= done;
+        any_done |= done;
+      }
+      if (any_done || pos > p_end - 1 || pos >= max_len - 1 || rounds >= max_rounds || (rounds > 1 && confirmed <= 0)) break;
     }
     c->last_draft[3] = rounds;
     s_start = pos;
@@ -1533,7 +1543,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   // common sequence length exactly as HF's loop would have stopped: when the last row hit eos, or at max_len
   const int produced = s_start + steps + 1;  // positions 0 .. s_start + steps are filled
   // first position a SAMPLED token sits at (forced / confirmed draft tokens before it are never <eos>; unconfirmed draft tokens
-  // behind `produced` are stale and never looked at)
+  // behind `produced` are stale and never looked at).  The draft rounds end at the first <eos> of ANY stream, so a stream's <eos>
+  // sits at s_start or behind it, never in front
   const int scan_from = n_draft > 0 ? std::max(s_start, n_begin) : n_prompt;
   int L = scan_from + 1;
   for (int b = 0; b < B; ++b) {

@@ -249,6 +249,56 @@ typedef struct tw_bias_opts {
 int tw_generate_greedy_biased(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
                               const tw_bias_opts* bopts, int32_t* out_ids_host, int32_t* out_len_host, void* stream);
 
+/* tw_generate_greedy (or _biased) with a per-stream repetition penalty and a per-stream no-repeat n-gram size.  Replaces:
+ * RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor (HF:generation/logits_process.py), which HF's generate builds in the
+ * order sequence bias, repetition penalty, no-repeat n-gram (HF:generation/utils.py:1154-1183), all three ahead of Whisper's own
+ * processors (appended at :1293).  HF takes one value per generate call; here every row (stream) of the call has its own.
+ *
+ * THE RULE.  Row b consumes position p and produces the token at p + 1.  h = the row's ids at positions 0 .. p, n = p + 1 of them: prompt,
+ * forced tokens and draft tokens included, as HF's input_ids.  x = the row's float32 logits after the row's sequence bias, if it has one.
+ *   1. Penalty.  r = penalty[b], a finite float32 > 0; 1.0f = off.  S = { h[i] : penalty_ignore <= i < n } (penalty_ignore is HF's
+ *      prompt_ignore_length; 0 is what HF's generate uses).  For every DISTINCT id v of S
+ *          x'[v] = x[v] < 0 ? x[v] * r : x[v] / r
+ *      one float32 multiply or one correctly rounded float32 division (not a multiply by a reciprocal), from the ORIGINAL x[v]: an id
+ *      that occurs twice is penalised once (HF gathers the original score for every occurrence and scatters equal values).  +0, -0 and
+ *      -inf follow from the expression as written (+0 and -0 are divided; -inf stays -inf).
+ *   2. No-repeat n-gram.  N = no_repeat_ngram[b]; 0 = off.  Nothing happens while n < N.  Otherwise, for every i in 0 .. n - N with
+ *          h[i + j] == h[n - N + 1 + j]  for j = 0 .. N - 2
+ *      x'[h[i + N - 1]] = -inf.  The whole history is read (penalty_ignore does not apply); N == 1 bans every id of the history.
+ *      1 and 2 commute (-inf * r is -inf).
+ *   3. Everything else in the step reads x' and keeps its bits: the suppress lists, begin-suppress, the min_new_tokens <eos> mask, the
+ *      timestamp grammar, "the timestamp mass beats every text token", the lowest-id arg-max.  The sampler masks an id by treating its
+ *      logit as -inf, so a banned id IS a masked id, and a row in which everything is masked or banned returns id 0.
+ * A row with r == 1 and N == 0 produces the plain call's tokens bit for bit, whatever the other rows set; a row's result does not depend
+ * on its slot or on its batch-mates.  Rows still consuming their prompt and finished rows are left alone.
+ *
+ * ropts == NULL, or every row off: the call IS tw_generate_greedy (tw_generate_greedy_biased with bopts), launch for launch.  Otherwise a
+ * step issues one launch more (one workgroup per row, behind the bias launch and in front of the sampler; no atomics, no store whose
+ * value depends on the order of the threads), captured step graphs are kept apart from the other calls' (repeat alone and bias + repeat
+ * each have their own), n_forced and n_draft are honoured (the rows-mode launches of a draft's verification are processed the same way,
+ * so the result is the processed plain call's: same ids, same alignment rows), and tw_last_draft, tw_last_timings, want_alignment and
+ * tw_token_timestamps behave as after tw_generate_greedy.  The per-row table lives in context-owned device memory, allocated by the first
+ * call of a context that uses it (a sibling owns its own) and freed by tw_destroy.
+ *
+ * TW_EINVAL in addition to tw_generate_greedy(_biased)'s, all before any work is enqueued (the context stays usable): a penalty that is
+ * NaN, infinite or <= 0; N < 0 or N > target_positions; penalty_ignore < 0; B > 64.  tw_generate_sample*, tw_generate_greedy_ragged and
+ * tw_score_tokens take no repeat options. */
+typedef struct tw_repeat_opts {
+  const float*   penalty;          /* host [B]; 1.0f = off; NULL = off for every row */
+  const int32_t* no_repeat_ngram;  /* host [B]; 0 = off; NULL = off for every row */
+  int32_t        penalty_ignore;   /* HF's prompt_ignore_length; 0 = HF generate's */
+} tw_repeat_opts;
+int tw_generate_greedy_repeat(tw_ctx* ctx, int32_t B, const int32_t* prompt_host, int32_t n_prompt, const tw_greedy_opts* opts,
+                              const tw_bias_opts* bopts /* may be NULL */, const tw_repeat_opts* ropts,
+                              int32_t* out_ids_host, int32_t* out_len_host, void* stream);
+/* Parity access, context-free like tw_vad_energy: steps 1 and 2 of the rule above on caller-provided data.  Row r of logits_dev (device,
+ * float32 [rows, V], edited in place) is processed with the history hist_host[r * ld .. r * ld + n_hist_host[r]) and ropts->penalty[r],
+ * ropts->no_repeat_ngram[r].  The call returns after the stream has been synchronised.  TW_EINVAL: the refusals above (with
+ * target_positions = 512, the history one launch holds), rows outside 1 .. 64, ld > 512, n_hist outside [0, ld], a history id outside
+ * [0, V), a null pointer. */
+int tw_repeat_logits(int32_t device, float* logits_dev, int32_t V, int32_t rows, const int32_t* hist_host, int32_t ld,
+                     const int32_t* n_hist_host, const tw_repeat_opts* ropts, void* stream);
+
 /* tw_generate_greedy for rows whose prompts differ in length ("ragged prompts"): the batch is LEFT-padded to one length n_prompt, as HF
  * batches Whisper's previous-text prompts (HF:models/whisper/generation_whisper.py:1709-1772 pads decoder_input_ids on the left and passes
  * decoder_attention_mask = ids != pad), and n_pad_host[b] says how many leading entries of row b are padding.

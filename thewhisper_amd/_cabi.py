@@ -52,6 +52,10 @@ class tw_bias_opts(C.Structure):
                 ("tokens", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float))]
 
 
+class tw_repeat_opts(C.Structure):
+    _fields_ = [("penalty", C.POINTER(C.c_float)), ("no_repeat_ngram", C.POINTER(C.c_int32)), ("penalty_ignore", C.c_int32)]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -76,6 +80,10 @@ SYMBOLS = [
                                             C.POINTER(tw_bias_opts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_greedy_ragged", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_generate_greedy_repeat", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
+                                            C.POINTER(tw_bias_opts), C.POINTER(tw_repeat_opts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("tw_repeat_logits", C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                   C.POINTER(tw_repeat_opts), _P]),
     ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),

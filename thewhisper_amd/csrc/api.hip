@@ -109,6 +109,9 @@ struct tw_ctx {
   // tw_generate_greedy_biased: the packed table of the call's sequences (tw_common.h: SeqBiasArgs) and its pinned staging, both of
   // kSeqBiasTabWords words, allocated by the first biased call of the context
   int* bias_tab = nullptr; int* h_bias = nullptr;
+  // tw_generate_greedy_repeat: the per-stream table (tw_common.h: RepeatArgs) of kRepeatTabWords words and its pinned staging, allocated
+  // by the first call of the context that sets a penalty or an n-gram size
+  int* repeat_tab = nullptr; int* h_repeat = nullptr;
   // tw_generate_greedy_ragged: the per-stream padding lengths [64] the ragged kernels read (tw_common.h: tw_row_pos) and their pinned
   // staging, allocated by the first ragged call of the context
   int* n_pad_tab = nullptr; int* h_n_pad = nullptr;
@@ -267,6 +270,7 @@ int tw_destroy(tw_ctx* c) {
   if (c->h_verify) (void)hipHostFree(c->h_verify);
   if (c->h_score) (void)hipHostFree(c->h_score);
   if (c->h_bias) (void)hipHostFree(c->h_bias);
+  if (c->h_repeat) (void)hipHostFree(c->h_repeat);
   if (c->h_n_pad) (void)hipHostFree(c->h_n_pad);
   for (int i = 0; i < 5; ++i) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
@@ -1068,8 +1072,10 @@ int prefill_core(tw_ctx* c, int B, const int* tok, int ld, int n_pos, hipStream_
 // On return *p_next = p_acc + 1 and tok[.. + *p_next] holds those tokens.
 // *next_given = 1 when the tokens the round PRODUCED at *p_next are (for every stream) the guesses that stood there (p_next <= p_given).
 // ba != nullptr (tw_generate_greedy_biased): every launch's logits pass through launch_seq_bias before its sampler, rows mode.
+// ra != nullptr (tw_generate_greedy_repeat): ... and through launch_repeat, behind the bias.
 int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, int p_start, int p_end, int rows_cap, const SamplerArgs& sa0,
-                 hipStream_t st, int* p_next, int* n_launches, int p_given, int* next_given, const SeqBiasArgs* ba) {
+                 hipStream_t st, int* p_next, int* n_launches, int p_given, int* next_given, const SeqBiasArgs* ba,
+                 const RepeatArgs* ra) {
   const int n_pos = p_end - p_start + 1;
   if (n_pos < 1 || B > rows_cap) return fail(c, TW_EINVAL, "verify: bad round [%d, %d] for %d streams", p_start, p_end, B);
   if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "verify: %d positions x %d streams exceed the row table", n_pos, B);
@@ -1104,6 +1110,11 @@ int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, 
       SeqBiasArgs b = *ba;
       b.rows = l * B; b.rows_streams = B; b.row_pos0 = p0;
       HIPCHK(c, launch_seq_bias(b, st));
+    }
+    if (ra) {
+      RepeatArgs rp = *ra;
+      rp.rows = l * B; rp.rows_streams = B; rp.row_pos0 = p0;
+      HIPCHK(c, launch_repeat(rp, st));
     }
     HIPCHK(c, launch_sampler_rows(sa, st));
     HIPCHK(c, hipMemcpyAsync(hv, c->verify_state, sizeof(int) * (2 + B), hipMemcpyDeviceToHost, st));
@@ -1193,6 +1204,26 @@ int pack_seq_bias(tw_ctx* c, int B, const tw_bias_opts* bo, std::vector<int>& ta
   return TW_OK;
 }
 
+// Checks a tw_repeat_opts for `rows` rows (every TW_EINVAL of tw_generate_greedy_repeat; max_n: the largest n-gram size) and fills the
+// table repeat_kernel reads (tw_common.h: RepeatArgs).  *any = some row has an option on.  Host work only.
+int pack_repeat(tw_ctx* c, const char* fn, int rows, int max_n, const tw_repeat_opts* ro, int* tab, bool* any) {
+  if (rows < 1 || rows > 64) return fail(c, TW_EINVAL, "%s: %d rows (1..64)", fn, rows);
+  if (ro->penalty_ignore < 0) return fail(c, TW_EINVAL, "%s: penalty_ignore %d < 0", fn, ro->penalty_ignore);
+  *any = false;
+  for (int b = 0; b < 64; ++b) {
+    const float r = (b < rows && ro->penalty) ? ro->penalty[b] : 1.0f;
+    const int N = (b < rows && ro->no_repeat_ngram) ? ro->no_repeat_ngram[b] : 0;
+    if (!std::isfinite(r) || !(r > 0.f)) return fail(c, TW_EINVAL, "%s: the penalty of row %d is NaN, infinite or <= 0", fn, b);
+    if (N < 0 || N > max_n) return fail(c, TW_EINVAL, "%s: no_repeat_ngram[%d] = %d outside [0, %d]", fn, b, N, max_n);
+    memcpy(tab + b, &r, sizeof r);
+    tab[64 + b] = N;
+    *any |= r != 1.0f || N != 0;
+  }
+  tab[128] = ro->penalty_ignore;
+  for (int i = 129; i < kRepeatTabWords; ++i) tab[i] = 0;
+  return TW_OK;
+}
+
 int reset_state(tw_ctx* c, int n_prompt, hipStream_t st) {
   DecState s{0, n_prompt, 0, 0};
   memcpy(c->h_pinned + 576, &s, sizeof s);
@@ -1235,14 +1266,15 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
 // sampler is launch_sample; rows with temperature < 0 start finished.  fo != nullptr (validated by tw_generate_sample_filtered, which
 // hands it on only when some sampled row has a filter on): every step's sampler is launch_sample_filtered.  bo != nullptr
 // (tw_generate_greedy_biased, greedy only, n_seq > 0): launch_seq_bias runs in front of every sampler launch, rows mode included.
+// ro != nullptr (tw_generate_greedy_repeat, greedy only; dropped here when every row is off): launch_repeat runs behind it.
 // n_pad != nullptr (tw_generate_greedy_ragged, which validated it: plain greedy only, no forced / draft tokens, some row padded): every
 // step is a ragged step (decode_core) that embeds its own input, so the sampler writes no next input row.
 static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
                          const tw_filter_opts* fo, const tw_bias_opts* bo, int32_t* out_ids, int32_t* out_len, void* stream,
-                         const int32_t* n_pad = nullptr) {
-  const char* fn = n_pad ? "tw_generate_greedy_ragged" : bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
+                         const int32_t* n_pad = nullptr, const tw_repeat_opts* ro = nullptr) {
+  const char* fn = n_pad ? "tw_generate_greedy_ragged" : ro ? "tw_generate_greedy_repeat" : bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
   const bool ragged = n_pad != nullptr;
-  if (ragged && (so || fo || bo || o->n_forced != 0 || o->n_draft != 0)) return fail(c, TW_EINVAL, "%s: padding goes with the plain greedy call only", fn);
+  if (ragged && (so || fo || bo || ro || o->n_forced != 0 || o->n_draft != 0)) return fail(c, TW_EINVAL, "%s: padding goes with the plain greedy call only", fn);
   if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
   if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
@@ -1267,6 +1299,13 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   if (biased) {
     if (B > 64) return fail(c, TW_EINVAL, "%s: %d streams (1..64)", fn, B);
     int r = pack_seq_bias(c, B, bo, bias_tab);
+    if (r != TW_OK) return r;
+  }
+  int repeat_tab[kRepeatTabWords];   // the call's per-stream penalties and n-gram sizes (checked here; uploaded with the initial state)
+  bool repeat = false;
+  if (ro) {
+    if (so || fo) return fail(c, TW_EINVAL, "%s: repeat options go with the greedy call only", fn);
+    int r = pack_repeat(c, fn, B, c->P, ro, repeat_tab, &repeat);
     if (r != TW_OK) return r;
   }
   c->dec_key_bound = max_len;   // per step: the 64-key bucket of the position (below)
@@ -1323,6 +1362,12 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     memcpy(c->h_bias, bias_tab.data(), sizeof(int) * bias_tab.size());
     HIPCHK(c, hipMemcpyAsync(c->bias_tab, c->h_bias, sizeof(int) * bias_tab.size(), hipMemcpyHostToDevice, st));
   }
+  if (repeat) {   // the same for the repeat table
+    if (!c->repeat_tab) ALLOC(c, c->repeat_tab, sizeof(int) * kRepeatTabWords, true);
+    if (!c->h_repeat) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_repeat), sizeof(int) * kRepeatTabWords));
+    memcpy(c->h_repeat, repeat_tab, sizeof repeat_tab);
+    HIPCHK(c, hipMemcpyAsync(c->repeat_tab, c->h_repeat, sizeof repeat_tab, hipMemcpyHostToDevice, st));
+  }
   if (ragged) {   // the same for the padding lengths (the staging is not touched again before this call's stream synchronisation)
     if (!c->n_pad_tab) ALLOC(c, c->n_pad_tab, sizeof(int) * 64, true);
     if (!c->h_n_pad) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_n_pad), sizeof(int) * 64));
@@ -1369,6 +1414,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   sa.suppress_bits = c->suppress_bits; sa.partials = c->sampler_partials;
   SeqBiasArgs ba{};   // the table lives in context-owned device memory: one captured graph serves every list
   ba.logits = c->logits; ba.V = c->V; ba.rows = B; ba.seq = c->seq; ba.seq_ld = P; ba.finished = c->finished; ba.stt = c->stt; ba.tab = c->bias_tab;
+  RepeatArgs rpa{};   // ... and every penalty and n-gram size
+  rpa.logits = c->logits; rpa.V = c->V; rpa.rows = B; rpa.seq = c->seq; rpa.seq_ld = P; rpa.finished = c->finished; rpa.stt = c->stt; rpa.tab = c->repeat_tab;
   // the embedding of the token a step has chosen is written by the sampler's last launch (k_decode.hip: embed_row), so a step is
   // layers + logits + sampler; only the FIRST step of the call needs its input row from a launch of its own
   c->last_draft[0] = n_draft * B; c->last_draft[1] = c->last_draft[2] = c->last_draft[3] = 0;
@@ -1396,7 +1443,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       const int rows = rounds == 0 ? std::min(cap, std::max(first_rows, B)) : std::min(cap, std::max(retry_rows, 4 * B));
       const int pe = rounds == 0 ? p_end : std::min(p_end, pos + std::max(1, rows / B) - 1);
       int pn = 0, next_given = 0;
-      int r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, &c->last_draft[2], p_end, &next_given, biased ? &ba : nullptr);
+      int r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, &c->last_draft[2], p_end, &next_given, biased ? &ba : nullptr,
+                           repeat ? &rpa : nullptr);
       if (r != TW_OK) return r;
       ++rounds;
       // guesses this round confirmed: the given tokens at positions <= p_acc that were compared, and the token the round produced
@@ -1422,10 +1470,10 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  // (last field: the sampler flavour - greedy, biased greedy, sampling, filtered sampling - or 'r', a ragged greedy call, whose steps are
-  //  other launches: a graph of one is never replayed for a call of another)
+  // (last field: the sampler flavour - greedy, biased greedy, greedy with repeat options 'p', biased with repeat options 'q', sampling,
+  //  filtered sampling - or 'r', a ragged greedy call, whose steps are other launches: a graph of one is never replayed for a call of another)
   snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, ragged ? 'r' : biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, ragged ? 'r' : repeat ? (biased ? 'q' : 'p') : biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
   SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
   sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
   FilterArgs fla{};   // ... and every top-k / top-p
@@ -1433,6 +1481,10 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   auto sample_step = [&]() -> hipError_t {
     if (biased) {
       hipError_t e = launch_seq_bias(ba, st);
+      if (e != hipSuccess) return e;
+    }
+    if (repeat) {
+      hipError_t e = launch_repeat(rpa, st);
       if (e != hipSuccess) return e;
     }
     if (!so) return launch_sampler(sa, st);
@@ -1585,6 +1637,15 @@ int tw_generate_greedy_biased(tw_ctx* c, int32_t B, const int32_t* prompt, int32
   TW_ON_DEVICE(c);
   // nothing to add: the call IS tw_generate_greedy, launch for launch
   return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, (bo && bo->n_seq != 0) ? bo : nullptr, out_ids, out_len, stream);
+}
+
+int tw_generate_greedy_repeat(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_bias_opts* bo,
+                              const tw_repeat_opts* ro, int32_t* out_ids, int32_t* out_len, void* stream) {
+  if (!c || !prompt || !o || !out_ids || !out_len) return fail(c, TW_EINVAL, "tw_generate_greedy_repeat: null argument");
+  TW_ON_DEVICE(c);
+  if (ro && B > 64) return fail(c, TW_EINVAL, "tw_generate_greedy_repeat: %d streams (1..64)", B);
+  // ro == nullptr, or every row off (generate_loop finds out while it checks the values): the call IS tw_generate_greedy(_biased)
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, (bo && bo->n_seq != 0) ? bo : nullptr, out_ids, out_len, stream, nullptr, ro);
 }
 
 int tw_generate_greedy_ragged(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const int32_t* n_pad,
@@ -1865,6 +1926,45 @@ int tw_vad_energy(int32_t device, const float* pcm_dev, int64_t stream_stride, i
   DeviceGuard guard(device);
   hipError_t e = launch_vad_energy(pcm_dev, stream_stride, B, n_frames, state_dev, prob_dev, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) { g_create_error = std::string("vad_energy_kernel: ") + hipGetErrorString(e); return TW_EHIP; }
+  return TW_OK;
+}
+
+int tw_repeat_logits(int32_t device, float* logits_dev, int32_t V, int32_t rows, const int32_t* hist_host, int32_t ld,
+                     const int32_t* n_hist_host, const tw_repeat_opts* ro, void* stream) {
+  const char* fn = "tw_repeat_logits";
+  if (!logits_dev || !hist_host || !n_hist_host || !ro) return fail(nullptr, TW_EINVAL, "%s: null argument", fn);
+  if (V < 1 || ld < 0 || ld > kRepeatMaxHist) return fail(nullptr, TW_EINVAL, "%s: V = %d, ld = %d (ld at most %d)", fn, V, ld, kRepeatMaxHist);
+  // staging: history [rows][ld] | n_hist [rows] | table
+  std::vector<int> h;
+  bool any = false;
+  {
+    int tab[kRepeatTabWords];
+    int r = pack_repeat(nullptr, fn, rows, kRepeatMaxHist, ro, tab, &any);
+    if (r != TW_OK) return r;
+    h.resize((size_t)rows * ld + rows + kRepeatTabWords);
+    for (int i = 0; i < rows; ++i) {
+      const int n = n_hist_host[i];
+      if (n < 0 || n > ld) return fail(nullptr, TW_EINVAL, "%s: n_hist[%d] = %d outside [0, %d]", fn, i, n, ld);
+      for (int j = 0; j < ld; ++j) {
+        const int t = hist_host[(size_t)i * ld + j];
+        if (j < n && (t < 0 || t >= V)) return fail(nullptr, TW_EINVAL, "%s: history id %d of row %d outside [0, %d)", fn, t, i, V);
+        h[(size_t)i * ld + j] = j < n ? t : 0;
+      }
+      h[(size_t)rows * ld + i] = n;
+    }
+    memcpy(h.data() + (size_t)rows * ld + rows, tab, sizeof tab);
+  }
+  DeviceGuard guard(device);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int* dev = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), sizeof(int) * h.size());
+  if (e != hipSuccess) return fail(nullptr, TW_ENOMEM, "%s: hipMalloc failed: %s", fn, hipGetErrorString(e));
+  e = hipMemcpyAsync(dev, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_repeat_logits(logits_dev, V, rows, dev, ld, dev + (size_t)rows * ld, dev + (size_t)rows * ld + rows, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(nullptr, TW_EHIP, "%s: %s", fn, hipGetErrorString(e));
   return TW_OK;
 }
 

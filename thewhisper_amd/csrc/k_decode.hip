@@ -2137,6 +2137,77 @@ __global__ __launch_bounds__(256) void seq_bias_kernel(SeqBiasArgs a) {
   }
 }
 
+// Repetition penalty and no-repeat n-grams on one row (tw_generate_greedy_repeat, tw_repeat_logits; the rule is stated in
+// include/thewhisper.h), by one workgroup of kRepeatMaxHist threads: thread i owns history index i.  h: the row's n ids (n <=
+// kRepeatMaxHist, every id in [0, V)), hi = h[i] loaded by the caller for every i below the row's allocated length - the address
+// does not depend on n, so the load flies beside the loads n comes from; r: the penalty (1.0f = off); N: the n-gram size (0 = off);
+// sh: kRepeatMaxHist words of LDS.
+// Every argument but the thread index is uniform over the workgroup, so the barriers are reached by all of its threads.
+//   penalty: every thread of [ignore, n) loads the ORIGINAL logit of its id; behind a barrier the FIRST occurrence of an id in
+//            [ignore, n) - found by scanning the history in LDS, four ids per (broadcast) read - stores the penalised value: an id is
+//            penalised once, from its original value, and has one writer.  `/` is IEEE division (the build passes no fast-math flag;
+//            __fdiv_rn says so), not a multiply by a reciprocal.
+//   n-gram:  behind a second barrier (a banned id may also be a penalised one: -inf has to be the later store) thread i compares the
+//            window h[i .. i+N-2] with the suffix h[n-N+1 .. n-1] and stores -inf to h[i+N-1].  Several threads may ban one id: they
+//            store the same bits.
+// No atomics, and no store whose value depends on the order of the threads.
+__device__ __forceinline__ void repeat_row(float* lg, int hi, int n, float r, int N, int ignore, int* sh) {
+  const int i = threadIdx.x;
+  const int id = i < n ? hi : -1;
+  sh[i] = id;
+  const bool pen = r != 1.0f && i >= ignore && i < n;
+  float x = 0.f;
+  if (pen) x = lg[id];
+  __syncthreads();
+  if (pen) {
+    bool first = true;
+    const int4* sh4 = reinterpret_cast<const int4*>(sh);
+    for (int j = ignore & ~3; j < i; j += 4) {      // (ids in front of `ignore` and at or behind i do not count)
+      const int4 q = sh4[j >> 2];
+      first &= !((q.x == id && j >= ignore) || (q.y == id && j + 1 >= ignore && j + 1 < i) || (q.z == id && j + 2 >= ignore && j + 2 < i) ||
+                 (q.w == id && j + 3 >= ignore && j + 3 < i));
+    }
+    if (first) lg[id] = x < 0.f ? x * r : __fdiv_rn(x, r);
+  }
+  if (N < 1 || n < N) return;
+  __syncthreads();
+  if (i <= n - N) {
+    const int* suf = sh + (n - N + 1);
+    bool same = true;
+    for (int j = 0; j < N - 1; ++j) same &= sh[i + j] == suf[j];
+    if (same) lg[sh[i + N - 1]] = -INFINITY;
+  }
+}
+
+// tw_generate_greedy_repeat: one launch behind seq_bias_kernel (if the call has a bias) and in front of the step's sampler.  One
+// workgroup per row of the launch, rows as seq_bias_kernel derives them; rows still consuming their prompt and finished rows are left
+// alone, and so is a row whose table entry is off (penalty 1.0f, N 0): its logits keep their bits.
+__global__ __launch_bounds__(kRepeatMaxHist) void repeat_kernel(RepeatArgs a) {
+  __shared__ __attribute__((aligned(16))) int sh[kRepeatMaxHist];
+  const int r = blockIdx.x;
+  // (rows mode: r % rows_streams; the ordinary step: r - known before the position is)
+  const int stream = a.rows_streams > 0 ? r % a.rows_streams : r;
+  const int hi = (int)threadIdx.x < a.seq_ld ? a.seq[(long long)stream * a.seq_ld + threadIdx.x] : -1;
+  int stream_, p;
+  tw_row_of(r, a.rows_streams, a.rows_streams > 0 ? a.row_pos0 : a.stt->pos, stream_, p);
+  const float pen = __int_as_float(a.tab[stream]);
+  const int N = a.tab[64 + stream];
+  if (pen == 1.0f && N == 0) return;                      // a row with both options off
+  const int n = p + 1;                                    // ids of the history: positions 0 .. p
+  if (n < a.stt->n_prompt || n > a.seq_ld) return;        // still consuming its prompt: nothing is sampled
+  if (a.rows_streams == 0 && a.finished[r] != 0) return;  // finished: the row receives pad_id whatever the logits say
+  repeat_row(a.logits + (long long)r * a.V, hi, n, pen, N, a.tab[128], sh);
+}
+
+// tw_repeat_logits: the same rule, state from arguments (row r: its own history and its own table entry)
+__global__ __launch_bounds__(kRepeatMaxHist) void repeat_logits_kernel(float* logits, int V, const int* hist, int ld, const int* n_hist,
+                                                                       const int* tab) {
+  __shared__ __attribute__((aligned(16))) int sh[kRepeatMaxHist];
+  const int r = blockIdx.x;
+  const int hi = (int)threadIdx.x < ld ? hist[(long long)r * ld + threadIdx.x] : -1;
+  repeat_row(logits + (long long)r * V, hi, n_hist[r], __int_as_float(tab[r]), tab[64 + r], tab[128], sh);
+}
+
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
 }  // namespace
@@ -2481,6 +2552,20 @@ hipError_t launch_seq_bias(const SeqBiasArgs& a, hipStream_t st) {
       (a.rows_streams == 0 ? !a.finished : a.rows % a.rows_streams != 0))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(seq_bias_kernel, dim3(a.rows), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_repeat(const RepeatArgs& a, hipStream_t st) {
+  if (a.rows < 1 || a.rows > 64 || !a.logits || !a.seq || !a.stt || !a.tab || a.rows_streams < 0 || a.seq_ld > kRepeatMaxHist ||
+      (a.rows_streams == 0 ? !a.finished : a.rows % a.rows_streams != 0))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(repeat_kernel, dim3(a.rows), dim3(kRepeatMaxHist), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist, int ld, const int* n_hist, const int* tab, hipStream_t st) {
+  if (rows < 1 || rows > 64 || V < 1 || ld < 0 || !logits || !hist || !n_hist || !tab) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(repeat_logits_kernel, dim3(rows), dim3(kRepeatMaxHist), 0, st, logits, V, hist, ld, n_hist, tab);
   return hipGetLastError();
 }
 

@@ -446,6 +446,24 @@ struct SeqBiasArgs {
   const int* tab;
 };
 hipError_t launch_seq_bias(const SeqBiasArgs& a, hipStream_t st);
+// Repetition penalty and no-repeat n-grams (tw_generate_greedy_repeat; the rule is in include/thewhisper.h; k_decode.hip:
+// repeat_kernel): one launch behind launch_seq_bias and in front of launch_sampler / launch_sampler_rows that edits logits[row], in
+// place, from the row's history seq[stream][0 .. p].  `tab` is the per-stream table of the call in context-owned device memory (int32
+// words): tab[s] = the float32 penalty of stream s (its bits), tab[64 + s] = its N, tab[128] = penalty_ignore.  The pointer is the
+// same for every call of a context, so one captured step graph serves every setting.
+constexpr int kRepeatMaxHist = 512;     // history ids a row can hold (target_positions <= 511): one thread each
+constexpr int kRepeatTabWords = 192;    // penalty[64] | N[64] | ignore | padding
+struct RepeatArgs {
+  float* logits; int V; int rows;       // [rows][V]
+  const int* seq; int seq_ld;           // [streams][seq_ld] token history (SamplerArgs::seq)
+  const int* finished;                  // [streams] (ordinary step only)
+  const DecState* stt;
+  int rows_streams; int row_pos0;       // rows mode as SamplerArgs
+  const int* tab;
+};
+hipError_t launch_repeat(const RepeatArgs& a, hipStream_t st);
+// The same per-row rule on caller-provided data (tw_repeat_logits): row r reads hist[r * ld .. + n_hist[r]) and tab[r], tab[64 + r].
+hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist, int ld, const int* n_hist, const int* tab, hipStream_t st);
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st);     // pos += n only (teacher-forced stepping, prefill)
 
 // A11: alignment rows -> token timestamps

@@ -129,6 +129,36 @@ def ragged_n_pad(n_pad, B: int, n_forced: int = 0, n_draft: int = 0, biased: boo
     return np.ascontiguousarray(arr, dtype=np.int32)
 
 
+def repeat_rows(repetition_penalty, no_repeat_ngram_size, B: int):
+    """``repetition_penalty`` / ``no_repeat_ngram_size`` (None, a scalar for every row, or one value per row) as the arrays of
+    ``tw_repeat_opts``: float32 [B] (1.0 = off) and int32 [B] (0 = off).  None when every row has both off: the call is then the plain
+    one.  Values the library would refuse raise ``ValueError`` here."""
+    pen = np.ones(B, dtype=np.float32) if repetition_penalty is None else np.asarray(repetition_penalty, dtype=np.float32).reshape(-1)
+    ngr = np.zeros(B, dtype=np.int64) if no_repeat_ngram_size is None else np.asarray(no_repeat_ngram_size).reshape(-1)
+    if ngr.dtype.kind not in "iu":
+        raise ValueError(f"no_repeat_ngram_size must be integers, got {no_repeat_ngram_size!r}")
+    if pen.size not in (1, B) or ngr.size not in (1, B):
+        raise ValueError(f"repetition_penalty / no_repeat_ngram_size: one value or one per row ({B}), got {pen.size} / {ngr.size}")
+    pen = np.ascontiguousarray(np.broadcast_to(pen, (B,)), dtype=np.float32)
+    ngr = np.broadcast_to(ngr, (B,))
+    if not (np.isfinite(pen).all() and (pen > 0).all()):
+        raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty!r}")
+    if (ngr < 0).any() or (ngr > 2 ** 31 - 1).any():
+        raise ValueError(f"no_repeat_ngram_size must be >= 0, got {no_repeat_ngram_size!r}")
+    if (pen == 1.0).all() and (ngr == 0).all():
+        return None
+    return pen, np.ascontiguousarray(ngr, dtype=np.int32)
+
+
+def _repeat_opts(rows, penalty_ignore: int):
+    """``tw_repeat_opts`` over the arrays of ``repeat_rows`` (which the caller keeps alive)."""
+    ro = _cabi.tw_repeat_opts()
+    ro.penalty = rows[0].ctypes.data_as(C.POINTER(C.c_float))
+    ro.no_repeat_ngram = rows[1].ctypes.data_as(C.POINTER(C.c_int32))
+    ro.penalty_ignore = int(penalty_ignore)
+    return ro
+
+
 class WhisperEngine:
     """One MI355X context: weights + workspace + KV arenas for up to ``max_batch`` concurrent streams
     of ``T`` encoder frames (= 50 x chunk seconds)."""
@@ -467,8 +497,15 @@ class WhisperEngine:
         sequence_bias=None,
         sequence_bias_rows=None,
         n_pad=None,
+        repetition_penalty=None,
+        no_repeat_ngram_size=None,
+        penalty_ignore: int = 0,
     ) -> Dict[str, np.ndarray]:
-        """``n_pad``: one integer per row - the first ``n_pad[b]`` entries of prompt row b are LEFT padding (tw_generate_greedy_ragged, where
+        """``repetition_penalty`` / ``no_repeat_ngram_size``: HF's options of those names, a scalar for every row or one value per row
+        (1.0 / 0 = off); ``penalty_ignore``: HF's ``prompt_ignore_length`` of the penalty.  The rule is tw_generate_greedy_repeat's
+        (include/thewhisper.h): HF's two processors behind the sequence bias and ahead of Whisper's processors, per row, honoured under
+        ``n_forced`` and ``n_draft``.  Not together with ``n_pad``.
+        ``n_pad``: one integer per row - the first ``n_pad[b]`` entries of prompt row b are LEFT padding (tw_generate_greedy_ragged, where
         the rule is stated: the row is decoded as if alone with its real tokens; the returned rows keep their padding).  Not together
         with ``n_forced``, ``n_draft`` or a sequence bias.
         ``sequence_bias``: HF's ``sequence_bias`` (list or dict form) for every row; ``sequence_bias_rows``: one such list per row
@@ -486,6 +523,11 @@ class WhisperEngine:
         if sequence_bias is not None:
             sequence_bias_rows = [sequence_bias] * B
         packed = pack_sequence_bias(list(sequence_bias_rows), B) if sequence_bias_rows is not None else None
+        if int(penalty_ignore) < 0:
+            raise ValueError(f"penalty_ignore must be >= 0, got {penalty_ignore!r}")
+        repeat = repeat_rows(repetition_penalty, no_repeat_ngram_size, B)
+        if repeat is not None and pads is not None:
+            raise ValueError("n_pad does not go with repetition_penalty / no_repeat_ngram_size (the ragged call takes no repeat options)")
         o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
                                      min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
         out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
@@ -498,6 +540,18 @@ class WhisperEngine:
                                                     pads.ctypes.data_as(C.POINTER(C.c_int32)),
                                                     out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
             self._chk(rc, "tw_generate_greedy_ragged")
+        elif repeat is not None:
+            bo = None
+            if packed is not None:
+                bo = _cabi.tw_bias_opts()
+                bo.n_seq = int(packed["bias"].size)
+                bo.row_off, bo.seq_off, bo.tokens = (packed[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("row_off", "seq_off", "tokens"))
+                bo.bias = packed["bias"].ctypes.data_as(C.POINTER(C.c_float))
+            ro = _repeat_opts(repeat, penalty_ignore)
+            rc = self.lib.tw_generate_greedy_repeat(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
+                                                    C.byref(bo) if bo is not None else None, C.byref(ro),
+                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
+            self._chk(rc, "tw_generate_greedy_repeat")
         elif packed is None:
             rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
                                              out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
@@ -519,6 +573,30 @@ class WhisperEngine:
             self._chk(self.lib.tw_last_draft(self.ctx, *[C.byref(x) for x in v]), "tw_last_draft")
             res["draft"] = {"offered": int(v[0].value), "accepted": int(v[1].value), "launches": int(v[2].value), "rounds": int(v[3].value)}
         return res
+
+    def repeat_logits(self, logits: torch.Tensor, history, n_hist=None, *, repetition_penalty=None, no_repeat_ngram_size=None,
+                      penalty_ignore: int = 0) -> torch.Tensor:
+        """The repeat rule of tw_generate_greedy_repeat on caller-provided data (tw_repeat_logits): ``logits`` - a contiguous float32
+        ``[rows, V]`` tensor on this engine's device - is edited IN PLACE and returned; row r is processed with the ids
+        ``history[r, :n_hist[r]]`` (``history``: int ``[rows, ld]``; ``n_hist`` None = every row's whole ``ld``) and row r of the two
+        options (a scalar or one value per row)."""
+        if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous() or logits.device != torch.device(self.device):
+            raise ValueError("repeat_logits: logits must be a contiguous float32 [rows, V] tensor on the engine's device")
+        rows, V = int(logits.shape[0]), int(logits.shape[1])
+        hist = np.ascontiguousarray(history, dtype=np.int32).reshape(rows, -1)
+        ld = int(hist.shape[1])
+        nh = np.full(rows, ld, dtype=np.int32) if n_hist is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_hist, dtype=np.int32), (rows,)))
+        rr = repeat_rows(repetition_penalty, no_repeat_ngram_size, rows)
+        if rr is None:
+            rr = (np.ones(rows, dtype=np.float32), np.zeros(rows, dtype=np.int32))
+        ro = _repeat_opts(rr, penalty_ignore)
+        if hist.size == 0:
+            hist = np.zeros(1, dtype=np.int32)   # (a valid pointer for ld == 0)
+        rc = self.lib.tw_repeat_logits(int(torch.device(self.device).index or 0), C.c_void_p(logits.data_ptr()), V, rows,
+                                       hist.ctypes.data_as(C.POINTER(C.c_int32)), ld, nh.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ro),
+                                       self._sp())
+        _cabi.check(self.lib, None, rc, "tw_repeat_logits")     # (context-free: the message is the library's, not the context's)
+        return logits
 
     def generate_greedy_ragged(self, prompts, *, pad_id: int = 50257, **kw) -> Dict[str, np.ndarray]:
         """``generate_greedy`` for prompts of different lengths (a list of 1-D id sequences), in ONE call: the rows are left-padded with

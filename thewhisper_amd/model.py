@@ -24,6 +24,8 @@ import numpy as np
 import torch
 from transformers import WhisperConfig, WhisperForConditionalGeneration
 from transformers.generation.logits_process import (
+    NoRepeatNGramLogitsProcessor,
+    RepetitionPenaltyLogitsProcessor,
     SequenceBiasLogitsProcessor,
     SuppressTokensAtBeginLogitsProcessor,
     SuppressTokensLogitsProcessor,
@@ -100,6 +102,7 @@ class _EngineGreedyMixin(GenerationMixin):
         n_prompt = int(decoder_input_ids.shape[1])
         opts = self._parse_logits_processors(logits_processor, n_prompt)
         bias = self._sequence_bias(gc, logits_processor)
+        repeat = self._repeat_options(gc, logits_processor)
         max_target = int(self.config.max_target_positions)
         if getattr(gc, "max_new_tokens", None) is not None:
             max_len = n_prompt + int(gc.max_new_tokens)
@@ -128,6 +131,11 @@ class _EngineGreedyMixin(GenerationMixin):
                 raise ValueError("token scores (score_sink) and a padded decoder_attention_mask do not go together: re-scoring takes no padding")
             if bias:
                 raise ValueError("sequence_bias and a padded decoder_attention_mask do not go together")
+            if repeat:
+                raise ValueError("repetition_penalty / no_repeat_ngram_size and a padded decoder_attention_mask do not go together")
+        if repeat and getattr(self, "score_sink", None) is not None:
+            raise ValueError("repetition_penalty / no_repeat_ngram_size and token scores (score_sink) do not go together: the re-scoring "
+                             "pass does not know the rule")
 
         eng.encode(inputs)
         eng.cross_kv(B)
@@ -137,6 +145,7 @@ class _EngineGreedyMixin(GenerationMixin):
                          pad_id=int(pad), want_alignment=want_align, **opts)
         if bias:
             greedy_kw["sequence_bias"] = bias
+        greedy_kw.update(repeat)
         if n_pad is not None:
             greedy_kw["n_pad"] = n_pad
         probe = getattr(self, "_plan_probe", None)
@@ -170,10 +179,7 @@ class _EngineGreedyMixin(GenerationMixin):
         for k in ("assistant_model", "encoder_outputs", "streamer", "past_key_values"):   # (decoder_attention_mask: decoder_mask_n_pad)
             if kwargs.get(k) is not None:
                 bad.append(k)
-        if getattr(gc, "repetition_penalty", None) not in (None, 1.0):
-            bad.append("repetition_penalty")
-        if getattr(gc, "no_repeat_ngram_size", None) not in (None, 0):
-            bad.append("no_repeat_ngram_size")
+        # (repetition_penalty, no_repeat_ngram_size: _repeat_options)
         if getattr(gc, "num_return_sequences", 1) not in (None, 1):
             bad.append("num_return_sequences > 1")
         if bad:
@@ -204,6 +210,47 @@ class _EngineGreedyMixin(GenerationMixin):
         return sequence_bias_dict(found[0]) if found else None
 
     @staticmethod
+    def _repeat_options(gc, processors) -> Dict[str, Any]:
+        """HF's ``repetition_penalty`` / ``no_repeat_ngram_size`` of the call as ``generate_greedy`` keywords (empty: both off): from the
+        generation config (HF builds the two processors behind the sequence bias and ahead of Whisper's, HF:generation/utils.py:1154-1183
+        - the order the engine applies) or from a ``RepetitionPenaltyLogitsProcessor`` / ``NoRepeatNGramLogitsProcessor`` in a custom
+        list, which must stand ahead of the ``WhisperTimeStampLogitsProcessor`` and not ahead of a ``SequenceBiasLogitsProcessor``."""
+        pen, ngr, ignore, seen_ts, seen_rep = [], [], 0, False, False
+        for p in processors or []:
+            if isinstance(p, WhisperTimeStampLogitsProcessor):
+                seen_ts = True
+            elif isinstance(p, SequenceBiasLogitsProcessor):
+                if seen_rep:
+                    raise NotImplementedError("a repetition-penalty / no-repeat-n-gram processor ahead of a SequenceBiasLogitsProcessor: the "
+                                              "MI355X engine applies the bias first, as HF's generate orders them")
+            elif isinstance(p, (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor)):
+                if seen_ts:
+                    raise NotImplementedError(f"a {type(p).__name__} behind the WhisperTimeStampLogitsProcessor: the MI355X engine applies "
+                                              "it ahead of Whisper's processors, as the generation config's option does")
+                seen_rep = True
+                if isinstance(p, RepetitionPenaltyLogitsProcessor):
+                    if getattr(p, "logits_indices", None) is not None:
+                        raise NotImplementedError("a RepetitionPenaltyLogitsProcessor with logits_indices")
+                    pen.append(float(p.penalty))
+                    ignore = int(getattr(p, "prompt_ignore_length", None) or 0)
+                else:
+                    ngr.append(int(p.ngram_size))
+        if getattr(gc, "repetition_penalty", None) not in (None, 1.0):
+            pen.append(float(gc.repetition_penalty))
+        if getattr(gc, "no_repeat_ngram_size", None) not in (None, 0):
+            ngr.append(int(gc.no_repeat_ngram_size))
+        if len(pen) > 1 or len(ngr) > 1:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size given twice (the generation config and / or several processors)")
+        out: Dict[str, Any] = {}
+        if pen and pen[0] != 1.0:
+            out["repetition_penalty"] = pen[0]
+            if ignore:
+                out["penalty_ignore"] = ignore
+        if ngr and ngr[0] != 0:
+            out["no_repeat_ngram_size"] = ngr[0]
+        return out
+
+    @staticmethod
     def _parse_logits_processors(processors, n_prompt: int) -> Dict[str, Any]:
         opts: Dict[str, Any] = dict(timestamps=False, begin_suppress=(), suppress=(), no_timestamps_id=0,
                                     max_initial_timestamp_index=None)
@@ -222,6 +269,8 @@ class _EngineGreedyMixin(GenerationMixin):
                 opts["max_initial_timestamp_index"] = p.max_initial_timestamp_index
             elif isinstance(p, SequenceBiasLogitsProcessor):
                 pass      # read by _sequence_bias
+            elif isinstance(p, (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor)):
+                pass      # read by _repeat_options
             else:
                 raise NotImplementedError(f"logits processor {type(p).__name__} is not implemented on the MI355X engine")
         return opts
@@ -310,7 +359,8 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
-                "max_new_tokens", "min_new_tokens", "max_length", "temperature", "return_dict_in_generate", "sequence_bias"}
+                "max_new_tokens", "min_new_tokens", "max_length", "temperature", "return_dict_in_generate", "sequence_bias", "repetition_penalty",
+                "no_repeat_ngram_size"}
     _GC_FIELDS = ("max_new_tokens", "max_length", "min_new_tokens", "min_length", "eos_token_id", "pad_token_id", "suppress_tokens",
                   "begin_suppress_tokens", "no_timestamps_token_id", "max_initial_timestamp_index", "return_timestamps", "task",
                   "language", "num_beams", "do_sample", "temperature", "no_speech_threshold", "logprob_threshold",

@@ -334,6 +334,9 @@ class Pass:
         if self.score and (plan.greedy.get("sequence_bias") or any(w.bias for w in works)):
             raise ValueError("a sequence bias and token scores do not go together (the re-scoring pass does not know the bias: its "
                              "log-probabilities would be those of the unbiased distribution)")
+        if self.score and (plan.greedy.get("repetition_penalty") or plan.greedy.get("no_repeat_ngram_size")):
+            raise ValueError("repetition_penalty / no_repeat_ngram_size and token scores do not go together (the re-scoring pass does not "
+                             "know the rule)")
         greedy_kw = self._greedy_kw()
         t0 = time.perf_counter()
         if n_forced:
@@ -383,6 +386,9 @@ class Pass:
         if plan.greedy.get("sequence_bias") or any(w.bias for w in works):
             raise ValueError("a sequence bias and the temperature fallback do not go together (the sampler and the re-scoring pass do not "
                              "know the bias)")
+        if plan.greedy.get("repetition_penalty") or plan.greedy.get("no_repeat_ngram_size"):
+            raise ValueError("repetition_penalty / no_repeat_ngram_size and the temperature fallback do not go together (the sampler and "
+                             "the re-scoring pass do not know the rule)")
         B, n_prompt = len(works), plan.n_prompt
         base = prompt[:, :n_prompt]
         row_ts: List[Optional[torch.Tensor]] = [None] * B

@@ -44,6 +44,8 @@ class AMDWhisperBackend:
         temperature_fallback=None,
         hotwords=None,
         hotword_boost: Optional[float] = None,
+        repetition_penalty: Optional[float] = None,
+        no_repeat_ngram_size: Optional[int] = None,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -92,7 +94,13 @@ class AMDWhisperBackend:
         the list between calls.  With hotwords set the call ALWAYS runs the restated short-form loop; a backend whose call is not
         eligible for it raises ``ValueError``.  ``draft_previous_tick`` stays on: the biased call returns the same ids whatever the
         draft.  Not together with ``temperature_fallback``, ``token_scores`` or ``reuse_committed_prefix``: the sampler and the
-        re-scoring pass do not know the bias."""
+        re-scoring pass do not know the bias.
+
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` (opt-in; HF's generate options of those names, off by default): every decode of
+        this backend applies them on the device (tw_generate_greedy_repeat, where the rule is stated: HF's two processors behind the
+        sequence bias and ahead of Whisper's own).  They travel as generate options, so they are part of the learned short-form plan.
+        ``draft_previous_tick`` stays on - the call returns the same ids whatever the draft - and hotwords go with them.  Not together
+        with ``temperature_fallback`` or ``token_scores``: the sampler and the re-scoring pass do not know the rule."""
         from .asr_pipeline import ASRPipeline
 
         if torch_dtype is None:
@@ -134,6 +142,22 @@ class AMDWhisperBackend:
             raise ValueError("temperature_fallback and reuse_committed_prefix do not go together (a forced token is not redrawn)")
         self.last_fallback: List[Dict[str, Any]] = []
         self._no_speech_id: Any = False           # not looked up yet
+        self.repetition_penalty: Optional[float] = None
+        self.no_repeat_ngram_size: Optional[int] = None
+        if repetition_penalty is not None:
+            r = float(repetition_penalty)
+            if not (r > 0.0 and r <= float(np.finfo(np.float32).max)):      # (NaN fails the comparison too)
+                raise ValueError(f"repetition_penalty must be a finite float > 0, got {repetition_penalty!r}")
+            self.repetition_penalty = r if r != 1.0 else None
+        if no_repeat_ngram_size is not None:
+            if isinstance(no_repeat_ngram_size, bool) or int(no_repeat_ngram_size) != no_repeat_ngram_size or int(no_repeat_ngram_size) < 0:
+                raise ValueError(f"no_repeat_ngram_size must be an integer >= 0, got {no_repeat_ngram_size!r}")
+            self.no_repeat_ngram_size = int(no_repeat_ngram_size) or None
+        if self.repetition_penalty is not None or self.no_repeat_ngram_size is not None:
+            for name in ("temperature_fallback", "token_scores"):
+                if getattr(self, name, None):
+                    raise ValueError(f"repetition_penalty / no_repeat_ngram_size and {name} do not go together (the sampler and the "
+                                     "re-scoring pass do not know the rule)")
         self.hotwords: List[str] = []
         self.hotword_boost: Optional[float] = None
         self._hotword_bias: Optional[Dict[Any, float]] = None     # what every chunk of a call carries (shortform.ChunkWork.bias)
@@ -174,7 +198,12 @@ class AMDWhisperBackend:
         return resample(audio, int(sample_rate), self.sample_rate, kernel=self._resample_kernel), self.sample_rate
 
     def _generate_kwargs(self) -> Dict[str, Any]:
-        return {"use_cache": True, "num_beams": 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
+        kw = {"use_cache": True, "num_beams": 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
+        if self.repetition_penalty is not None:
+            kw["repetition_penalty"] = self.repetition_penalty
+        if self.no_repeat_ngram_size is not None:
+            kw["no_repeat_ngram_size"] = self.no_repeat_ngram_size
+        return kw
 
     @property
     def no_speech_id(self) -> Optional[int]:

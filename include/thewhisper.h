@@ -84,7 +84,9 @@ typedef struct tw_config {
 
 /* Options of one greedy decode (A9/A10).  Mirrors what HF's generate derives from
  * generation_config + the three Whisper logits processors
- * (HF:models/whisper/generation_whisper.py:1774-1812, HF:generation/logits_process.py:1816-2047). */
+ * (HF:models/whisper/generation_whisper.py:1774-1812, HF:generation/logits_process.py:1816-2047).
+ * Every tw_generate_* call and tw_score_tokens check them alike and answer TW_EINVAL to: a list count that is negative or above its
+ * capacity (64 begin-suppress ids, 1024 suppress ids), a positive count with a NULL list, pad_id or eos_id outside the vocabulary. */
 typedef struct tw_greedy_opts {
   int32_t eos_id;
   int32_t pad_id;

@@ -878,6 +878,17 @@ def test_c_abi_error_behaviour():
         refused(lib.tw_generate_greedy(ctx, 2, None, 3, C.byref(o), op, C.byref(n), sp))
         refused(lib.tw_generate_greedy(ctx, 2, pp, 3, None, op, C.byref(n), sp))
         refused(lib.tw_generate_greedy(ctx, 2, pp, 3, C.byref(o), None, C.byref(n), sp))
+        # the processors' lists (tw_greedy_opts): a count without its list, a negative count - every member of the generate family
+        temp, seed = (C.c_float * 2)(0.5, 0.5), (C.c_uint64 * 2)(1, 2)
+        so = _cabi.tw_sample_opts(temperature=temp, seed=seed)
+        pen = (C.c_float * 2)(1.3, 1.3)
+        ro = _cabi.tw_repeat_opts(penalty=pen)
+        for field, bad in (("n_suppress", 3), ("n_begin_suppress", -1)):
+            setattr(o, field, bad)
+            refused(lib.tw_generate_greedy(ctx, 2, pp, 3, C.byref(o), op, C.byref(n), sp), (TW_EINVAL,))
+            refused(lib.tw_generate_sample(ctx, 2, pp, 3, C.byref(o), C.byref(so), op, C.byref(n), sp), (TW_EINVAL,))
+            refused(lib.tw_generate_greedy_repeat(ctx, 2, pp, 3, C.byref(o), None, C.byref(ro), op, C.byref(n), sp), (TW_EINVAL,))
+            setattr(o, field, 0)
         # word timestamps without recorded alignment rows
         ts = np.zeros((2, 8), np.float32)
         refused(lib.tw_token_timestamps(ctx, 2, 3, 8, None, 0.02, ts.ctypes.data_as(C.POINTER(C.c_float)), sp))

@@ -395,6 +395,8 @@ def test_argument_checks_leave_the_context_usable():
             "positions x streams above the row table": dict(seqs=long_seq),
             "begin-suppress list too long": dict(seqs=seqs, opts=opts(n_begin_suppress=65)),
             "suppress list too long": dict(seqs=seqs, opts=opts(n_suppress=1025)),
+            "suppress count without its list": dict(seqs=seqs, opts=opts(n_suppress=3, suppress=None)),
+            "negative begin-suppress count": dict(seqs=seqs, opts=opts(n_begin_suppress=-1)),
             "eos outside the vocabulary": dict(seqs=seqs, opts=opts(eos_id=V)), "pad outside the vocabulary": dict(seqs=seqs, opts=opts(pad_id=-1)),
             "no_speech_pos == seq_len - 1": dict(seqs=seqs, ns_id=NO_SPEECH, ns_pos=7), "no_speech_pos < 0": dict(seqs=seqs, ns_id=NO_SPEECH, ns_pos=-1),
             "no_speech_id >= vocab": dict(seqs=seqs, ns_id=V),

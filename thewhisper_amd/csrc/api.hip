@@ -38,6 +38,26 @@ struct LayerW {
   int tr_qkv = 16, tr_o = 16, tr_qc = 16, tr_oc = 16, tr_1 = 16, tr_2 = 16;
 };
 
+// ---- pinned host staging: every block has a type, and its fields are the only way in (tw_ctx::h_*; alloc_staging) ----
+struct PinnedScratch {       // h_pinned
+  int finished[8][64];       // ring of the generate loop's read-backs of the finished flags, one slot per launch
+  int n_valid[64];           // tw_logmel's valid-sample counts
+  DecState state;            // reset_state's upload
+};
+struct VerifyStage {         // h_verify: the device's verify_state (tw_common.h: SamplerArgs) as read back, and what a round resets it to
+  int first_mismatch, decided, choice[64];   // [0] | [1] = p_acc + 1 once the round is decided, else 0 | [2 + b] = stream b's token there
+  int reset[2];                              // the two leading words at the start of a round
+};
+struct GenStage {            // h_stage: the initial state of a tw_generate_* call; tw_score_tokens stages its suppress lists here too
+  int first[64], finished0[64], last_ts0[64];   // per stream: first input token | finished flag | last timestamp token
+  int bsup[64], sup[1024];                      // begin-suppress and suppress lists
+  DecState state;
+  float inv_t[64]; uint32_t key[64][2], off[64][2]; int noisy[64];   // tw_generate_sample
+  int top_k[64]; float top_p[64];                                    // tw_generate_sample_filtered
+};
+struct RowStage { int *tok, *lastts; };                  // h_rows: position-major tables of a rows-mode pass, [row_ids_cap] each (fill_row_tables)
+struct ScoreBlock { float *masked, *raw, *no_speech; };  // tw_score_tokens' results, device and pinned alike: [Bmax][P] | [Bmax][P] | [Bmax]
+
 }  // namespace
 
 struct tw_ctx {
@@ -98,14 +118,14 @@ struct tw_ctx {
   // tw_generate_sample_filtered: per-row top-k / top-p (uploaded per call) and the filter kernel's choice
   int* filter_top_k = nullptr; float* filter_top_p = nullptr; int* filter_choice = nullptr;   // [64] each
   unsigned* suppress_bits = nullptr;  // [(V+31)/32] static suppress list as a bitmap, rebuilt per generate call
-  int* h_pinned = nullptr;  // pinned host scratch: finished ring [8][64] | n_valid [64] | DecState upload [16]
+  PinnedScratch* h_pinned = nullptr;
   int* row_ids = nullptr;   // device token table of a prefill (position-major), row_ids_cap ints
-  int* h_rows = nullptr;    // its pinned host staging: [2][row_ids_cap] (token table | last-timestamp table of a verify round)
+  RowStage h_rows{};        // its pinned host staging, and that of row_lastts
   // draft-and-verify (tw_greedy_opts::n_draft): per-row sampler state and results (SamplerArgs, tw_common.h)
   int* row_lastts = nullptr;     // [row_ids_cap] position-major like row_ids
   int* row_choice = nullptr;     // [row_ids_cap]
   int* verify_state = nullptr;   // [2 + 64] device
-  int* h_verify = nullptr;       // pinned: [2 + 64] read back | [1] reset value
+  VerifyStage* h_verify = nullptr;
   // tw_generate_greedy_biased: the packed table of the call's sequences (tw_common.h: SeqBiasArgs) and its pinned staging, both of
   // kSeqBiasTabWords words, allocated by the first biased call of the context
   int* bias_tab = nullptr; int* h_bias = nullptr;
@@ -123,13 +143,10 @@ struct tw_ctx {
   int *score_bsup = nullptr, *score_sup = nullptr;   // [64], [1024]
   unsigned* score_bits = nullptr;      // [(V+31)/32]
   ScorePartial* score_parts = nullptr; // [64][32]
-  float* score_out = nullptr;          // masked [Bmax][P] | raw [Bmax][P] | no-speech [Bmax]
-  float* h_score = nullptr;            // pinned, the same layout
+  ScoreBlock score_out{}, h_score{}; size_t score_floats = 0;   // one block of score_floats floats each, on the device and pinned (masked = its start)
   int row_cap = 0;          // rows the per-token activation buffers hold (>= max_batch; 64 for the prefill launches)
-  int* h_stage = nullptr;   // pinned staging of tw_generate_greedy: token table [Bmax][P] (up and down) | 3 x [Bmax] | suppress lists | DecState
-                            // | tw_generate_sample: inv_t [64] | key [64][2] | off [64][2] | noisy [64]
-                            // | tw_generate_sample_filtered: top_k [64] | top_p [64]
-  size_t h_stage_ints = 0;
+  GenStage* h_stage = nullptr;
+  int* h_seq = nullptr;     // pinned token table [Bmax][P] of tw_generate_* (up and down) and tw_score_tokens (up)
   hipEvent_t ring_ev[8]{};
   int last_seq_len = 0, last_n_prompt = 0;
   int dec_key_bound = 0;  // upper bound of decoder positions for the current decode (prompt + max new tokens)
@@ -242,8 +259,20 @@ void build_mel_bank(int n_mels, std::vector<float>& bank, std::vector<int>& lo, 
     if (hi[m] == 0) lo[m] = 0;
 }
 
-int upload(tw_ctx* c, void* dst, const void* src, size_t bytes) {
-  HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+// Every pinned staging block of a context and tw_score_tokens' device results: the one place that knows a capacity or where a
+// part begins (needs Bmax, P and row_ids_cap).  Freed in tw_destroy.
+int alloc_staging(tw_ctx* c) {
+  const size_t plane = (size_t)c->Bmax * c->P;
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), sizeof(PinnedScratch), hipHostMallocDefault));
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_verify), sizeof(VerifyStage), hipHostMallocDefault));
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), sizeof(GenStage), hipHostMallocDefault));
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_seq), sizeof(int) * plane, hipHostMallocDefault));
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rows.tok), sizeof(int) * 2 * c->row_ids_cap, hipHostMallocDefault));
+  c->h_rows.lastts = c->h_rows.tok + c->row_ids_cap;
+  c->score_floats = 2 * plane + c->Bmax;
+  ALLOC(c, c->score_out.masked, sizeof(float) * c->score_floats, true);
+  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_score.masked), sizeof(float) * c->score_floats, hipHostMallocDefault));
+  for (ScoreBlock* s : {&c->score_out, &c->h_score}) { s->raw = s->masked + plane; s->no_speech = s->raw + plane; }
   return TW_OK;
 }
 
@@ -264,14 +293,9 @@ int tw_destroy(tw_ctx* c) {
   (void)hipDeviceSynchronize();
   for (auto& kv : c->step_graphs) (void)hipGraphExecDestroy(kv.second);
   for (void* p : c->allocs) (void)hipFree(p);
-  if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_rows) (void)hipHostFree(c->h_rows);
-  if (c->h_verify) (void)hipHostFree(c->h_verify);
-  if (c->h_score) (void)hipHostFree(c->h_score);
-  if (c->h_bias) (void)hipHostFree(c->h_bias);
-  if (c->h_repeat) (void)hipHostFree(c->h_repeat);
-  if (c->h_n_pad) (void)hipHostFree(c->h_n_pad);
+  void* const pinned[] = {c->h_pinned, c->h_stage, c->h_seq, c->h_rows.tok, c->h_verify, c->h_score.masked, c->h_bias, c->h_repeat, c->h_n_pad};
+  for (void* p : pinned)
+    if (p) (void)hipHostFree(p);
   for (int i = 0; i < 5; ++i) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
@@ -343,9 +367,6 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CHIP(hipStreamCreate(&c->own_stream));
   for (int i = 0; i < 5; ++i) { CHIP(hipEventCreate(&c->ev0[i])); CHIP(hipEventCreate(&c->ev1[i])); }
   for (int i = 0; i < 8; ++i) CHIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
-  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), sizeof(int) * (8 * 64 + 64 + 16), hipHostMallocDefault));
-  c->h_stage_ints = (size_t)c->Bmax * c->P + 3 * (size_t)c->Bmax + 64 + 1024 + 16 + 6 * 64 + 2 * 64;
-  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), sizeof(int) * c->h_stage_ints, hipHostMallocDefault));
 
   const size_t e = c->esz;
   const size_t d = c->d, H = c->H, F = c->ffn, V = c->V, T = c->T, Tp = c->Tp, P = c->P, C = c->C, B = c->Bmax;
@@ -461,7 +482,8 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
     CALLOC(c->cross_vsc, Ld * B * H * Tp, true);
   }
   // per-token decoder activations that feed a projection are fragment-major in groups of 16 streams (tw_xt_index)
-  // (sized for the 64 rows of a prefill launch - rows mode, tw_common.h - whatever max_batch is: < 1 MB)
+  // (sized for the 64 rows of a prefill launch - rows mode, tw_common.h - whatever max_batch is: < 1 MB; rows_per_launch() is at
+  //  most 64, so no launch's row count ever has to be clamped to row_cap)
   c->row_cap = (int)std::max<size_t>(B, 64);
   const size_t R = c->row_cap;
   const size_t Bg = (R + 15) / 16 * 16;  // whole groups of 16 streams
@@ -471,11 +493,9 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CALLOC(c->dstats, R * (d / 4) * 2 * 4, true);
   c->row_ids_cap = (size_t)B * P;
   CALLOC(c->row_ids, c->row_ids_cap * 4, true);
-  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_rows), sizeof(int) * 2 * c->row_ids_cap, hipHostMallocDefault));
   CALLOC(c->row_lastts, c->row_ids_cap * 4, true);
   CALLOC(c->row_choice, c->row_ids_cap * 4, true);
   CALLOC(c->verify_state, (2 + 64) * 4, true);
-  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_verify), sizeof(int) * (2 + 64 + 2), hipHostMallocDefault));
   CALLOC(c->logits, R * V * 4, true);   // (the rows of a verify launch - up to 64 - whatever max_batch is: 13 MB)
   const size_t Ha = c->Ha > 0 ? c->Ha : 1;
   CALLOC(c->align, B * Ha * P * T * 4, true);
@@ -500,8 +520,7 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   CALLOC(c->score_seq, B * P * 4, true); CALLOC(c->score_bsup, 64 * 4, true); CALLOC(c->score_sup, 1024 * 4, true);
   CALLOC(c->score_bits, ((V + 31) / 32 + 2048) * 4, true);
   CALLOC(c->score_parts, 64 * 32 * sizeof(ScorePartial), true);
-  CALLOC(c->score_out, (2 * B * P + B) * 4, true);
-  CHIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_score), sizeof(float) * (2 * B * P + B), hipHostMallocDefault));
+  { int r = alloc_staging(c); if (r != TW_OK) return bail(r); }   // (here: the device block of the scores keeps its place among the allocations)
   // ---- dtw workspace ----
   CALLOC(c->zbuf, B * Ha * P * T * 4, false);
   CALLOC(c->mat, B * P * T * 4, false);
@@ -742,8 +761,8 @@ int tw_logmel(tw_ctx* c, const float* pcm, int64_t pcm_stride, const int32_t* n_
   hipStream_t st = pick_stream(c, stream);
   const int* nv = nullptr;
   if (n_valid_host) {
-    memcpy(c->h_pinned + 512, n_valid_host, sizeof(int) * B);
-    HIPCHK(c, hipMemcpyAsync(c->n_valid_dev, c->h_pinned + 512, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    memcpy(c->h_pinned->n_valid, n_valid_host, sizeof(int) * B);
+    HIPCHK(c, hipMemcpyAsync(c->n_valid_dev, c->h_pinned->n_valid, sizeof(int) * B, hipMemcpyHostToDevice, st));
     nv = c->n_valid_dev;
   }
   tic(c, 0, st);
@@ -945,23 +964,35 @@ bool getenv_off_fuse() {
   return off;
 }
 
+// What one decode_core pass is asked for.  The defaults are tw_decode_step's pass; every other caller names what differs.
+struct DecodeOpts {
+  // > 0: rows mode (tw_common.h: tw_row_of) - the B rows are rows_streams streams x B / rows_streams consecutive positions whose
+  // tokens are `ids` (device, row order)
+  int rows_streams = 0;
+  const int* ids = nullptr;
+  // false: the input rows are already in place (the sampler's last launch of the previous step wrote them, SamplerArgs::x_next)
+  bool embed = true;
+  // the tied-logits projection of every row.  false: the tokens of the rows' positions are known (prefill_core).  Rows mode with it
+  // (draft-and-verify: verify_round) is the same launch the step uses, so a row's logits are bit for bit what the one-position step
+  // would have produced (k_decode.hip: one reduction order for every B)
+  bool logits = true;
+  // false: the cross attention is launched with Ha = 0 and no slot table, so the alignment rows an earlier tw_generate_greedy
+  // recorded stay as they are (tw_score_tokens); its output does not depend on it
+  bool record_alignment = true;
+  // != nullptr (device, [64]): a step of tw_generate_greedy_ragged (ordinary step only) - the embedding (the step's own, whatever
+  // `embed` says), the K / V^T scatter of the QKV launch and the self attention are the ragged instantiations (tw_common.h:
+  // tw_row_pos); every other launch is the plain step's
+  const int* n_pad = nullptr;
+};
+
 // one token for every stream: embed -> Ld layers -> final LN + tied logits (fp32)
-// rs > 0: rows mode (tw_common.h: tw_row_of) - the B rows are rs streams x B / rs consecutive positions whose tokens are `ids`
-// (device, row order); no logits are produced (the tokens of those positions are known: prefill_core)
-// embed = false: the input rows are already in place (the sampler's last launch of the previous step wrote them, SamplerArgs::x_next)
-// rows_logits: rows mode WITH the tied-logits projection of every row (draft-and-verify: verify_round) - the same launch the step uses,
-// so a row's logits are bit for bit what the one-position step would have produced (k_decode.hip: one reduction order for every B)
-// record_alignment = false: the cross attention is launched with Ha = 0 and no slot table, so the alignment rows an earlier
-// tw_generate_greedy recorded stay as they are (tw_score_tokens); its output does not depend on it
-// n_pad != nullptr (device, [64]): a step of tw_generate_greedy_ragged (ordinary step only) - the embedding, the K / V^T scatter of the QKV
-// launch and the self attention are the ragged instantiations (tw_common.h: tw_row_pos); every other launch is the plain step's
-int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = nullptr, bool embed = true, bool rows_logits = false,
-                bool record_alignment = true, const int* n_pad = nullptr) {
+int decode_core(tw_ctx* c, int B, hipStream_t st, const DecodeOpts& o = DecodeOpts{}) {
   const int d = c->d, H = c->H, F = c->ffn, T = c->T, P = c->P, dt = c->dtype;
   const size_t e = c->esz;
-  if (n_pad && (rs != 0 || !embed)) return fail(c, TW_EINVAL, "decode_core: a ragged step is an ordinary step with its own embedding");
+  const int rs = o.rows_streams; const int* n_pad = o.n_pad;
+  if (n_pad && rs != 0) return fail(c, TW_EINVAL, "decode_core: a ragged step is an ordinary step with its own embedding");
   if (n_pad) HIPCHK(c, launch_embed_ragged(dt, c->cur_ids, c->stt, n_pad, c->tok_emb, c->dec_pos, c->dx0, B, d, st));
-  else if (embed) HIPCHK(c, launch_embed(dt, rs > 0 ? ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
+  else if (o.embed) HIPCHK(c, launch_embed(dt, rs > 0 ? o.ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
   void* xin = c->dx0;
   void* xmid = c->dx1;
   const int Pp = (P + 63) / 64 * 64;
@@ -1003,8 +1034,8 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = n
       HIPCHK(c, launch_gemv(dt, a, st));
     }
     HIPCHK(c, launch_dec_cross_attn(dt, c->dq, fq, at(c->cross_k, cross_layer * l, c->w8 ? 1 : e), at(c->cross_v, cross_layer * l, c->w8 ? 1 : e),
-                                    c->datt, B, H, T, c->Tp, (c->Ha > 0 && record_alignment) ? c->align_slot + (size_t)l * H : nullptr, c->align,
-                                    record_alignment ? c->Ha : 0,
+                                    c->datt, B, H, T, c->Tp, (c->Ha > 0 && o.record_alignment) ? c->align_slot + (size_t)l * H : nullptr, c->align,
+                                    o.record_alignment ? c->Ha : 0,
                                     P, c->stt, c->w8 ? c->cross_ksc + (size_t)c->Bmax * H * c->Tp * l : nullptr,
                                     c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, st));
     {
@@ -1027,7 +1058,7 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = n
     }
     void* t = xin; xin = xmid; xmid = t;
   }
-  if (rs == 0 || rows_logits) {
+  if (o.logits) {
     GemvArgs a{};
     a.x = xin; a.ldx = d; a.ln_gw = c->logit_gw; a.ln_cb = c->logit_cb; a.W = c->logit_w; a.wscale = c->logit_ws; a.a16 = c->a16; a.N = c->V; a.K = d; a.B = B;
     a.y_f32 = c->logits;
@@ -1036,25 +1067,47 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, int rs = 0, const int* ids = n
   return TW_OK;
 }
 
+// rows of a rows-mode launch (B streams x consecutive positions): W8A8 quantises activations per group of 16 rows, one group per launch
+int rows_per_launch(const tw_ctx* c) { return (c->w8 && !c->a16) ? 16 : 64; }
+
+// dec_key_bound of a launch whose last position is n_keys - 1: the self attention reads keys [0, n_keys) in whole 64-key buckets, and
+// never past the bucket of `limit` (the cache's P, or a call's max_len)
+int key_bound(int n_keys, int limit) { return std::min((n_keys + 63) / 64 * 64, (limit + 63) / 64 * 64); }
+
+// The position-major row tables of a rows-mode pass over positions [p_first, p_last] of B streams whose tokens are tok[b * ld + p]: row
+// (p - p_first) * B + b (row r of the launch at p0 is stream r % B at position p0 + r / B) holds, in h_rows.tok, the token at p and -
+// with_lastts - in h_rows.lastts the last timestamp token (>= ts_begin) among the sampled tokens (positions >= n_begin) up to p, or -1
+void fill_row_tables(tw_ctx* c, int B, const int* tok, int ld, int p_first, int p_last, bool with_lastts, int n_begin, int ts_begin) {
+  for (int b = 0; b < B; ++b) {
+    int lt = -1;
+    for (int p = with_lastts ? std::min(n_begin, p_first) : p_first; p <= p_last; ++p) {
+      const int t = tok[(size_t)b * ld + p];
+      if (p >= n_begin && t >= ts_begin) lt = t;
+      if (p < p_first) continue;
+      c->h_rows.tok[(size_t)(p - p_first) * B + b] = t;
+      if (with_lastts) c->h_rows.lastts[(size_t)(p - p_first) * B + b] = lt;
+    }
+  }
+}
+
 // Batched prefill of the positions [0, n_pos) of B streams whose tokens are known (host table tok[b * ld + p]): launches of up to
 // `cap` rows = B streams x L consecutive positions (rows mode), each a full pass through the decoder layers that fills the
 // self-attention caches and the alignment rows of its positions; the weights are streamed once per L positions instead of once per
 // position.  On return the device position is n_pos.  Not captured in a graph (a handful of launches per call).
 int prefill_core(tw_ctx* c, int B, const int* tok, int ld, int n_pos, hipStream_t st) {
   if (n_pos <= 0) return TW_OK;
-  const int cap = (c->w8 && !c->a16) ? 16 : 64;     // W8A8 quantises activations per group of 16 rows: one group per launch
+  const int cap = rows_per_launch(c);
   if (B > cap) return fail(c, TW_EINVAL, "prefill: %d streams exceed the %d rows of a launch", B, cap);
-  const int L = std::max(1, std::min(cap, c->row_cap) / B);
-  // position-major token table: row r of the launch at p0 is stream r % B at position p0 + r / B
+  const int L = std::max(1, cap / B);
   if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "prefill: %d positions x %d streams exceed the row table", n_pos, B);
-  int* h = c->h_rows;
-  for (int p = 0; p < n_pos; ++p)
-    for (int b = 0; b < B; ++b) h[(size_t)p * B + b] = tok[(size_t)b * ld + p];
-  HIPCHK(c, hipMemcpyAsync(c->row_ids, h, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  fill_row_tables(c, B, tok, ld, 0, n_pos - 1, false, 0, 0);
+  HIPCHK(c, hipMemcpyAsync(c->row_ids, c->h_rows.tok, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  DecodeOpts rows; rows.rows_streams = B; rows.logits = false;
   for (int p0 = 0; p0 < n_pos; p0 += L) {
     const int l = std::min(L, n_pos - p0);
-    c->dec_key_bound = std::min(((p0 + l + 63) / 64) * 64, ((c->P + 63) / 64) * 64);
-    int r = decode_core(c, l * B, st, B, c->row_ids + (size_t)p0 * B);
+    c->dec_key_bound = key_bound(p0 + l, c->P);
+    rows.ids = c->row_ids + (size_t)p0 * B;
+    int r = decode_core(c, l * B, st, rows);
     if (r != TW_OK) return r;
     HIPCHK(c, launch_advance(c->stt, l, st));
   }
@@ -1074,34 +1127,24 @@ int prefill_core(tw_ctx* c, int B, const int* tok, int ld, int n_pos, hipStream_
 // ba != nullptr (tw_generate_greedy_biased): every launch's logits pass through launch_seq_bias before its sampler, rows mode.
 // ra != nullptr (tw_generate_greedy_repeat): ... and through launch_repeat, behind the bias.
 int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, int p_start, int p_end, int rows_cap, const SamplerArgs& sa0,
-                 hipStream_t st, int* p_next, int* n_launches, int p_given, int* next_given, const SeqBiasArgs* ba,
-                 const RepeatArgs* ra) {
+                 hipStream_t st, int* p_next, int p_given, int* next_given, const SeqBiasArgs* ba, const RepeatArgs* ra) {
   const int n_pos = p_end - p_start + 1;
   if (n_pos < 1 || B > rows_cap) return fail(c, TW_EINVAL, "verify: bad round [%d, %d] for %d streams", p_start, p_end, B);
   if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "verify: %d positions x %d streams exceed the row table", n_pos, B);
   const int L = std::max(1, rows_cap / B);
-  int* h = c->h_rows;
-  int* hl = c->h_rows + c->row_ids_cap;
-  for (int b = 0; b < B; ++b) {
-    int lt = -1;
-    for (int p = n_begin; p < p_start; ++p) if (tok[(size_t)b * ld + p] >= ts_begin) lt = tok[(size_t)b * ld + p];
-    for (int p = p_start; p <= p_end; ++p) {
-      const int t = tok[(size_t)b * ld + p];
-      if (p >= n_begin && t >= ts_begin) lt = t;
-      h[(size_t)(p - p_start) * B + b] = t;
-      hl[(size_t)(p - p_start) * B + b] = lt;
-    }
-  }
-  int* hv = c->h_verify;
-  hv[66] = 0x7fffffff; hv[67] = 0;
-  HIPCHK(c, hipMemcpyAsync(c->row_ids, h, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->row_lastts, hl, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->verify_state, hv + 66, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  fill_row_tables(c, B, tok, ld, p_start, p_end, true, n_begin, ts_begin);
+  VerifyStage* hv = c->h_verify;
+  hv->reset[0] = 0x7fffffff; hv->reset[1] = 0;   // no mismatch yet, undecided
+  HIPCHK(c, hipMemcpyAsync(c->row_ids, c->h_rows.tok, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->row_lastts, c->h_rows.lastts, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->verify_state, hv->reset, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  DecodeOpts rows; rows.rows_streams = B;
   for (int p0 = p_start; p0 <= p_end; p0 += L) {
     const int l = std::min(L, p_end - p0 + 1);
     const size_t off = (size_t)(p0 - p_start) * B;
-    c->dec_key_bound = std::min(((p0 + l + 63) / 64) * 64, ((c->P + 63) / 64) * 64);
-    int r = decode_core(c, l * B, st, B, c->row_ids + off, true, true);
+    c->dec_key_bound = key_bound(p0 + l, c->P);
+    rows.ids = c->row_ids + off;
+    int r = decode_core(c, l * B, st, rows);
     if (r != TW_OK) return r;
     SamplerArgs sa = sa0;
     sa.B = l * B; sa.rows_streams = B; sa.row_pos0 = p0; sa.row_lastts = c->row_lastts + off; sa.row_choice = c->row_choice + off;
@@ -1119,14 +1162,14 @@ int verify_round(tw_ctx* c, int B, int* tok, int ld, int n_begin, int ts_begin, 
     HIPCHK(c, launch_sampler_rows(sa, st));
     HIPCHK(c, hipMemcpyAsync(hv, c->verify_state, sizeof(int) * (2 + B), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    ++*n_launches;
-    if (hv[1] != 0) {
-      const int pn = hv[1];
+    ++c->last_draft[2];
+    if (hv->decided != 0) {
+      const int pn = hv->decided;
       if (pn < p0 + 1 || pn > p0 + l) return fail(c, TW_EHIP, "verify: decided position %d outside the launch [%d, %d)", pn - 1, p0, p0 + l);
       bool same = pn <= p_given;
       for (int b = 0; b < B; ++b) {
-        same = same && tok[(size_t)b * ld + pn] == hv[2 + b];
-        tok[(size_t)b * ld + pn] = hv[2 + b];
+        same = same && tok[(size_t)b * ld + pn] == hv->choice[b];
+        tok[(size_t)b * ld + pn] = hv->choice[b];
       }
       *next_given = same ? 1 : 0;
       *p_next = pn;
@@ -1225,9 +1268,43 @@ int pack_repeat(tw_ctx* c, const char* fn, int rows, int max_n, const tw_repeat_
 }
 
 int reset_state(tw_ctx* c, int n_prompt, hipStream_t st) {
-  DecState s{0, n_prompt, 0, 0};
-  memcpy(c->h_pinned + 576, &s, sizeof s);
-  HIPCHK(c, hipMemcpyAsync(c->stt, c->h_pinned + 576, sizeof s, hipMemcpyHostToDevice, st));
+  c->h_pinned->state = DecState{0, n_prompt, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(c->stt, &c->h_pinned->state, sizeof(DecState), hipMemcpyHostToDevice, st));
+  return TW_OK;
+}
+
+// Every TW_EINVAL of the logits processors' options, for every tw_generate_* call and tw_score_tokens alike (include/thewhisper.h)
+int check_processor_opts(tw_ctx* c, const tw_greedy_opts* o) {
+  if (o->n_begin_suppress < 0 || o->n_begin_suppress > 64 || o->n_suppress < 0 || o->n_suppress > 1024 ||
+      (o->n_begin_suppress > 0 && !o->begin_suppress) || (o->n_suppress > 0 && !o->suppress))
+    return fail(c, TW_EINVAL, "suppress lists too long");
+  if (o->pad_id < 0 || o->pad_id >= c->V || o->eos_id < 0 || o->eos_id >= c->V)
+    return fail(c, TW_EINVAL, "pad_id %d / eos_id %d outside the vocabulary", o->pad_id, o->eos_id);   // (the sampler embeds pad_id for finished rows)
+  return TW_OK;
+}
+
+// The two suppress lists of `o` (checked; nullptr: none) through h_stage to their device arrays, and the static list as a bitmap
+int upload_suppress_lists(tw_ctx* c, const tw_greedy_opts* o, int* bsup_dev, int* sup_dev, unsigned* bits, hipStream_t st) {
+  const int n_bsup = o ? o->n_begin_suppress : 0, n_sup = o ? o->n_suppress : 0;
+  if (n_bsup > 0) {
+    memcpy(c->h_stage->bsup, o->begin_suppress, sizeof(int) * n_bsup);
+    HIPCHK(c, hipMemcpyAsync(bsup_dev, c->h_stage->bsup, sizeof(int) * n_bsup, hipMemcpyHostToDevice, st));
+  }
+  if (n_sup > 0) {
+    memcpy(c->h_stage->sup, o->suppress, sizeof(int) * n_sup);
+    HIPCHK(c, hipMemcpyAsync(sup_dev, c->h_stage->sup, sizeof(int) * n_sup, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, launch_suppress_bitmap(sup_dev, n_sup, bits, c->V, st));
+  return TW_OK;
+}
+
+// A device table of `cap` ints and its pinned staging, both allocated by the first call of the context that needs them and freed in
+// tw_destroy: the first n ints of src go up (the staging is not touched again before the call's stream synchronisation)
+int upload_first_use_table(tw_ctx* c, int*& dev, int*& pinned, size_t cap, bool zero, const int* src, size_t n, hipStream_t st) {
+  if (!dev) ALLOC(c, dev, sizeof(int) * cap, zero);
+  if (!pinned) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&pinned), sizeof(int) * cap));
+  memcpy(pinned, src, sizeof(int) * n);
+  HIPCHK(c, hipMemcpyAsync(dev, pinned, sizeof(int) * n, hipMemcpyHostToDevice, st));
   return TW_OK;
 }
 
@@ -1272,12 +1349,16 @@ int tw_decode_step(tw_ctx* c, int32_t B, const int32_t* ids_host, float* logits_
 static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_sample_opts* so,
                          const tw_filter_opts* fo, const tw_bias_opts* bo, int32_t* out_ids, int32_t* out_len, void* stream,
                          const int32_t* n_pad = nullptr, const tw_repeat_opts* ro = nullptr) {
-  const char* fn = n_pad ? "tw_generate_greedy_ragged" : ro ? "tw_generate_greedy_repeat" : bo ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
-  const bool ragged = n_pad != nullptr;
+  const bool ragged = n_pad != nullptr, biased = bo != nullptr;
+  // the call's flavour: its name in messages, and its character in the step-graph key - the sampler's launches, or 'r', a ragged call,
+  // whose steps are other launches: a graph of one flavour is never replayed for a call of another
+  const char* fn = ragged ? "tw_generate_greedy_ragged" : ro ? "tw_generate_greedy_repeat" : biased ? "tw_generate_greedy_biased" : fo ? "tw_generate_sample_filtered" : so ? "tw_generate_sample" : "tw_generate_greedy";
+  char flavour = ragged ? 'r'                         : ro ? (biased ? 'q' : 'p')         : biased ? 'b'                         : fo ? 'f'                           : so ? 's'                  : 'g';
   if (ragged && (so || fo || bo || ro || o->n_forced != 0 || o->n_draft != 0)) return fail(c, TW_EINVAL, "%s: padding goes with the plain greedy call only", fn);
   if (B < 1 || B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
-  if (o->n_begin_suppress > 64 || o->n_suppress > 1024) return fail(c, TW_EINVAL, "suppress lists too long");
+  int r = check_processor_opts(c, o);
+  if (r != TW_OK) return r;
   if (o->want_alignment && c->Ha == 0) return fail(c, TW_EINVAL, "want_alignment but the context has no alignment heads");
   // forced output tokens (tw_greedy_opts::n_forced): the begin index of the generation is n_begin, the tokens behind it are given
   const int n_forced = o->n_forced;
@@ -1286,27 +1367,25 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   const int n_draft = o->n_draft;
   if (n_draft < 0 || n_draft >= n_prompt || (n_draft > 0 && n_forced > 0))
     return fail(c, TW_EINVAL, "bad n_draft %d (n_prompt %d, n_forced %d: one of the two)", n_draft, n_prompt, n_forced);
-  if (o->pad_id < 0 || o->pad_id >= c->V || o->eos_id < 0 || o->eos_id >= c->V)
-    return fail(c, TW_EINVAL, "pad_id %d / eos_id %d outside the vocabulary", o->pad_id, o->eos_id);   // (the sampler embeds pad_id for finished rows)
   const int n_begin = n_prompt - n_forced - n_draft;
   int max_len = n_begin + o->max_new_tokens;
   if (o->max_length > 0 && o->max_length < max_len) max_len = o->max_length;
   if (max_len > c->P) max_len = c->P;
   if (max_len <= n_prompt) return fail(c, TW_EINVAL, "nothing to generate (max_len %d <= n_prompt %d)", max_len, n_prompt);
   const int out_ld = o->max_length > 0 ? o->max_length : max_len;
-  const bool biased = bo != nullptr;
   std::vector<int> bias_tab;   // the call's packed sequence table (checked here, with the other refusals; uploaded with the initial state)
   if (biased) {
     if (B > 64) return fail(c, TW_EINVAL, "%s: %d streams (1..64)", fn, B);
-    int r = pack_seq_bias(c, B, bo, bias_tab);
+    r = pack_seq_bias(c, B, bo, bias_tab);
     if (r != TW_OK) return r;
   }
   int repeat_tab[kRepeatTabWords];   // the call's per-stream penalties and n-gram sizes (checked here; uploaded with the initial state)
   bool repeat = false;
   if (ro) {
     if (so || fo) return fail(c, TW_EINVAL, "%s: repeat options go with the greedy call only", fn);
-    int r = pack_repeat(c, fn, B, c->P, ro, repeat_tab, &repeat);
+    r = pack_repeat(c, fn, B, c->P, ro, repeat_tab, &repeat);
     if (r != TW_OK) return r;
+    if (!repeat) flavour = biased ? 'b' : 'g';   // every row off: the call is the plain or the biased one
   }
   c->dec_key_bound = max_len;   // per step: the 64-key bucket of the position (below)
   hipStream_t st = pick_stream(c, stream);
@@ -1314,19 +1393,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
 
   // ---- initial state: staged in PINNED memory, so the uploads are asynchronous and the loop's first launch follows them without a
   //      host synchronisation (the staging area is not touched again before the stream synchronisation at the end of this call) ----
-  int* hseq = c->h_stage;                                  // [B][P]
-  int* first = hseq + (size_t)c->Bmax * P;                 // [B]
-  int* zeros = first + c->Bmax;
-  int* neg = zeros + c->Bmax;
-  int* bsup = neg + c->Bmax;                               // [64]
-  int* sup = bsup + 64;                                    // [1024]
-  DecState* s0p = reinterpret_cast<DecState*>(sup + 1024);
-  float* h_inv_t = reinterpret_cast<float*>(sup + 1024 + 16);     // [64]
-  uint32_t* h_key = reinterpret_cast<uint32_t*>(h_inv_t + 64);    // [64][2]
-  uint32_t* h_off = h_key + 128;                                  // [64][2]
-  int* h_noisy = reinterpret_cast<int*>(h_off + 128);             // [64]
-  int* h_top_k = h_noisy + 64;                                    // [64]
-  float* h_top_p = reinterpret_cast<float*>(h_top_k + 64);        // [64]
+  GenStage& hs = *c->h_stage;
+  int* hseq = c->h_seq;                                    // [B][P]
   for (size_t i = 0; i < (size_t)B * P; ++i) hseq[i] = o->pad_id;
   for (int b = 0; b < B; ++b) {
     for (int i = 0; i < n_prompt; ++i) {
@@ -1335,73 +1403,57 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       hseq[(size_t)b * P + i] = t;
     }
     // with forced tokens the loop starts at the LAST given position (everything before it is prefilled below)
-    first[b] = prompt[(size_t)b * n_prompt + (n_forced > 0 ? n_prompt - 1 : 0)];
-    zeros[b] = (so && so->temperature[b] < 0.f) ? 1 : 0;   // a row that sits the call out starts finished
-    neg[b] = -1;
+    hs.first[b] = prompt[(size_t)b * n_prompt + (n_forced > 0 ? n_prompt - 1 : 0)];
+    hs.finished0[b] = (so && so->temperature[b] < 0.f) ? 1 : 0;   // a row that sits the call out starts finished
+    hs.last_ts0[b] = -1;
     if (so) {
       const float t = so->temperature[b];
-      h_noisy[b] = t > 0.f ? 1 : 0;
-      h_inv_t[b] = t > 0.f ? 1.0f / t : 1.0f;
+      hs.noisy[b] = t > 0.f ? 1 : 0;
+      hs.inv_t[b] = t > 0.f ? 1.0f / t : 1.0f;
       const uint64_t sd = so->seed ? so->seed[b] : 0, of = so->offset ? so->offset[b] : 0;
-      h_key[2 * b] = (uint32_t)sd; h_key[2 * b + 1] = (uint32_t)(sd >> 32);
-      h_off[2 * b] = (uint32_t)of; h_off[2 * b + 1] = (uint32_t)(of >> 32);
+      hs.key[b][0] = (uint32_t)sd; hs.key[b][1] = (uint32_t)(sd >> 32);
+      hs.off[b][0] = (uint32_t)of; hs.off[b][1] = (uint32_t)(of >> 32);
       if (fo) {   // (a greedy row ignores the filters: its arg-max is always kept)
-        h_top_k[b] = (t > 0.f && fo->top_k) ? fo->top_k[b] : 0;
-        h_top_p[b] = (t > 0.f && fo->top_p) ? fo->top_p[b] : 1.0f;
+        hs.top_k[b] = (t > 0.f && fo->top_k) ? fo->top_k[b] : 0;
+        hs.top_p[b] = (t > 0.f && fo->top_p) ? fo->top_p[b] : 1.0f;
       }
     }
     for (int i = n_begin; i < n_prompt; ++i) {   // state the sampler would have after producing the forced tokens itself
       const int t = prompt[(size_t)b * n_prompt + i];
       if (t == o->eos_id) return fail(c, TW_EINVAL, n_draft > 0 ? "a draft token is <eos>" : "a forced token is <eos>");
-      if (n_forced > 0 && o->timestamps && t > o->no_timestamps_id) neg[b] = t;
+      if (n_forced > 0 && o->timestamps && t > o->no_timestamps_id) hs.last_ts0[b] = t;
     }
   }
-  if (biased) {   // device table and pinned staging: allocated by the first biased call of the context, freed in tw_destroy
-    if (!c->bias_tab) ALLOC(c, c->bias_tab, sizeof(int) * kSeqBiasTabWords, false);
-    if (!c->h_bias) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_bias), sizeof(int) * kSeqBiasTabWords));
-    memcpy(c->h_bias, bias_tab.data(), sizeof(int) * bias_tab.size());
-    HIPCHK(c, hipMemcpyAsync(c->bias_tab, c->h_bias, sizeof(int) * bias_tab.size(), hipMemcpyHostToDevice, st));
+  // the call's tables, each allocated by the context's first call of that flavour (upload_first_use_table)
+  if (biased) r = upload_first_use_table(c, c->bias_tab, c->h_bias, kSeqBiasTabWords, false, bias_tab.data(), bias_tab.size(), st);
+  if (r == TW_OK && repeat) r = upload_first_use_table(c, c->repeat_tab, c->h_repeat, kRepeatTabWords, true, repeat_tab, kRepeatTabWords, st);
+  if (r == TW_OK && ragged) {
+    int pads[64] = {};
+    std::copy(n_pad, n_pad + B, pads);
+    r = upload_first_use_table(c, c->n_pad_tab, c->h_n_pad, 64, true, pads, 64, st);
   }
-  if (repeat) {   // the same for the repeat table
-    if (!c->repeat_tab) ALLOC(c, c->repeat_tab, sizeof(int) * kRepeatTabWords, true);
-    if (!c->h_repeat) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_repeat), sizeof(int) * kRepeatTabWords));
-    memcpy(c->h_repeat, repeat_tab, sizeof repeat_tab);
-    HIPCHK(c, hipMemcpyAsync(c->repeat_tab, c->h_repeat, sizeof repeat_tab, hipMemcpyHostToDevice, st));
-  }
-  if (ragged) {   // the same for the padding lengths (the staging is not touched again before this call's stream synchronisation)
-    if (!c->n_pad_tab) ALLOC(c, c->n_pad_tab, sizeof(int) * 64, true);
-    if (!c->h_n_pad) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_n_pad), sizeof(int) * 64));
-    for (int b = 0; b < 64; ++b) c->h_n_pad[b] = b < B ? n_pad[b] : 0;
-    HIPCHK(c, hipMemcpyAsync(c->n_pad_tab, c->h_n_pad, sizeof(int) * 64, hipMemcpyHostToDevice, st));
-  }
+  if (r != TW_OK) return r;
   HIPCHK(c, hipMemcpyAsync(c->seq, hseq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->cur_ids, first, sizeof(int) * B, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->finished, zeros, sizeof(int) * B, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->last_ts, neg, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->cur_ids, hs.first, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->finished, hs.finished0, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->last_ts, hs.last_ts0, sizeof(int) * B, hipMemcpyHostToDevice, st));
   if (so) {
-    HIPCHK(c, hipMemcpyAsync(c->sample_inv_t, h_inv_t, sizeof(float) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->sample_key, h_key, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->sample_off, h_off, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->sample_noisy, h_noisy, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_inv_t, hs.inv_t, sizeof(float) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_key, hs.key, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_off, hs.off, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sample_noisy, hs.noisy, sizeof(int) * B, hipMemcpyHostToDevice, st));
   }
   if (fo) {
-    HIPCHK(c, hipMemcpyAsync(c->filter_top_k, h_top_k, sizeof(int) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->filter_top_p, h_top_p, sizeof(float) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->filter_top_k, hs.top_k, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->filter_top_p, hs.top_p, sizeof(float) * B, hipMemcpyHostToDevice, st));
   }
-  if (o->n_begin_suppress > 0) {
-    memcpy(bsup, o->begin_suppress, sizeof(int) * o->n_begin_suppress);
-    HIPCHK(c, hipMemcpyAsync(c->begin_suppress_dev, bsup, sizeof(int) * o->n_begin_suppress, hipMemcpyHostToDevice, st));
-  }
-  if (o->n_suppress > 0) {
-    memcpy(sup, o->suppress, sizeof(int) * o->n_suppress);
-    HIPCHK(c, hipMemcpyAsync(c->suppress_dev, sup, sizeof(int) * o->n_suppress, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, launch_suppress_bitmap(c->suppress_dev, o->n_suppress, c->suppress_bits, c->V, st));
-  *s0p = DecState{0, n_begin, max_len - 1, B};
-  HIPCHK(c, hipMemcpyAsync(c->stt, s0p, sizeof(DecState), hipMemcpyHostToDevice, st));
+  r = upload_suppress_lists(c, o, c->begin_suppress_dev, c->suppress_dev, c->suppress_bits, st);
+  if (r != TW_OK) return r;
+  hs.state = DecState{0, n_begin, max_len - 1, B};
+  HIPCHK(c, hipMemcpyAsync(c->stt, &hs.state, sizeof(DecState), hipMemcpyHostToDevice, st));
   int s_start = n_forced > 0 ? n_prompt - 1 : 0;
   if (n_forced > 0) {   // positions 0 .. n_prompt-2 in batched launches (self-attention caches + alignment rows); device pos -> s_start
-    int r = prefill_core(c, B, prompt, n_prompt, s_start, st);
+    r = prefill_core(c, B, prompt, n_prompt, s_start, st);
     if (r != TW_OK) return r;
   }
 
@@ -1432,7 +1484,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     //      that hold <eos> at `pos`, since no earlier round ended on one - and the ordinary loop pads those rows from here;
     //      the other streams' remaining guesses are dropped. ----
     constexpr int first_rows = 64, retry_rows = 16, max_rounds = 16;   // rows of round 1 / of a retry launch, rounds per call
-    const int cap = std::min((c->w8 && !c->a16) ? 16 : 64, c->row_cap);   // W8A8 quantises activations per group of 16 rows: one group per launch
+    const int cap = rows_per_launch(c);
     if (B > cap) return fail(c, TW_EINVAL, "n_draft: %d streams exceed the %d rows of a launch", B, cap);
     const int ts_begin = o->timestamps ? o->no_timestamps_id + 1 : c->V;
     const int p_end = n_prompt - 1;
@@ -1443,8 +1495,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       const int rows = rounds == 0 ? std::min(cap, std::max(first_rows, B)) : std::min(cap, std::max(retry_rows, 4 * B));
       const int pe = rounds == 0 ? p_end : std::min(p_end, pos + std::max(1, rows / B) - 1);
       int pn = 0, next_given = 0;
-      int r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, &c->last_draft[2], p_end, &next_given, biased ? &ba : nullptr,
-                           repeat ? &rpa : nullptr);
+      r = verify_round(c, B, hseq, P, n_begin, ts_begin, pos, pe, rows, sa, st, &pn, p_end, &next_given, biased ? &ba : nullptr, repeat ? &rpa : nullptr);
       if (r != TW_OK) return r;
       ++rounds;
       // guesses this round confirmed: the given tokens at positions <= p_acc that were compared, and the token the round produced
@@ -1465,15 +1516,15 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     s_start = pos;
   }
   sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = ragged ? nullptr : c->dx0; sa.d = c->d; sa.dtype = c->dtype;
-  const int* pad_tab = ragged ? c->n_pad_tab : nullptr;
+  DecodeOpts step; step.embed = false; step.n_pad = ragged ? c->n_pad_tab : nullptr;   // the loop's step: its input rows are in place, or - ragged - it embeds its own
   if (!ragged) HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
-  // (last field: the sampler flavour - greedy, biased greedy, greedy with repeat options 'p', biased with repeat options 'q', sampling,
-  //  filtered sampling - or 'r', a ragged greedy call, whose steps are other launches: a graph of one is never replayed for a call of another)
+  // (last field: the call's flavour, above - greedy, biased greedy, greedy with repeat options 'p', biased with repeat options 'q',
+  //  sampling, filtered sampling, ragged greedy)
   snprintf(keybuf, sizeof keybuf, "%d|%d|%d|%d|%d|%d|%d|%d|%d|%c", B, o->eos_id, o->pad_id, o->min_new_tokens, o->timestamps,
-           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, ragged ? 'r' : repeat ? (biased ? 'q' : 'p') : biased ? 'b' : fo ? 'f' : so ? 's' : 'g');
+           o->no_timestamps_id, o->max_initial_timestamp_index, o->n_begin_suppress, o->n_suppress, flavour);
   SampleArgs sma{};   // the per-row arrays live in device memory: one captured graph serves every temperature and seed
   sma.inv_t = c->sample_inv_t; sma.key = c->sample_key; sma.off = c->sample_off; sma.noisy = c->sample_noisy; sma.parts = c->sample_parts;
   FilterArgs fla{};   // ... and every top-k / top-p
@@ -1511,7 +1562,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     int r = TW_OK;
     hipError_t es = hipSuccess;
     for (int i = 0; i < n && r == TW_OK && es == hipSuccess; ++i) {
-      r = decode_core(c, B, st, 0, nullptr, ragged, false, true, pad_tab);
+      r = decode_core(c, B, st, step);
       if (r == TW_OK) es = sample_step();
     }
     hipError_t ee = hipStreamEndCapture(st, &g);
@@ -1553,7 +1604,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
                           s + group_forced - 1 < n_begin + o->min_new_tokens - 1;
     const int n = eos_free ? group_forced : ((use_graph && s + group <= max_len - 1) ? group : 1);   // steps in this launch
     const int last = s + n - 1;
-    const int kb = std::min(((last + 64) / 64) * 64, ((max_len + 63) / 64) * 64);   // keys [0, kb) cover positions s .. last
+    const int kb = key_bound(last + 1, max_len);   // keys [0, kb) cover positions s .. last
     if (use_graph) {
       hipGraphExec_t ex = nullptr;
       int r = graph_for(kb, n, &ex);
@@ -1561,20 +1612,20 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       HIPCHK(c, hipGraphLaunch(ex, st));
     } else {
       c->dec_key_bound = kb;
-      int r = decode_core(c, B, st, 0, nullptr, ragged, false, true, pad_tab);
+      int r = decode_core(c, B, st, step);
       if (r != TW_OK) return r;
       HIPCHK(c, sample_step());
     }
     steps += n;
     s += n;
     const int slot = launches % 8;
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + slot * 64, c->finished, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned->finished[slot], c->finished, sizeof(int) * B, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipEventRecord(c->ring_ev[slot], st));
     if (launches >= LAG) {
       const int ps = (launches - LAG) % 8;
       HIPCHK(c, hipEventSynchronize(c->ring_ev[ps]));
       bool done = true;
-      for (int b = 0; b < B; ++b) done &= (c->h_pinned[ps * 64 + b] != 0);
+      for (int b = 0; b < B; ++b) done &= (c->h_pinned->finished[ps][b] != 0);
       all_done = done;
     }
     if (launches == 0) ht_first = ht_ms();
@@ -1662,11 +1713,10 @@ int tw_generate_greedy_ragged(tw_ctx* c, int32_t B, const int32_t* prompt, int32
       padded |= n_pad[b] > 0;
     }
   }
-  // nothing padded: the call IS tw_generate_greedy, launch for launch
-  if (!padded) return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream);
-  if (o->n_forced != 0 || o->n_draft != 0)
+  if (padded && (o->n_forced != 0 || o->n_draft != 0))
     return fail(c, TW_EINVAL, "%s: n_forced %d / n_draft %d: forced and draft tokens do not go with padded rows", fn, o->n_forced, o->n_draft);
-  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream, n_pad);
+  // nothing padded: the call IS tw_generate_greedy, launch for launch
+  return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream, padded ? n_pad : nullptr);
 }
 
 // tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter
@@ -1717,20 +1767,15 @@ int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_
   if (!c || !ids) return fail(c, TW_EINVAL, "tw_score_tokens: null argument");
   TW_ON_DEVICE(c);
   const int P = c->P;
-  const int cap = std::min((c->w8 && !c->a16) ? 16 : 64, c->row_cap);   // W8A8 quantises activations per group of 16 rows: one group per launch
+  const int cap = rows_per_launch(c);
   if (B < 1 || B > cap) return fail(c, TW_EINVAL, "tw_score_tokens: %d streams, a launch has %d rows", B, cap);
   if (n_prompt < 1 || seq_len <= n_prompt || seq_len > P) return fail(c, TW_EINVAL, "tw_score_tokens: seq_len %d outside (n_prompt %d, %d]", seq_len, n_prompt, P);
   if (ld < seq_len) return fail(c, TW_EINVAL, "tw_score_tokens: ld %d < seq_len %d", ld, seq_len);
   const int n_pos = seq_len - 1;    // position p yields the score of the token at p + 1
   if ((size_t)n_pos * B > c->row_ids_cap) return fail(c, TW_EINVAL, "tw_score_tokens: %d positions x %d streams exceed the row table", n_pos, B);
   if (!o && out_logprob) return fail(c, TW_EINVAL, "tw_score_tokens: the masked log-probabilities need the processors' options");
-  if (o) {
-    if (o->n_begin_suppress < 0 || o->n_begin_suppress > 64 || o->n_suppress < 0 || o->n_suppress > 1024 ||
-        (o->n_begin_suppress > 0 && !o->begin_suppress) || (o->n_suppress > 0 && !o->suppress))
-      return fail(c, TW_EINVAL, "suppress lists too long");
-    if (o->pad_id < 0 || o->pad_id >= c->V || o->eos_id < 0 || o->eos_id >= c->V)
-      return fail(c, TW_EINVAL, "pad_id %d / eos_id %d outside the vocabulary", o->pad_id, o->eos_id);
-  }
+  int r = o ? check_processor_opts(c, o) : TW_OK;
+  if (r != TW_OK) return r;
   if (no_speech_id >= c->V) return fail(c, TW_EINVAL, "tw_score_tokens: no_speech_id %d outside the vocabulary", no_speech_id);
   if (no_speech_id >= 0 && (no_speech_pos < 0 || no_speech_pos >= seq_len - 1))
     return fail(c, TW_EINVAL, "tw_score_tokens: no_speech_pos %d outside [0, %d)", no_speech_pos, seq_len - 1);
@@ -1743,65 +1788,45 @@ int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_
   hipStream_t st = pick_stream(c, stream);
 
   // ---- staging (pinned; not touched again before the synchronisation at the end of this call) ----
-  int* hseq = c->h_stage;                                       // [B][P]
-  int* bsup = hseq + (size_t)c->Bmax * P + 3 * (size_t)c->Bmax; // [64]
-  int* sup = bsup + 64;                                         // [1024]
-  int* h = c->h_rows;                                           // position-major token table
-  int* hl = c->h_rows + c->row_ids_cap;                         // ... and the last timestamp token among the tokens sampled so far
-  const int ts_begin = (o && o->timestamps) ? o->no_timestamps_id + 1 : c->V;
-  for (int b = 0; b < B; ++b) {
-    int lt = -1;
-    for (int i = 0; i < P; ++i) hseq[(size_t)b * P + i] = i < seq_len ? ids[(size_t)b * ld + i] : 0;
-    for (int p = 0; p < n_pos; ++p) {
-      const int t = ids[(size_t)b * ld + p];
-      if (p >= n_prompt && t >= ts_begin) lt = t;
-      h[(size_t)p * B + b] = t;
-      hl[(size_t)p * B + b] = lt;
-    }
-  }
-  HIPCHK(c, hipMemcpyAsync(c->score_seq, hseq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->row_ids, h, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->row_lastts, hl, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
-  const int n_bsup = o ? o->n_begin_suppress : 0, n_sup = o ? o->n_suppress : 0;
-  if (n_bsup > 0) {
-    memcpy(bsup, o->begin_suppress, sizeof(int) * n_bsup);
-    HIPCHK(c, hipMemcpyAsync(c->score_bsup, bsup, sizeof(int) * n_bsup, hipMemcpyHostToDevice, st));
-  }
-  if (n_sup > 0) {
-    memcpy(sup, o->suppress, sizeof(int) * n_sup);
-    HIPCHK(c, hipMemcpyAsync(c->score_sup, sup, sizeof(int) * n_sup, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, launch_suppress_bitmap(c->score_sup, n_sup, c->score_bits, c->V, st));
-  int r = reset_state(c, n_prompt, st);     // device position 0, begin index n_prompt
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < P; ++i) c->h_seq[(size_t)b * P + i] = i < seq_len ? ids[(size_t)b * ld + i] : 0;
+  // the rows' tokens, and per row the last timestamp token among the tokens sampled so far
+  fill_row_tables(c, B, ids, ld, 0, n_pos - 1, true, n_prompt, (o && o->timestamps) ? o->no_timestamps_id + 1 : c->V);
+  HIPCHK(c, hipMemcpyAsync(c->score_seq, c->h_seq, sizeof(int) * (size_t)B * P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->row_ids, c->h_rows.tok, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->row_lastts, c->h_rows.lastts, sizeof(int) * (size_t)n_pos * B, hipMemcpyHostToDevice, st));
+  r = upload_suppress_lists(c, o, c->score_bsup, c->score_sup, c->score_bits, st);
+  if (r == TW_OK) r = reset_state(c, n_prompt, st);     // device position 0, begin index n_prompt
   if (r != TW_OK) return r;
 
   ScoreArgs a{};
   a.s.logits = c->logits; a.s.V = c->V; a.s.seq = c->score_seq; a.s.seq_ld = P; a.s.stt = c->stt;
-  a.s.begin_suppress = c->score_bsup; a.s.n_begin_suppress = n_bsup; a.s.suppress_bits = c->score_bits;
+  a.s.begin_suppress = c->score_bsup; a.s.n_begin_suppress = o ? o->n_begin_suppress : 0; a.s.suppress_bits = c->score_bits;
   a.s.max_initial_ts = -1;
   if (o) {   // (NULL: nothing is masked and the masked numbers, equal to the raw ones, are not handed out)
     a.s.eos = o->eos_id; a.s.pad = o->pad_id; a.s.min_new = o->min_new_tokens; a.s.timestamps = o->timestamps;
     a.s.no_ts_id = o->no_timestamps_id; a.s.max_initial_ts = o->max_initial_timestamp_index;
   }
-  const size_t plane = (size_t)c->Bmax * P;
-  a.parts = c->score_parts; a.out_masked = c->score_out; a.out_raw = c->score_out + plane; a.out_ld = P;
-  a.ns_id = no_speech_id >= 0 ? no_speech_id : -1; a.ns_pos = no_speech_pos; a.out_ns = c->score_out + 2 * plane;
+  a.parts = c->score_parts; a.out_masked = c->score_out.masked; a.out_raw = c->score_out.raw; a.out_ld = P;
+  a.ns_id = no_speech_id >= 0 ? no_speech_id : -1; a.ns_pos = no_speech_pos; a.out_ns = c->score_out.no_speech;
 
   // ---- positions 0 .. seq_len-2 in rows-mode launches with logits (B streams x L consecutive positions), each scored at once ----
   const int key_bound_before = c->dec_key_bound;
   const int L = std::max(1, cap / B);
+  DecodeOpts rows; rows.rows_streams = B; rows.record_alignment = false;
   for (int p0 = 0; p0 < n_pos; p0 += L) {
     const int l = std::min(L, n_pos - p0);
     const size_t off = (size_t)p0 * B;
-    c->dec_key_bound = std::min(((p0 + l + 63) / 64) * 64, ((P + 63) / 64) * 64);
-    r = decode_core(c, l * B, st, B, c->row_ids + off, true, true, /*record_alignment=*/false);
+    c->dec_key_bound = key_bound(p0 + l, P);
+    rows.ids = c->row_ids + off;
+    r = decode_core(c, l * B, st, rows);
     if (r != TW_OK) { c->dec_key_bound = key_bound_before; return r; }
     a.s.B = l * B; a.s.rows_streams = B; a.s.row_pos0 = p0; a.s.row_lastts = c->row_lastts + off;
     HIPCHK(c, launch_score_rows(a, st));
     HIPCHK(c, launch_advance(c->stt, l, st));
   }
   c->dec_key_bound = key_bound_before;
-  HIPCHK(c, hipMemcpyAsync(c->h_score, c->score_out, sizeof(float) * (2 * plane + c->Bmax), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_score.masked, c->score_out.masked, sizeof(float) * c->score_floats, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
 
   // ---- [B, seq_len]: 0 for the prompt and for the padding behind a row's first <eos> (the <eos> itself is scored) ----
@@ -1812,10 +1837,10 @@ int tw_score_tokens(tw_ctx* c, int32_t B, const int32_t* ids, int32_t ld, int32_
         if (ids[(size_t)b * ld + i] == o->eos_id) { last = i; break; }
     for (int i = 0; i < seq_len; ++i) {
       const bool scored = i >= n_prompt && i <= last;
-      if (out_logprob) out_logprob[(size_t)b * seq_len + i] = scored ? c->h_score[(size_t)b * P + i] : 0.f;
-      if (out_logprob_raw) out_logprob_raw[(size_t)b * seq_len + i] = scored ? c->h_score[plane + (size_t)b * P + i] : 0.f;
+      if (out_logprob) out_logprob[(size_t)b * seq_len + i] = scored ? c->h_score.masked[(size_t)b * P + i] : 0.f;
+      if (out_logprob_raw) out_logprob_raw[(size_t)b * seq_len + i] = scored ? c->h_score.raw[(size_t)b * P + i] : 0.f;
     }
-    if (no_speech_id >= 0 && out_no_speech) out_no_speech[b] = c->h_score[2 * plane + b];
+    if (no_speech_id >= 0 && out_no_speech) out_no_speech[b] = c->h_score.no_speech[b];
   }
   return TW_OK;
 }

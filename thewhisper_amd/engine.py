@@ -159,6 +159,17 @@ def _repeat_opts(rows, penalty_ignore: int):
     return ro
 
 
+def _bias_opts(packed):
+    """``tw_bias_opts`` over the arrays of ``pack_sequence_bias`` (which the caller keeps alive); None for None."""
+    if packed is None:
+        return None
+    bo = _cabi.tw_bias_opts()
+    bo.n_seq = int(packed["bias"].size)
+    bo.row_off, bo.seq_off, bo.tokens = (packed[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("row_off", "seq_off", "tokens"))
+    bo.bias = packed["bias"].ctypes.data_as(C.POINTER(C.c_float))
+    return bo
+
+
 class WhisperEngine:
     """One MI355X context: weights + workspace + KV arenas for up to ``max_batch`` concurrent streams
     of ``T`` encoder frames (= 50 x chunk seconds)."""
@@ -478,6 +489,20 @@ class WhisperEngine:
                 return C.c_void_p(ds)
         return self._sp()
 
+    def _generate(self, name: str, prompt: np.ndarray, o, extras, max_length: int, pad_id: int, sp) -> Dict[str, np.ndarray]:
+        """One call of the generate family: ``name(ctx, B, prompt, n0, &o, *extras, out, &out_len, stream)``, which every member is;
+        ``extras``: the arguments between, ready for ctypes."""
+        B, n0 = prompt.shape
+        out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
+        out_len = C.c_int32(0)
+        i32p = C.POINTER(C.c_int32)
+        rc = getattr(self.lib, name)(self.ctx, B, prompt.ctypes.data_as(i32p), n0, C.byref(o), *extras, out.ctypes.data_as(i32p),
+                                     C.byref(out_len), sp)
+        self._chk(rc, name)
+        self._release_held()   # the call returns after synchronising its stream, which is ordered after the encoder stage
+        L = int(out_len.value)
+        return {"sequences": out[:, :L].astype(np.int64), "length": L}
+
     def generate_greedy(
         self,
         prompt: np.ndarray,
@@ -516,7 +541,7 @@ class WhisperEngine:
         ``n_draft``: the last ``n_draft`` tokens of every prompt row are GUESSES of the output (tw_greedy_opts::n_draft): verified in
         batched launches, the call returns what it returns without them; ``draft`` in the result says how many were confirmed."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
-        B, n0 = prompt.shape
+        B = prompt.shape[0]
         pads = ragged_n_pad(n_pad, B, n_forced, n_draft, sequence_bias is not None or sequence_bias_rows is not None)
         if sequence_bias is not None and sequence_bias_rows is not None:
             raise ValueError("sequence_bias (every row) and sequence_bias_rows (per row): give one of the two")
@@ -530,44 +555,20 @@ class WhisperEngine:
             raise ValueError("n_pad does not go with repetition_penalty / no_repeat_ngram_size (the ragged call takes no repeat options)")
         o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
                                      min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
-        out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
-        out_len = C.c_int32(0)
         # (calls with a forced prefix stay on the caller's stream: their batched prefill - launches of up to 64 rows - wants the whole
         #  chip; measured on the reuse path's short calls: 16.1 ms per tick there, 19.9 on the 160-CU stream)
         sp = self._loop_stream() if int(n_forced) == 0 and int(n_draft) == 0 else self._sp()
+        bo = _bias_opts(packed)
         if pads is not None:
-            rc = self.lib.tw_generate_greedy_ragged(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
-                                                    pads.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-            self._chk(rc, "tw_generate_greedy_ragged")
+            name, extras = "tw_generate_greedy_ragged", (pads.ctypes.data_as(C.POINTER(C.c_int32)),)
         elif repeat is not None:
-            bo = None
-            if packed is not None:
-                bo = _cabi.tw_bias_opts()
-                bo.n_seq = int(packed["bias"].size)
-                bo.row_off, bo.seq_off, bo.tokens = (packed[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("row_off", "seq_off", "tokens"))
-                bo.bias = packed["bias"].ctypes.data_as(C.POINTER(C.c_float))
             ro = _repeat_opts(repeat, penalty_ignore)
-            rc = self.lib.tw_generate_greedy_repeat(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
-                                                    C.byref(bo) if bo is not None else None, C.byref(ro),
-                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-            self._chk(rc, "tw_generate_greedy_repeat")
-        elif packed is None:
-            rc = self.lib.tw_generate_greedy(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o),
-                                             out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len),
-                                             sp)
-            self._chk(rc, "tw_generate_greedy")
+            name, extras = "tw_generate_greedy_repeat", (C.byref(bo) if bo is not None else None, C.byref(ro))
+        elif bo is None:
+            name, extras = "tw_generate_greedy", ()
         else:
-            bo = _cabi.tw_bias_opts()
-            bo.n_seq = int(packed["bias"].size)
-            bo.row_off, bo.seq_off, bo.tokens = (packed[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("row_off", "seq_off", "tokens"))
-            bo.bias = packed["bias"].ctypes.data_as(C.POINTER(C.c_float))
-            rc = self.lib.tw_generate_greedy_biased(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(bo),
-                                                    out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-            self._chk(rc, "tw_generate_greedy_biased")
-        self._release_held()   # the call returns after synchronising its stream, which is ordered after the encoder stage
-        L = int(out_len.value)
-        res = {"sequences": out[:, :L].astype(np.int64), "length": L}
+            name, extras = "tw_generate_greedy_biased", (C.byref(bo),)
+        res = self._generate(name, prompt, o, extras, max_length, pad_id, sp)
         if int(n_draft) > 0:
             v = [C.c_int32(0) for _ in range(4)]
             self._chk(self.lib.tw_last_draft(self.ctx, *[C.byref(x) for x in v]), "tw_last_draft")
@@ -622,7 +623,7 @@ class WhisperEngine:
         from the top-k ids and, of those, the smallest set of the largest whose mass reaches ``top_p`` (tw_generate_sample_filtered,
         where the rule is stated; ``top_k=50`` is HF's candidate set).  With both off the call is the unfiltered one."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
-        B, n0 = prompt.shape
+        B = prompt.shape[0]
         filt = filter_rows(top_k, top_p, B)
         rows = [None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dt).reshape(-1), (B,)))
                 for x, dt in ((temperature, np.float32), (seed, np.uint64), (offset, np.uint64))]
@@ -632,23 +633,13 @@ class WhisperEngine:
         so.offset = rows[2].ctypes.data_as(C.POINTER(C.c_uint64)) if rows[2] is not None else None
         o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
                                      min_new_tokens, max_new_tokens, max_length, want_alignment, n_forced, n_draft)
-        out = np.full((B, int(max_length)), pad_id, dtype=np.int32)
-        out_len = C.c_int32(0)
         sp = self._loop_stream()     # the decode stream, as the plain greedy call
         if filt is None:
-            rc = self.lib.tw_generate_sample(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
-                                             out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-            self._chk(rc, "tw_generate_sample")
-        else:
-            fo = _cabi.tw_filter_opts()
-            fo.top_k = filt[0].ctypes.data_as(C.POINTER(C.c_int32))
-            fo.top_p = filt[1].ctypes.data_as(C.POINTER(C.c_float))
-            rc = self.lib.tw_generate_sample_filtered(self.ctx, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), n0, C.byref(o), C.byref(so),
-                                                      C.byref(fo), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out_len), sp)
-            self._chk(rc, "tw_generate_sample_filtered")
-        self._release_held()
-        L = int(out_len.value)
-        return {"sequences": out[:, :L].astype(np.int64), "length": L}
+            return self._generate("tw_generate_sample", prompt, o, (C.byref(so),), max_length, pad_id, sp)
+        fo = _cabi.tw_filter_opts()
+        fo.top_k = filt[0].ctypes.data_as(C.POINTER(C.c_int32))
+        fo.top_p = filt[1].ctypes.data_as(C.POINTER(C.c_float))
+        return self._generate("tw_generate_sample_filtered", prompt, o, (C.byref(so), C.byref(fo)), max_length, pad_id, sp)
 
     # ---- scores of finished sequences --------------------------------------------------------
     def score_tokens(

@@ -399,6 +399,57 @@ int tw_generate_sample_filtered(tw_ctx* ctx, int32_t B, const int32_t* prompt_ho
                                 const tw_sample_opts* sopts, const tw_filter_opts* fopts, int32_t* out_ids_host,
                                 int32_t* out_len_host, void* stream);
 
+/* Beam search on the device with the n-best list.  Replaces: GenerationMixin._beam_search (HF:generation/utils.py:2976-3560) for
+ * num_beams = K in 2 .. 8 with Whisper's logits processors, as WhisperGenerationMixin.generate_with_fallback invokes it for
+ * generate_kwargs={"num_beams": K} (HF:models/whisper/generation_whisper.py:1027).
+ *
+ * THE RULE.  n_clips clips, K beams each, n0 = n_prompt, max_len = min(max_length, n0 + max_new_tokens, target_positions); all scores
+ * float32.  Per clip: run_seq[K] = the prompt K times, run_score = [0, -1e9, ..], fin_seq[K] = the prompt then pad_id,
+ * fin_score[K] = -1e9, fin_flag[K] = false, open = true, cur = n0.  One step consumes position cur - 1 of every beam:
+ *   1. x_k = beam k's float32 logits; lp_k[v] = x_k[v] - m_k - log(sum_v exp(x_k[v] - m_k)) over all V ids, m_k = max x_k (HF's
+ *      log_softmax, before any processor).
+ *   2. The processors of `opts` on lp_k with history run_seq[k] and begin index n0: exactly tw_generate_greedy's mask, "timestamp mass
+ *      beats every text token" included.  A masked id is -inf, every other id keeps its bits (no renormalisation).
+ *   3. a[k V + v] = lp_k[v] + run_score[k] (one float32 add).  Candidates j = 0 .. 2K-1: the 2K largest a, descending, the lower flat
+ *      index first on equal values (torch.topk leaves ties open): score s_j, source beam b_j, id t_j, sequence run_seq[b_j] + [t_j].
+ *   4. hit_j = t_j == eos_id || cur + 1 >= max_len.
+ *   5. r_j = hit_j ? s_j + (-1e9f) : s_j.  The K largest r_j (descending, lower j first) become run_seq / run_score; their b_j are
+ *      beam_idx[K].
+ *   6. f_j = s_j / pen[cur + 1 - n0], pen[g] = (float)pow((double)g, (double)length_penalty), one correctly rounded float32 division;
+ *      then -1e9f is added once for each of: early_stopping and all of fin_flag; !open; !(j < K && hit_j).  The new finished set is the
+ *      K largest of [fin_score[0 .. K-1], f_0 .. f_{2K-1}] (descending, lower index of that concatenation first); a chosen candidate's
+ *      flag is j < K && hit_j.
+ *   7. Every self-attention cache row of beam k becomes that of beam beam_idx[k]; cur += 1.
+ *   8. open = open && any_k(run_score[0] / pen[cur - n0] > (fin_flag[k] ? min(fin_score) : -1e9f)).
+ *   9. The clip is over - its state frozen - when !open, or early_stopping and all of fin_flag, or every hit_j held.
+ * fin_seq[0] / fin_score[0] is the best hypothesis, fin_seq[0 .. K-1] the n-best list in descending score; an entry whose score is
+ * <= -1e9 is a placeholder.  Deviation: where float32 rounding maps two different logits of one beam onto the same accumulated score,
+ * the larger logit is listed first (the rule says the lower id); real ties between equal logits follow the rule.
+ *
+ * Rows: beam k of clip c is row (slot) k * n_clips + c.  The call copies every clip's cross K / V to the slots of its beams >= 1 and
+ * never writes slots 0 .. n_clips-1: afterwards the context holds the n_clips clips as tw_cross_kv left them (tw_score_tokens and
+ * further tw_generate_* calls for them need no re-encoding); whatever slots n_clips .. n_clips * K - 1 held is gone.  A step is the
+ * ordinary decoder pass over n_clips * K rows plus four short launches (slice partials, one workgroup per clip for steps 3-6 / 8 / 9,
+ * the in-place cache reorder, the position); steps are not captured, so use_graph contexts run the same launches.  A clip's result
+ * does not depend on its slot or on its batch-mates.  tw_last_timings[3] and the step count are filled; the state tables live in
+ * context-owned device memory, allocated by the first beam call of a context (a sibling owns its own) and freed by tw_destroy.
+ *
+ * out_ids_host [n_clips, max_length]: the best hypotheses.  out_len_host: int32 [2], ALWAYS two entries (unlike the other tw_generate_*
+ * calls): [0] the common length of the best hypotheses (n0 + the longest generated part), [1] the common length of all K hypotheses
+ * of all clips, written whether or not the n-best list is asked for.  out_score_host [n_clips] (may be NULL); out_nbest_ids_host
+ * [n_clips, K, max_length] (may be NULL) and out_nbest_score_host [n_clips, K] (may be NULL).  Everything behind a hypothesis's end
+ * is pad_id.
+ * TW_ESTATE: tw_encode + tw_cross_kv did not fill n_clips slots.  TW_EINVAL, before any work is enqueued (the context stays usable):
+ * num_beams outside 2 .. 8, n_clips * num_beams above max_batch or above 64, a NaN or infinite length_penalty, early_stopping outside
+ * {0, 1}, want_alignment / n_forced / n_draft set, a TW_BF16_MXFP8 / TW_BF16_W8A16 context, a context whose target_positions exceed
+ * 512 (the histories a workgroup holds), tw_generate_greedy's own refusals. */
+typedef struct tw_beam_opts { int32_t num_beams; float length_penalty; int32_t early_stopping; } tw_beam_opts;   /* 2..8, finite, 0 | 1 */
+int tw_generate_beam(tw_ctx* ctx, int32_t n_clips, const int32_t* prompt_host /*[n_clips, n_prompt]*/, int32_t n_prompt,
+                     const tw_greedy_opts* opts, const tw_beam_opts* bopts,
+                     int32_t* out_ids_host /*[n_clips, max_length] best*/, int32_t* out_len_host /*[2]*/, float* out_score_host /*[n_clips], may be NULL*/,
+                     int32_t* out_nbest_ids_host /*[n_clips, K, max_length], may be NULL*/, float* out_nbest_score_host /*[n_clips, K], may be NULL*/,
+                     void* stream);
+
 /* Of the most recent tw_generate_greedy with n_draft > 0 (all streams together): draft tokens offered, draft tokens confirmed, rows-mode
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */
 int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds);

@@ -56,6 +56,10 @@ class tw_repeat_opts(C.Structure):
     _fields_ = [("penalty", C.POINTER(C.c_float)), ("no_repeat_ngram", C.POINTER(C.c_int32)), ("penalty_ignore", C.c_int32)]
 
 
+class tw_beam_opts(C.Structure):
+    _fields_ = [("num_beams", C.c_int32), ("length_penalty", C.c_float), ("early_stopping", C.c_int32)]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -89,6 +93,9 @@ SYMBOLS = [
     ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),
                                               C.POINTER(tw_sample_opts), C.POINTER(tw_filter_opts), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), _P]),
+    ("tw_generate_beam", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_beam_opts),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_float), _P]),
     ("tw_last_draft", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("tw_score_tokens", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(tw_greedy_opts),
                                   C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),

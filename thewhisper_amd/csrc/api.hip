@@ -135,6 +135,9 @@ struct tw_ctx {
   // tw_generate_greedy_ragged: the per-stream padding lengths [64] the ragged kernels read (tw_common.h: tw_row_pos) and their pinned
   // staging, allocated by the first ragged call of the context
   int* n_pad_tab = nullptr; int* h_n_pad = nullptr;
+  // tw_generate_beam: the state tables of the call (BeamTab: scores, finished set, flags, penalty table, finished hypotheses), their
+  // pinned image (up with the initial state, down with the result) and the slice partials, allocated by the first beam call of the context
+  int* beam_tab = nullptr; int* h_beam = nullptr; BeamPartial* beam_parts = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
   size_t row_ids_cap = 0;
   // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
@@ -293,7 +296,7 @@ int tw_destroy(tw_ctx* c) {
   (void)hipDeviceSynchronize();
   for (auto& kv : c->step_graphs) (void)hipGraphExecDestroy(kv.second);
   for (void* p : c->allocs) (void)hipFree(p);
-  void* const pinned[] = {c->h_pinned, c->h_stage, c->h_seq, c->h_rows.tok, c->h_verify, c->h_score.masked, c->h_bias, c->h_repeat, c->h_n_pad};
+  void* const pinned[] = {c->h_pinned, c->h_stage, c->h_seq, c->h_rows.tok, c->h_verify, c->h_score.masked, c->h_bias, c->h_repeat, c->h_n_pad, c->h_beam};
   for (void* p : pinned)
     if (p) (void)hipHostFree(p);
   for (int i = 0; i < 5; ++i) {
@@ -1717,6 +1720,159 @@ int tw_generate_greedy_ragged(tw_ctx* c, int32_t B, const int32_t* prompt, int32
     return fail(c, TW_EINVAL, "%s: n_forced %d / n_draft %d: forced and draft tokens do not go with padded rows", fn, o->n_forced, o->n_draft);
   // nothing padded: the call IS tw_generate_greedy, launch for launch
   return generate_loop(c, B, prompt, n_prompt, o, nullptr, nullptr, nullptr, out_ids, out_len, stream, padded ? n_pad : nullptr);
+}
+
+// Word offsets of the beam state tables inside tw_ctx::beam_tab / h_beam (tw_common.h: BeamArgs); rows are beam-major, k * n_clips + c
+namespace {
+constexpr size_t kBeamRunScore = 0, kBeamFinScore = 64, kBeamFinFlag = 128, kBeamFinLen = 192, kBeamOpen = 256, kBeamDone = 320,
+                 kBeamIdx = 384, kBeamPen = 448 /* 576 words */, kBeamFinSeq = 1024;
+size_t beam_tab_words(const tw_ctx* c) { return kBeamFinSeq + (size_t)64 * c->P; }
+}  // namespace
+
+// The beam loop (THE RULE: include/thewhisper.h).  Not captured: a beam step is issued launch by launch in use_graph contexts too, so
+// the two settings run the same launches, and the captured greedy step graphs of the context are left alone.
+int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_beam_opts* bo,
+                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_nbest_ids, float* out_nbest_score, void* stream) {
+  const char* fn = "tw_generate_beam";
+  if (!c || !prompt || !o || !bo || !out_ids || !out_len) return fail(c, TW_EINVAL, "%s: null argument", fn);
+  TW_ON_DEVICE(c);
+  const int K = bo->num_beams;
+  if (K < 2 || K > kBeamMax) return fail(c, TW_EINVAL, "%s: num_beams %d outside 2..%d", fn, K, kBeamMax);
+  if (n < 1 || (long long)n * K > c->Bmax || n * K > 64)
+    return fail(c, TW_EINVAL, "%s: %d clips x %d beams exceed max_batch %d (or 64 rows)", fn, n, K, c->Bmax);
+  if (!std::isfinite(bo->length_penalty)) return fail(c, TW_EINVAL, "%s: length_penalty is NaN or infinite", fn);
+  if (bo->early_stopping != 0 && bo->early_stopping != 1) return fail(c, TW_EINVAL, "%s: early_stopping %d outside {0, 1}", fn, bo->early_stopping);
+  if (o->want_alignment || o->n_forced != 0 || o->n_draft != 0)
+    return fail(c, TW_EINVAL, "%s: want_alignment, n_forced and n_draft do not go with beams", fn);
+  if (c->w8) return fail(c, TW_EINVAL, "%s: fp8 contexts are not supported", fn);
+  if (c->P > kBeamSeqMax) return fail(c, TW_EINVAL, "%s: target_positions %d above %d", fn, c->P, kBeamSeqMax);
+  if (n > c->cross_B) return fail(c, TW_ESTATE, "%s: %d clips but cross K/V holds %d", fn, n, c->cross_B);
+  if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);
+  int r = check_processor_opts(c, o);
+  if (r != TW_OK) return r;
+  int max_len = n_prompt + o->max_new_tokens;
+  if (o->max_length > 0 && o->max_length < max_len) max_len = o->max_length;
+  if (max_len > c->P) max_len = c->P;
+  if (max_len <= n_prompt) return fail(c, TW_EINVAL, "nothing to generate (max_len %d <= n_prompt %d)", max_len, n_prompt);
+  const int out_ld = o->max_length > 0 ? o->max_length : max_len;
+  for (size_t i = 0; i < (size_t)n * n_prompt; ++i)
+    if (prompt[i] < 0 || prompt[i] >= c->V) return fail(c, TW_EINVAL, "prompt token %d out of range", prompt[i]);
+  hipStream_t st = pick_stream(c, stream);
+  const int P = c->P, rows = n * K;
+  const size_t words = beam_tab_words(c);
+  if (!c->beam_tab) ALLOC(c, c->beam_tab, sizeof(int) * words, true);
+  if (!c->beam_parts) ALLOC(c, c->beam_parts, sizeof(BeamPartial) * 64 * 32, true);
+  if (!c->h_beam) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_beam), sizeof(int) * words));
+
+  // ---- initial state, staged in pinned memory (not touched again before the synchronisation at the end of the call) ----
+  GenStage& hs = *c->h_stage;
+  int* hseq = c->h_seq;   // [rows][P]
+  int* hb = c->h_beam;
+  float* hbf = reinterpret_cast<float*>(hb);
+  memset(hb, 0, sizeof(int) * kBeamFinSeq);
+  for (int k = 0; k < K; ++k)
+    for (int b = 0; b < n; ++b) {
+      const int row = k * n + b;
+      for (int i = 0; i < P; ++i) hseq[(size_t)row * P + i] = hb[kBeamFinSeq + (size_t)row * P + i] = i < n_prompt ? prompt[(size_t)b * n_prompt + i] : o->pad_id;
+      hs.first[row] = prompt[(size_t)b * n_prompt];
+      hs.finished0[row] = 0;
+      hs.last_ts0[row] = -1;
+      hbf[kBeamRunScore + row] = k == 0 ? 0.f : -1e9f;
+      hbf[kBeamFinScore + row] = -1e9f;
+      hb[kBeamFinLen + row] = n_prompt;
+      hb[kBeamIdx + row] = k;
+      hb[kBeamOpen + b] = 1;
+    }
+  for (int g = 0; g <= P; ++g) hbf[kBeamPen + g] = (float)std::pow((double)g, (double)bo->length_penalty);
+  HIPCHK(c, hipMemcpyAsync(c->beam_tab, hb, sizeof(int) * (kBeamFinSeq + (size_t)rows * P), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->seq, hseq, sizeof(int) * (size_t)rows * P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->cur_ids, hs.first, sizeof(int) * rows, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->finished, hs.finished0, sizeof(int) * rows, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->last_ts, hs.last_ts0, sizeof(int) * rows, hipMemcpyHostToDevice, st));
+  r = upload_suppress_lists(c, o, c->begin_suppress_dev, c->suppress_dev, c->suppress_bits, st);
+  if (r != TW_OK) return r;
+  hs.state = DecState{0, n_prompt, max_len - 1, rows};
+  HIPCHK(c, hipMemcpyAsync(c->stt, &hs.state, sizeof(DecState), hipMemcpyHostToDevice, st));
+  // every clip's cross K / V for its beams 1 .. K-1: slots n .. n K - 1 (the clips' own slots are only read)
+  const size_t ckv_e = c->esz;
+  HIPCHK(c, launch_beam_cross_copy(c->cross_k, c->cross_v, (long long)((size_t)c->Bmax * c->Tp * c->d * ckv_e),
+                                   (long long)((size_t)c->Tp * c->d * ckv_e), c->Ld, n, K, st));
+  c->cross_B = n;   // the slots behind the clips now hold their copies
+
+  BeamArgs ba{};
+  SamplerArgs& sa = ba.s;
+  sa.logits = c->logits; sa.V = c->V; sa.B = rows; sa.seq = c->seq; sa.seq_ld = P; sa.cur_ids = c->cur_ids;
+  sa.finished = c->finished; sa.last_ts = c->last_ts; sa.stt = c->stt;
+  sa.eos = o->eos_id; sa.pad = o->pad_id; sa.min_new = o->min_new_tokens; sa.timestamps = o->timestamps;
+  sa.no_ts_id = o->no_timestamps_id; sa.max_initial_ts = o->max_initial_timestamp_index;
+  sa.begin_suppress = c->begin_suppress_dev; sa.n_begin_suppress = o->n_begin_suppress;
+  sa.suppress_bits = c->suppress_bits; sa.partials = c->sampler_partials;
+  ba.n_clips = n; ba.K = K; ba.early = bo->early_stopping; ba.max_len = max_len; ba.parts = c->beam_parts;
+  float* tf = reinterpret_cast<float*>(c->beam_tab);
+  ba.run_score = tf + kBeamRunScore; ba.fin_score = tf + kBeamFinScore; ba.pen = tf + kBeamPen;
+  ba.fin_flag = c->beam_tab + kBeamFinFlag; ba.fin_len = c->beam_tab + kBeamFinLen; ba.open = c->beam_tab + kBeamOpen;
+  ba.done = c->beam_tab + kBeamDone; ba.beam_idx = c->beam_tab + kBeamIdx; ba.fin_seq = c->beam_tab + kBeamFinSeq;
+
+  const int Pp = (P + 63) / 64 * 64;
+  DecodeOpts step; step.record_alignment = false;   // embeds from cur_ids; the alignment rows of an earlier call stay as they are
+  tic(c, 3, st);
+  constexpr int LAG = 2;
+  int steps = 0;
+  bool all_done = false;
+  for (int s = 0; s < max_len - 1 && !all_done; ++s) {
+    const bool in_prompt = s + 1 < n_prompt;   // the step only appends the next prompt token: no logits, nothing to reorder
+    const int kb = key_bound(s + 1, max_len);
+    c->dec_key_bound = kb;
+    step.logits = !in_prompt;
+    r = decode_core(c, rows, st, step);
+    if (r != TW_OK) return r;
+    HIPCHK(c, launch_beam_step(ba, in_prompt, st));
+    if (!in_prompt)
+      HIPCHK(c, launch_beam_reorder(c->dtype, c->self_k, c->self_v, (long long)c->Bmax * Pp * c->d, (long long)Pp * c->d, (long long)Pp * 64,
+                                    c->Ld, c->H, kb, ba, st));
+    HIPCHK(c, launch_advance(c->stt, 1, st));
+    ++steps;
+    const int slot = s % 8;
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned->finished[slot], ba.done, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipEventRecord(c->ring_ev[slot], st));
+    if (s >= LAG) {
+      const int ps = (s - LAG) % 8;
+      HIPCHK(c, hipEventSynchronize(c->ring_ev[ps]));
+      bool done = true;
+      for (int b = 0; b < n; ++b) done &= (c->h_pinned->finished[ps][b] != 0);
+      all_done = done;
+    }
+  }
+  toc(c, 3, st);
+  c->last_steps = steps;
+  HIPCHK(c, hipMemcpyAsync(hb, c->beam_tab, sizeof(int) * (kBeamFinSeq + (size_t)rows * P), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+
+  // ---- results: hypothesis i of clip b is finished row i * n + b; everything behind its end is pad_id ----
+  int L_best = n_prompt, L_all = n_prompt;
+  for (int b = 0; b < n; ++b)
+    for (int k = 0; k < K; ++k) {
+      const int len = std::min(std::max(hb[kBeamFinLen + k * n + b], n_prompt), max_len);
+      if (k == 0) L_best = std::max(L_best, len);
+      L_all = std::max(L_all, len);
+    }
+  auto emit = [&](int row, int32_t* dst) {
+    const int len = std::min(std::max(hb[kBeamFinLen + row], n_prompt), max_len);
+    for (int i = 0; i < out_ld; ++i) dst[i] = i < len ? hb[kBeamFinSeq + (size_t)row * P + i] : o->pad_id;
+  };
+  for (int b = 0; b < n; ++b) {
+    emit(b, out_ids + (size_t)b * out_ld);
+    if (out_score) out_score[b] = hbf[kBeamFinScore + b];
+    for (int k = 0; k < K; ++k) {
+      if (out_nbest_ids) emit(k * n + b, out_nbest_ids + ((size_t)b * K + k) * out_ld);
+      if (out_nbest_score) out_nbest_score[(size_t)b * K + k] = hbf[kBeamFinScore + k * n + b];
+    }
+  }
+  out_len[0] = L_best;   // (two entries, always: the header says so)
+  out_len[1] = L_all;
+  c->last_seq_len = L_best;
+  c->last_n_prompt = n_prompt;
+  return TW_OK;
 }
 
 // tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter

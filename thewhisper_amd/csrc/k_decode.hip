@@ -1512,8 +1512,8 @@ __device__ __forceinline__ void embed_row(const SamplerArgs& a, int b, int id, i
 }
 
 // Merge of the vocabulary slices of row b by one wavefront, in every lane: the row's best text and timestamp token over the unmasked
-// logits and the "timestamp mass beats every text token" decision (log-sum-exp merge of the slices' timestamp sums).  P: SamplerPartial
-// or SamplePartial, which begin with the same five fields.
+// logits and the "timestamp mass beats every text token" decision (log-sum-exp merge of the slices' timestamp sums).  P: SamplerPartial,
+// SamplePartial or BeamPartial, which begin with the same five fields (only those are read).
 struct SliceMerge { MaxIdx bt, bs; bool force_ts; };
 template <typename P>
 __device__ __forceinline__ SliceMerge merge_slices(const SamplerArgs& a, const P* parts, int b, int lane) {
@@ -2210,6 +2210,331 @@ __global__ __launch_bounds__(kRepeatMaxHist) void repeat_logits_kernel(float* lo
 
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
+// Beam search (tw_generate_beam, api.hip; THE RULE is in include/thewhisper.h; the tables are BeamArgs', tw_common.h): a step is the
+// ordinary decoder pass over n_clips x K rows, then
+//  * beam_part_kernel: the slicing, the register-resident slice and the vector / scalar paths of sampler_part_kernel.  Per (row, slice):
+//    (max, sum exp(x - max)) over ALL ids (the row's log-softmax is taken before any processor), the greedy partials of the masked
+//    logits (what merge_slices decides the mass rule on), and the slice's 2K best unmasked text ids and 2K best unmasked timestamp ids
+//    by 2K rounds of "the best one strictly behind the previous one" in the order (logit descending, id ascending).  Within a row the
+//    accumulated score is a non-decreasing function of the logit, so the row's 2K best are among them; where the float32 rounding of
+//    lp maps two different logits of a row onto one score, the larger logit comes first here (the rule says: the lower id).
+//  * beam_finish_kernel: one workgroup per clip, wavefront k merges the slices of beam k (fixed butterfly order), turns the listed
+//    logits into accumulated scores and extracts the row's 2K best by the same rounds; the K x 2K survivors are ranked by counting
+//    (score descending, flat index k V + v ascending); one thread does steps 4-6, 8 and 9 of the rule; all threads then write the
+//    gathered histories from the copies the workgroup took into LDS at its start.
+//  * beam_reorder_kernel: the self-attention caches follow beam_idx, in place (see there).
+// No atomics, no reduction whose order depends on the launch: a clip's result does not depend on its slot or its batch-mates.
+
+// strictly behind `p` in the order (value descending, id ascending)
+__device__ __forceinline__ bool beam_behind(float v, int i, MaxIdx p) { return v < p.v || (v == p.v && i > p.i); }
+
+template <int BEAM_NS, int BEAM_IT>
+__global__ __launch_bounds__(256) void beam_part_kernel(BeamArgs ba) {
+  __shared__ MaxIdx red_text[2][4], red_ts[2][4];
+  __shared__ float red_sum[4], red_raw[2][4];
+  const SamplerArgs& a = ba.s;
+  const int part = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* lg = a.logits + (long long)b * a.V;
+  const VocabSlice sl = vocab_slice<BEAM_NS, BEAM_IT>(a.V, part);
+  const int v0 = sl.v0, v1 = sl.v1;
+  float s0[BEAM_IT], s1[BEAM_IT];
+  unsigned wb[BEAM_IT];
+  slice_load(a, lg, sl, tid, s0, s1, wb);
+  __builtin_amdgcn_sched_barrier(0);
+  const SamplerMask k = sampler_mask(a, b);
+  if (k.in_prompt || ba.done[b % ba.n_clips] != 0) return;   // (workgroup-uniform) nothing is selected for this row
+  // ---- the slice's part of the row's log-softmax: over every id, before the mask ----
+  float rm = -INFINITY;
+  if (sl.vec_ok) {
+#pragma unroll
+    for (int it = 0; it < BEAM_IT; ++it)
+      if (v0 + (it * 256 + tid) * 2 < v1) rm = fmaxf(rm, fmaxf(s0[it], s1[it]));
+  } else {
+    for (int v = v0 + tid; v < v1; v += 256) rm = fmaxf(rm, lg[v]);
+  }
+  rm = wave_max(rm);
+  if (lane == 0) red_raw[0][wave] = rm;
+  __syncthreads();
+  rm = fmaxf(fmaxf(red_raw[0][0], red_raw[0][1]), fmaxf(red_raw[0][2], red_raw[0][3]));
+  float rs = 0.f;
+  if (sl.vec_ok) {
+#pragma unroll
+    for (int it = 0; it < BEAM_IT; ++it)
+      if (v0 + (it * 256 + tid) * 2 < v1) { rs += expf(s0[it] - rm); rs += expf(s1[it] - rm); }
+  } else {
+    for (int v = v0 + tid; v < v1; v += 256) rs += expf(lg[v] - rm);
+  }
+  rs = wave_sum(rs);
+  if (lane == 0) red_raw[1][wave] = rs;
+  __syncthreads();
+  rs = ((red_raw[1][0] + red_raw[1][1]) + red_raw[1][2]) + red_raw[1][3];
+  // ---- the mask, as sampler_part_kernel applies it ----
+  if (sl.vec_ok) {
+#pragma unroll
+    for (int it = 0; it < BEAM_IT; ++it) {
+      const int v = v0 + (it * 256 + tid) * 2;
+      const bool in = v < v1;
+      const int vc = in ? v : 0;
+      s0[it] = (in && !sampler_masked_at(a, k, vc, wb[it])) ? s0[it] : -INFINITY;
+      s1[it] = (in && !sampler_masked_at(a, k, vc + 1, wb[it])) ? s1[it] : -INFINITY;
+    }
+  }
+  // ---- 2K rounds: the best text and the best timestamp id strictly behind the previous round's ----
+  BeamPartial* o = ba.parts + b * SAMPLER_NS_MAX + part;
+  MaxIdx pt{INFINITY, -1}, ps{INFINITY, -1}, first_t{-INFINITY, 0x7fffffff}, first_s{-INFINITY, 0x7fffffff};
+  const int n_round = 2 * ba.K;
+  for (int r = 0; r < n_round; ++r) {
+    MaxIdx bt{-INFINITY, 0x7fffffff}, bs{-INFINITY, 0x7fffffff};
+    auto take = [&](float x, int v) {
+      if (v < k.ts_begin) { if (beam_behind(x, v, pt)) bt = better(bt, MaxIdx{x, v}); }
+      else { if (beam_behind(x, v, ps)) bs = better(bs, MaxIdx{x, v}); }
+    };
+    if (sl.vec_ok) {
+#pragma unroll
+      for (int it = 0; it < BEAM_IT; ++it) {
+        const int v = v0 + (it * 256 + tid) * 2;
+        if (v < v1) { take(s0[it], v); take(s1[it], v + 1); }
+      }
+    } else {
+      for (int v = v0 + tid; v < v1; v += 256) take(sampler_masked_at(a, k, v, a.suppress_bits[v >> 5]) ? -INFINITY : lg[v], v);
+    }
+    bt = wave_best(bt);
+    bs = wave_best(bs);
+    if (lane == 0) { red_text[r & 1][wave] = bt; red_ts[r & 1][wave] = bs; }
+    __syncthreads();
+    bt = red_text[r & 1][0];
+    bs = red_ts[r & 1][0];
+    for (int w = 1; w < 4; ++w) { bt = better(bt, red_text[r & 1][w]); bs = better(bs, red_ts[r & 1][w]); }
+    if (!(bt.v > -INFINITY)) bt.i = 0x7fffffff;   // the list is exhausted
+    if (!(bs.v > -INFINITY)) bs.i = 0x7fffffff;
+    if (tid == 0) { o->tx_v[r] = bt.v; o->tx_i[r] = bt.i; o->ts_v[r] = bs.v; o->ts_i[r] = bs.i; }
+    if (r == 0) { first_t = bt; first_s = bs; }
+    pt = bt;
+    ps = bs;
+  }
+  const float sum = slice_ts_sum(a, k, sl, lg, tid, s0, s1, first_s.v, red_sum);
+  if (tid == 0) {
+    o->bt_v = first_t.v; o->bt_i = first_t.i; o->bs_v = first_s.v; o->bs_i = first_s.i;
+    o->sum = sum; o->raw_m = rm; o->raw_s = rs; o->pad_ = 0;
+  }
+}
+
+__global__ __launch_bounds__(512) void beam_finish_kernel(BeamArgs ba) {
+  __shared__ int sh_run[kBeamMax][kBeamSeqMax], sh_fin[kBeamMax][kBeamSeqMax];   // the clip's histories as they were before this step
+  __shared__ float top_a[kBeamMax][kBeamCand];
+  __shared__ int top_t[kBeamMax][kBeamCand];
+  __shared__ float cand_s[kBeamCand], cand_r[kBeamCand], cand_f[kBeamCand];
+  __shared__ int cand_b[kBeamCand], cand_t[kBeamCand], cand_hit[kBeamCand];
+  __shared__ float old_fs[kBeamMax], run_new_s[kBeamMax], fin_new_s[kBeamMax];
+  __shared__ int old_flag[kBeamMax], old_len[kBeamMax], run_src[kBeamMax], run_tok[kBeamMax], fin_src[kBeamMax];
+  const SamplerArgs& a = ba.s;
+  const int c = blockIdx.x, n = ba.n_clips, K = ba.K, C2 = 2 * ba.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cur = a.stt->pos + 1, n0 = a.stt->n_prompt;   // cur: tokens every running hypothesis holds
+  const long long ld = a.seq_ld;
+  if (cur < n0) {   // the prompt lasts: its next token, for every beam
+    if (tid < K) {
+      const int r = tid * n + c;
+      a.cur_ids[r] = a.seq[r * ld + cur];
+      ba.beam_idx[r] = tid;
+    }
+    return;
+  }
+  if (ba.done[c] != 0) {   // frozen
+    if (tid < K) ba.beam_idx[tid * n + c] = tid;
+    return;
+  }
+  for (int idx = tid; idx < K * (cur + 1); idx += 512) {
+    const int kk = idx / (cur + 1), i = idx % (cur + 1);
+    sh_run[kk][i] = a.seq[(kk * n + c) * ld + i];
+    sh_fin[kk][i] = ba.fin_seq[(kk * n + c) * ld + i];
+  }
+  // ---- per beam: lp of the listed ids, accumulated scores, the row's 2K best ----
+  if (wave < K) {
+    const int r = wave * n + c;
+    const SliceMerge m = merge_slices(a, ba.parts, r, lane);
+    const BeamPartial* pp = ba.parts + r * SAMPLER_NS_MAX + (lane & 31);
+    const bool on = lane < 32;
+    const float pm = on ? pp->raw_m : -INFINITY;
+    const float M = wave_max(pm);
+    const float S = wave_sum(pm > -INFINITY ? pp->raw_s * expf(pm - M) : 0.f);
+    const float logZ = logf(S);
+    const float acc = ba.run_score[r];
+    const bool is_ts = lane >= 32;
+    const float* cvp = is_ts ? pp->ts_v : pp->tx_v;
+    const int* cip = is_ts ? pp->ts_i : pp->tx_i;
+    float ca[kBeamCand];
+    int ci[kBeamCand];
+#pragma unroll
+    for (int j = 0; j < kBeamCand; ++j) {
+      const float x = j < C2 ? cvp[j] : -INFINITY;
+      const bool ok = x > -INFINITY && !(m.force_ts && !is_ts);
+      ca[j] = ok ? __fadd_rn(__fsub_rn(__fsub_rn(x, M), logZ), acc) : -INFINITY;
+      ci[j] = ok ? cip[j] : 0x7fffffff;
+    }
+    MaxIdx prev{INFINITY, -1};
+    for (int rd = 0; rd < C2; ++rd) {
+      MaxIdx best{-INFINITY, 0x7fffffff};
+#pragma unroll
+      for (int j = 0; j < kBeamCand; ++j)
+        if (beam_behind(ca[j], ci[j], prev)) best = better(best, MaxIdx{ca[j], ci[j]});
+      best = wave_best(best);
+      if (lane == 0) { top_a[wave][rd] = best.v; top_t[wave][rd] = best.i; }
+      prev = best;
+    }
+  }
+  __syncthreads();
+  // ---- the 2K candidates of the clip: rank by counting over the K x 2K survivors ----
+  if (tid < K * C2) {
+    const int kk = tid / C2, j = tid % C2;
+    const float av = top_a[kk][j];
+    const int tv = top_t[kk][j];
+    int rank = 0;
+    for (int e = 0; e < K * C2; ++e) {
+      const int k2 = e / C2;
+      const float a2 = top_a[k2][e % C2];
+      const int t2 = top_t[k2][e % C2];
+      const bool beats = a2 > av || (a2 == av && (k2 < kk || (k2 == kk && (t2 < tv || (t2 == tv && e < tid)))));
+      rank += beats ? 1 : 0;
+    }
+    if (rank < C2) {
+      cand_s[rank] = av;
+      cand_b[rank] = kk;
+      cand_t[rank] = tv == 0x7fffffff ? 0 : tv;   // fewer than 2K unmasked ids in the whole clip: score -inf
+    }
+  }
+  __syncthreads();
+  // ---- steps 4-6, 8, 9 ----
+  if (tid == 0) {
+    const float NEG = -1e9f;
+    bool all_fin = true;
+    for (int kk = 0; kk < K; ++kk) {
+      old_fs[kk] = ba.fin_score[kk * n + c];
+      old_flag[kk] = ba.fin_flag[kk * n + c];
+      old_len[kk] = ba.fin_len[kk * n + c];
+      all_fin = all_fin && old_flag[kk] != 0;
+    }
+    const bool open0 = ba.open[c] != 0;
+    const float penv = ba.pen[cur + 1 - n0];
+    bool all_hit = true;
+    for (int j = 0; j < C2; ++j) {
+      const bool hit = cand_t[j] == a.eos || cur + 1 >= ba.max_len;
+      cand_hit[j] = hit ? 1 : 0;
+      all_hit = all_hit && hit;
+      cand_r[j] = hit ? __fadd_rn(cand_s[j], NEG) : cand_s[j];
+      float f = __fdiv_rn(cand_s[j], penv);
+      if (ba.early && all_fin) f = __fadd_rn(f, NEG);
+      if (!open0) f = __fadd_rn(f, NEG);
+      if (!(j < K && hit)) f = __fadd_rn(f, NEG);
+      cand_f[j] = f;
+    }
+    unsigned used = 0;
+    for (int i = 0; i < K; ++i) {   // step 5: the K best running candidates, lower j first on ties
+      int best = -1;
+      for (int j = 0; j < C2; ++j)
+        if (!((used >> j) & 1u) && (best < 0 || cand_r[j] > cand_r[best])) best = j;
+      used |= 1u << best;
+      run_src[i] = cand_b[best];
+      run_tok[i] = cand_t[best];
+      run_new_s[i] = cand_r[best];
+    }
+    used = 0;
+    bool all_new_fin = true;
+    int new_flag[kBeamMax], new_len[kBeamMax];
+    for (int i = 0; i < K; ++i) {   // step 6: the K best of [old finished, candidates], lower index first on ties
+      int best = -1;
+      float bv = 0.f;
+      for (int p = 0; p < K + C2; ++p) {
+        if ((used >> p) & 1u) continue;
+        const float v = p < K ? old_fs[p] : cand_f[p - K];
+        if (best < 0 || v > bv) { best = p; bv = v; }
+      }
+      used |= 1u << best;
+      fin_src[i] = best;
+      fin_new_s[i] = bv;
+      new_flag[i] = best < K ? old_flag[best] : ((best - K < K && cand_hit[best - K]) ? 1 : 0);
+      new_len[i] = best < K ? old_len[best] : cur + 1;
+      all_new_fin = all_new_fin && new_flag[i] != 0;
+    }
+    const float lhs = __fdiv_rn(run_new_s[0], penv);   // step 8 (pen[cur' - n0] with cur' = cur + 1)
+    bool any = false;
+    for (int kk = 0; kk < K; ++kk) any = any || lhs > (new_flag[kk] ? fin_new_s[K - 1] : NEG);
+    const bool open1 = open0 && any;
+    for (int kk = 0; kk < K; ++kk) {
+      ba.fin_score[kk * n + c] = fin_new_s[kk];
+      ba.fin_flag[kk * n + c] = new_flag[kk];
+      ba.fin_len[kk * n + c] = new_len[kk];
+    }
+    ba.open[c] = open1 ? 1 : 0;
+    ba.done[c] = (!open1 || (ba.early && all_new_fin) || all_hit) ? 1 : 0;   // step 9
+  }
+  __syncthreads();
+  // ---- the new histories, gathered from the LDS copies ----
+  for (int idx = tid; idx < K * (cur + 1); idx += 512) {
+    const int kk = idx / (cur + 1), i = idx % (cur + 1);
+    a.seq[(kk * n + c) * ld + i] = i < cur ? sh_run[run_src[kk]][i] : run_tok[kk];
+    const int fs = fin_src[kk];
+    ba.fin_seq[(kk * n + c) * ld + i] = fs < K ? sh_fin[fs][i] : (i < cur ? sh_run[cand_b[fs - K]][i] : cand_t[fs - K]);
+  }
+  if (tid < K) {
+    const int r = tid * n + c, src = run_src[tid], tok = run_tok[tid];
+    const int ts_begin = a.timestamps ? a.no_ts_id + 1 : a.V;
+    int lt = -1;   // recomputed from the gathered history, as sampler_rows_finish_kernel does
+    for (int i = n0; i < cur; ++i) if (sh_run[src][i] >= ts_begin) lt = sh_run[src][i];
+    if (tok >= ts_begin) lt = tok;
+    a.last_ts[r] = lt;
+    a.cur_ids[r] = tok;
+    ba.beam_idx[r] = src;
+    ba.run_score[r] = run_new_s[tid];
+  }
+}
+
+// Self-attention caches follow the beams, in place, one launch: workgroup = (64-key chunk, head, (layer, K | V, clip)).  A thread owns
+// VPT 16-byte vector offsets of the chunk and, for them, the vectors of ALL the clip's beams: it loads every vector it will
+// overwrite's source first, then stores - no other thread touches those addresses, so there is no staging arena and nothing to order.
+// Beams that continue themselves are not copied; a clip whose beam_idx is the identity, or which is done, returns at once.
+template <int VPT>   // 4: float32, 2: 16-bit elements (64 keys x 64 dims = VPT x 256 vectors)
+__global__ __launch_bounds__(256) void beam_reorder_kernel(u32x4_t* kc, u32x4_t* vc, long long layer_vec, long long b_vec, long long h_vec,
+                                                           BeamArgs ba) {
+  const int chunk = blockIdx.x, h = blockIdx.y, n = ba.n_clips, K = ba.K;
+  const int clip = blockIdx.z % n, kv = (blockIdx.z / n) & 1, layer = blockIdx.z / (2 * n);
+  if (chunk * 64 > ba.s.stt->pos || ba.done[clip] != 0) return;
+  int src[kBeamMax];
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < kBeamMax; ++k) {
+    src[k] = k < K ? ba.beam_idx[k * n + clip] : k;
+    any = any || src[k] != k;
+  }
+  if (!any) return;
+  u32x4_t* base = (kv ? vc : kc) + layer * layer_vec + h * h_vec + (long long)chunk * (VPT * 256) + threadIdx.x;
+  u32x4_t val[kBeamMax][VPT];
+#pragma unroll
+  for (int k = 0; k < kBeamMax; ++k)
+    if (src[k] != k) {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) val[k][j] = base[(long long)(src[k] * n + clip) * b_vec + j * 256];
+    }
+#pragma unroll
+  for (int k = 0; k < kBeamMax; ++k)
+    if (src[k] != k) {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) base[(long long)(k * n + clip) * b_vec + j * 256] = val[k][j];
+    }
+}
+
+// cross K / V of slot c -> slots k n + c, k >= 1: workgroup = (1024 vectors of a slot, destination slot - n, (layer, K | V))
+__global__ __launch_bounds__(256) void beam_cross_copy_kernel(u32x4_t* ck, u32x4_t* cv, long long layer_vec, long long slot_vec, int n) {
+  const int dst = n + blockIdx.y, clip = dst % n;
+  u32x4_t* base = ((blockIdx.z & 1) ? cv : ck) + (long long)(blockIdx.z >> 1) * layer_vec;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long long i = ((long long)blockIdx.x * 4 + j) * 256 + threadIdx.x;
+    if (i < slot_vec) base[dst * slot_vec + i] = base[clip * slot_vec + i];
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -2571,6 +2896,45 @@ hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist,
 
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st) {
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, st, stt, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_step(const BeamArgs& a0, bool in_prompt, hipStream_t st) {
+  const SamplerArgs& s = a0.s;
+  if (a0.K < 2 || a0.K > kBeamMax || a0.n_clips < 1 || s.B != a0.n_clips * a0.K || s.B > 64 || s.seq_ld > kBeamSeqMax || s.rows_streams != 0 ||
+      !s.logits || !s.seq || !s.cur_ids || !s.finished || !s.last_ts || !s.stt || !s.suppress_bits || !a0.parts || !a0.run_score ||
+      !a0.fin_seq || !a0.fin_score || !a0.fin_flag || !a0.fin_len || !a0.open || !a0.done || !a0.beam_idx || !a0.pen)
+    return hipErrorInvalidValue;
+  BeamArgs a = a0;
+  a.s.n_slices = 32;   // the slicing of launch_sampler whatever the number of rows: a row's partials, and the order they are merged in
+  if (!in_prompt) {    // (host-known: while the prompt lasts nothing is selected)
+    hipLaunchKernelGGL((beam_part_kernel<32, 4>), dim3(32, s.B), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(a.n_clips), dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_reorder(int dtype, void* kc, void* vc, long long layer_stride, long long bstride, long long hstride, int Ld, int H,
+                               int key_bound, const BeamArgs& a, hipStream_t st) {
+  const int E = dtype == 0 ? 4 : 8;   // elements per 16-byte vector
+  const int kb = (key_bound + 63) / 64 * 64;
+  if (a.K < 2 || a.K > kBeamMax || a.n_clips < 1 || a.n_clips * a.K > 64 || kb < 64 || hstride < (long long)kb * 64 || layer_stride % E != 0 ||
+      bstride % E != 0 || hstride % E != 0 || !kc || !vc || !a.beam_idx || !a.done || !a.s.stt)
+    return hipErrorInvalidValue;
+  const dim3 grid(kb / 64, H, Ld * 2 * a.n_clips);
+  if (dtype == 0) hipLaunchKernelGGL(beam_reorder_kernel<4>, grid, dim3(256), 0, st, (u32x4_t*)kc, (u32x4_t*)vc, layer_stride / E, bstride / E, hstride / E, a);
+  else hipLaunchKernelGGL(beam_reorder_kernel<2>, grid, dim3(256), 0, st, (u32x4_t*)kc, (u32x4_t*)vc, layer_stride / E, bstride / E, hstride / E, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_cross_copy(void* ck, void* cv, long long layer_bytes, long long slot_bytes, int Ld, int n_clips, int K, hipStream_t st) {
+  if (!ck || !cv || layer_bytes % 16 != 0 || slot_bytes % 16 != 0 || slot_bytes < 16 || n_clips < 1 || K < 2 || (long long)n_clips * K * slot_bytes > layer_bytes)
+    return hipErrorInvalidValue;
+  const long long slot_vec = slot_bytes / 16;
+  hipLaunchKernelGGL(beam_cross_copy_kernel, dim3((unsigned)((slot_vec + 1023) / 1024), (K - 1) * n_clips, Ld * 2), dim3(256), 0, st, (u32x4_t*)ck,
+                     (u32x4_t*)cv, layer_bytes / 16, slot_vec, n_clips);
   return hipGetLastError();
 }
 

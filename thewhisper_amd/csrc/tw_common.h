@@ -466,6 +466,44 @@ hipError_t launch_repeat(const RepeatArgs& a, hipStream_t st);
 hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist, int ld, const int* n_hist, const int* tab, hipStream_t st);
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st);     // pos += n only (teacher-forced stepping, prefill)
 
+// Beam search (tw_generate_beam; THE RULE is in include/thewhisper.h; k_decode.hip: beam_part_kernel, beam_finish_kernel,
+// beam_reorder_kernel).  Beam k of clip c is row k * n_clips + c of every per-row table (beam-major): `s` carries what sampler_mask()
+// needs for those rows - logits, V, B = n_clips * K, seq / seq_ld (the running hypotheses), cur_ids, finished (all zero), last_ts, stt,
+// the processor fields - and nothing of the sampler's workspaces.
+constexpr int kBeamMax = 8;                 // beams per clip
+constexpr int kBeamCand = 2 * kBeamMax;     // candidates a step keeps per clip, and per (row, slice, text | timestamp) list
+constexpr int kBeamSeqMax = 512;            // positions a hypothesis can hold (the self attention's 512-key limit)
+struct BeamPartial {  // per (row, vocabulary slice); begins with SamplerPartial's five fields (merge_slices)
+  float bt_v; int bt_i; float bs_v; int bs_i; float sum;
+  float raw_m, raw_s;                       // (max, sum exp(x - max)) over ALL ids of the slice: the row's log-softmax
+  int pad_;
+  float tx_v[kBeamCand]; int tx_i[kBeamCand];   // the slice's best unmasked text ids, (logit descending, id ascending); -inf: no more
+  float ts_v[kBeamCand]; int ts_i[kBeamCand];   // ... and timestamp ids, kept apart: the mass rule drops the text ones afterwards
+};
+struct BeamArgs {
+  SamplerArgs s;
+  int n_clips, K, early, max_len;
+  BeamPartial* parts;        // [64][32]
+  float* run_score;          // [rows]
+  int* fin_seq;              // [rows][seq_ld]: finished hypotheses, the prompt then pad_id at the start
+  float* fin_score;          // [rows]
+  int* fin_flag;             // [rows]
+  int* fin_len;              // [rows] tokens of the hypothesis, prompt included
+  int* open;                 // [n_clips]
+  int* done;                 // [n_clips]
+  int* beam_idx;             // [rows]: the beam whose cache rows beam k continues from (identity while the prompt lasts and once done)
+  const float* pen;          // [seq_ld + 1]: pen[g] = (float)pow((double)g, (double)length_penalty), host-tabulated
+};
+// part + finish; the position is NOT advanced (the reorder reads it): launch_beam_reorder, then launch_advance
+hipError_t launch_beam_step(const BeamArgs& a, bool in_prompt, hipStream_t st);
+// self-attention caches of every layer ([Ld] slabs of layer_stride elements; per row cache_bstride, per head cache_hstride, 64 keys =
+// one run of 4096 elements): row k * n_clips + c <- row beam_idx[..] * n_clips + c for the keys [0, pos], in place
+hipError_t launch_beam_reorder(int dtype, void* kc, void* vc, long long layer_stride, long long bstride, long long hstride, int Ld, int H,
+                               int key_bound, const BeamArgs& a, hipStream_t st);
+// cross K / V of clip c (slot c) -> slots k * n_clips + c, k = 1 .. K-1, every layer, one launch of 16-byte copies; the source slots
+// are only read
+hipError_t launch_beam_cross_copy(void* ck, void* cv, long long layer_bytes, long long slot_bytes, int Ld, int n_clips, int K, hipStream_t st);
+
 // A11: alignment rows -> token timestamps
 struct DtwArgs {
   const float* align; int Ha; int P; int T;   // [B][Ha][P][T]

@@ -609,6 +609,41 @@ class WhisperEngine:
         seq = res["sequences"]
         return {"sequences": [seq[b, int(n_pad[b]):] for b in range(seq.shape[0])], "n_pad": n_pad, "length": res["length"]}
 
+    # ---- beam search --------------------------------------------------------------------------
+    def generate_beam(self, prompt: np.ndarray, num_beams: int, length_penalty: float = 1.0, early_stopping: bool = False, *,
+                      max_new_tokens: int = 128, min_new_tokens: int = 0, max_length: int = 448, eos_id: int = 50257, pad_id: int = 50257,
+                      timestamps: bool = False, no_timestamps_id: int = 50364, max_initial_timestamp_index: Optional[int] = 50,
+                      begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = ()) -> Dict[str, np.ndarray]:
+        """Beam search with ``num_beams`` (2..8) beams per row of ``prompt`` (tw_generate_beam, where the rule - HF's
+        ``GenerationMixin._beam_search`` - is stated).  Needs ``max_batch >= rows x num_beams``.  ``sequences`` int64 [n, L]: the best
+        hypotheses; ``scores`` float32 [n]; ``nbest_sequences`` int64 [n, K, Ln] and ``nbest_scores`` float32 [n, K]: every hypothesis in
+        descending score (a score <= -1e9 marks a placeholder).  Everything behind a hypothesis's end is ``pad_id``.  The other
+        keywords are ``generate_greedy``'s processors."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        n, n0 = prompt.shape
+        K = int(num_beams)
+        if early_stopping not in (False, True, 0, 1):
+            raise ValueError(f"early_stopping must be False or True, got {early_stopping!r}")
+        o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
+                                     min_new_tokens, max_new_tokens, max_length)
+        bo = _cabi.tw_beam_opts()
+        bo.num_beams, bo.length_penalty, bo.early_stopping = K, float(length_penalty), 1 if early_stopping else 0
+        ld = int(max_length)
+        out = np.full((n, ld), pad_id, dtype=np.int32)
+        nbest = np.full((n, max(K, 1), ld), pad_id, dtype=np.int32)
+        score = np.zeros((n,), dtype=np.float32)
+        nscore = np.zeros((n, max(K, 1)), dtype=np.float32)
+        out_len = (C.c_int32 * 2)(0, 0)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        rc = self.lib.tw_generate_beam(self.ctx, n, prompt.ctypes.data_as(i32p), n0, C.byref(o), C.byref(bo), out.ctypes.data_as(i32p),
+                                       out_len, score.ctypes.data_as(f32p), nbest.ctypes.data_as(i32p), nscore.ctypes.data_as(f32p),
+                                       self._loop_stream())
+        self._chk(rc, "tw_generate_beam")
+        self._release_held()
+        L, Ln = int(out_len[0]), int(out_len[1])
+        return {"sequences": out[:, :L].astype(np.int64), "scores": score, "nbest_sequences": nbest[:, :, :Ln].astype(np.int64),
+                "nbest_scores": nscore, "length": L}
+
     # ---- temperature sampling ----------------------------------------------------------------
     def generate_sample(self, prompt: np.ndarray, temperature, seed, offset=None, *, max_new_tokens: int = 128, min_new_tokens: int = 0,
                         max_length: int = 448, eos_id: int = 50257, pad_id: int = 50257, timestamps: bool = False,

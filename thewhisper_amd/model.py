@@ -12,8 +12,8 @@ slicing - per chunk, host side) and replaces everything underneath it:
   loop with the Whisper logits processors on the GPU (A2-A10).
 * ``_extract_token_timestamps`` is overridden with the on-device median-filter + DTW (A11).
 
-Unsupported generation options (beam search, sampling, custom processors ...) raise
-``NotImplementedError``: there is no eager/CPU fallback.
+Beam search (``num_beams`` 2..8) runs on the device once ``model.beam_search = True`` (opt-in; ``_beam_generate``).  Unsupported
+generation options (sampling through this seam, custom processors ...) raise ``NotImplementedError``: there is no eager/CPU fallback.
 """
 from __future__ import annotations
 
@@ -90,12 +90,19 @@ class _EngineGreedyMixin(GenerationMixin):
     ):
         eng = self._require_engine()
         gc = generation_config if generation_config is not None else self.generation_config
-        self._check_supported(gc, stopping_criteria, prefix_allowed_tokens_fn, kwargs)
+        num_beams = int(kwargs.get("num_beams") or getattr(gc, "num_beams", 1) or 1)
+        beams = num_beams > 1 and bool(getattr(self, "beam_search", False))
+        self._check_supported(gc, stopping_criteria, prefix_allowed_tokens_fn, kwargs, beams_ok=beams)
         if inputs is None:
             inputs = kwargs.pop("input_features", None)
         if inputs is None or decoder_input_ids is None:
             raise NotImplementedError("the MI355X engine needs `input_features` and `decoder_input_ids`")
         B = int(inputs.shape[0])
+        if beams and num_beams > 8:
+            raise NotImplementedError(f"num_beams={num_beams}: the MI355X engine searches with 2..8 beams")
+        if beams and B * num_beams > eng.max_batch:
+            raise ValueError(f"num_beams={num_beams} on a batch of {B} chunks needs {B * num_beams} engine rows, the engine holds "
+                             f"max_batch={eng.max_batch}: construct ASRPipeline with batch_size={B * num_beams}")
         if B > eng.max_batch:
             raise ValueError(f"batch of {B} chunks exceeds the engine capacity max_batch={eng.max_batch}; "
                              "construct ASRPipeline with a matching batch_size")
@@ -137,6 +144,10 @@ class _EngineGreedyMixin(GenerationMixin):
             raise ValueError("repetition_penalty / no_repeat_ngram_size and token scores (score_sink) do not go together: the re-scoring "
                              "pass does not know the rule")
 
+        if beams:
+            return self._beam_generate(eng, gc, inputs, decoder_input_ids, num_beams, opts, bias, repeat, n_pad, kwargs,
+                                       dict(max_new_tokens=max_len - n_prompt, min_new_tokens=min_new, max_length=max_target,
+                                            eos_id=int(eos), pad_id=int(pad)))
         eng.encode(inputs)
         eng.cross_kv(B)
         want_align = bool(getattr(gc, "return_token_timestamps", False))
@@ -164,11 +175,41 @@ class _EngineGreedyMixin(GenerationMixin):
             return GenerateEncoderDecoderOutput(sequences=seq)
         return seq
 
+    def _beam_generate(self, eng, gc, inputs, decoder_input_ids, num_beams, opts, bias, repeat, n_pad, kwargs, limits):
+        """``num_beams`` > 1 with ``beam_search = True``: HF's ``_beam_search`` on the device (tw_generate_beam), the best hypothesis per
+        row.  What the beam call cannot do is refused by name."""
+        if getattr(gc, "return_token_timestamps", False) or kwargs.get("return_token_timestamps"):
+            raise NotImplementedError("return_token_timestamps with num_beams > 1: a beam result has no alignment rows on the MI355X engine")
+        if bias:
+            raise NotImplementedError("sequence_bias with num_beams > 1")
+        if repeat:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size with num_beams > 1")
+        if n_pad is not None:
+            raise NotImplementedError("a padded decoder_attention_mask with num_beams > 1")
+        if getattr(self, "score_sink", None) is not None:
+            raise NotImplementedError("token scores (score_sink) with num_beams > 1")
+        early = getattr(gc, "early_stopping", False)
+        if early not in (False, True):
+            raise NotImplementedError(f"early_stopping={early!r} with num_beams > 1: the MI355X engine implements False and True")
+        lp = getattr(gc, "length_penalty", None)
+        B = int(inputs.shape[0])
+        eng.encode(inputs)
+        eng.cross_kv(B)
+        prompt = decoder_input_ids.detach().to("cpu", torch.int32).numpy()
+        out = eng.generate_beam(prompt, num_beams, 1.0 if lp is None else float(lp), bool(early), **limits, **opts)
+        seq = torch.from_numpy(out["sequences"]).to(decoder_input_ids.device, torch.long)
+        self._last_greedy = {"B": B, "n_prompt": int(prompt.shape[1]), "len": int(seq.shape[1])}
+        if getattr(gc, "return_dict_in_generate", False):
+            from transformers.generation.utils import GenerateBeamEncoderDecoderOutput
+
+            return GenerateBeamEncoderDecoderOutput(sequences=seq, sequences_scores=torch.from_numpy(out["scores"]).to(seq.device))
+        return seq
+
     # -- helpers ---------------------------------------------------------------------------------
     @staticmethod
-    def _check_supported(gc, stopping_criteria, prefix_allowed_tokens_fn, kwargs):
+    def _check_supported(gc, stopping_criteria, prefix_allowed_tokens_fn, kwargs, beams_ok=False):
         bad = []
-        if getattr(gc, "num_beams", 1) not in (None, 1) or kwargs.get("num_beams", 1) not in (None, 1):
+        if not beams_ok and (getattr(gc, "num_beams", 1) not in (None, 1) or kwargs.get("num_beams", 1) not in (None, 1)):
             bad.append("num_beams > 1")
         if getattr(gc, "do_sample", False):
             bad.append("do_sample")
@@ -356,6 +397,9 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
     #: rule of tw_generate_greedy_ragged - every row is decoded as if it were alone, which is HF's batch-1 result for it and NOT HF's
     #: result for the padded batch (HF keeps absolute positions there; DESIGN.md, "Ragged decoder prompts").  An all-ones mask needs no opt-in.
     ragged_decoder_prompts: bool = False
+    #: opt-in: ``num_beams`` 2..8 runs HF's beam search on the device (tw_generate_beam) and returns the best hypothesis per row; False:
+    #: ``num_beams > 1`` raises NotImplementedError as before.  Needs an engine with ``max_batch >= batch x num_beams``.
+    beam_search: bool = False
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
@@ -383,6 +427,8 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         if int(feats.shape[0]) > self._engine.max_batch or int(feats.shape[0]) < 1:
             return None
         gc = kwargs.get("generation_config") or self.generation_config
+        if (kwargs.get("num_beams") or getattr(gc, "num_beams", 1) or 1) > 1:
+            return None           # beam calls always run HF's Whisper control flow around the engine call
         lang = kwargs.get("language", getattr(gc, "language", None))
         if lang is None and getattr(gc, "is_multilingual", False):
             return None           # language detection is a forward pass whose result selects the prompt per row

@@ -454,6 +454,13 @@ int tw_generate_beam(tw_ctx* ctx, int32_t n_clips, const int32_t* prompt_host /*
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */
 int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds);
 
+/* How the most recent call of the tw_generate_greedy / tw_generate_sample family consumed its prompt: the rows-mode launches it took
+ * (0: one position per step) and the prompt positions those launches consumed.  The plain greedy call (no forced, draft, bias, repeat,
+ * ragged or sampling options) with n_prompt >= 2 takes a prompt of at most 64 rows (n_prompt x n_clips; 16 in W8A8 contexts) as one
+ * launch; the result is the step path's, bit for bit.  A call with n_forced > 0 reports its batched prefill (positions 0 .. n_prompt - 2);
+ * the rows launches of a draft are tw_last_draft's.  Any pointer may be NULL. */
+int tw_last_prompt_rows(tw_ctx* ctx, int32_t* launches, int32_t* positions);
+
 /* Token log-probabilities and the no-speech probability of FINISHED sequences, by a teacher-forced re-scoring pass.  Replaces: the
  * `scores` HF's generate keeps per step and WhisperGenerationMixin._retrieve_avg_logprobs reduces
  * (HF:models/whisper/generation_whisper.py:1957-1974: log_softmax of the PROCESSED scores, gathered at the chosen tokens, summed and divided

@@ -139,6 +139,7 @@ struct tw_ctx {
   // pinned image (up with the initial state, down with the result) and the slice partials, allocated by the first beam call of the context
   int* beam_tab = nullptr; int* h_beam = nullptr; BeamPartial* beam_parts = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
+  int last_prompt_rows[2] = {0, 0};   // of the last call of the generate family: rows launches its prompt took, positions they consumed
   size_t row_ids_cap = 0;
   // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
   // (or its captured step graphs) reads is touched
@@ -1474,6 +1475,15 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   // the embedding of the token a step has chosen is written by the sampler's last launch (k_decode.hip: embed_row), so a step is
   // layers + logits + sampler; only the FIRST step of the call needs its input row from a launch of its own
   c->last_draft[0] = n_draft * B; c->last_draft[1] = c->last_draft[2] = c->last_draft[3] = 0;
+  c->last_prompt_rows[0] = c->last_prompt_rows[1] = 0;
+  if (n_forced > 0) {   // the batched prefill above (prefill_core)
+    const int per_launch = std::max(1, rows_per_launch(c) / B);
+    c->last_prompt_rows[0] = (s_start + per_launch - 1) / per_launch; c->last_prompt_rows[1] = s_start;
+  }
+  // The plain greedy call takes its prompt as ONE rows-mode launch (below, behind the timer's start) when the prompt's rows fit one:
+  // every other flavour - and a longer prompt or more streams - consumes it one position per step
+  const bool prompt_rows = !so && !fo && !biased && !repeat && !ragged && n_forced == 0 && n_draft == 0 && n_prompt >= 2 &&
+                           n_prompt * B <= rows_per_launch(c) && (size_t)n_prompt * B <= c->row_ids_cap;
   bool draft_all_done = false;
   if (n_draft > 0) {
     // ---- draft-and-verify: rounds of rows-mode launches over the given tokens (verify_round), then the ordinary loop from where the
@@ -1520,7 +1530,8 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   }
   sa.tok_emb = c->tok_emb; sa.pos_emb = c->dec_pos; sa.x_next = ragged ? nullptr : c->dx0; sa.d = c->d; sa.dtype = c->dtype;
   DecodeOpts step; step.embed = false; step.n_pad = ragged ? c->n_pad_tab : nullptr;   // the loop's step: its input rows are in place, or - ragged - it embeds its own
-  if (!ragged) HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
+  // (a prompt taken as rows: the sampler behind the rows launch writes the loop's first input row, below)
+  if (!ragged && !prompt_rows) HIPCHK(c, launch_embed(c->dtype, c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, c->d, 0, st));
 
   // ---- graph replay: one captured step per self-attention length bucket, captured on first use ----
   char keybuf[256];
@@ -1589,6 +1600,26 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   auto ht_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count(); };
   double ht_first = 0, ht_loop = 0;
   if (n_draft == 0) tic(c, 3, st);
+  if (prompt_rows) {
+    // ---- the prompt as rows: positions 0 .. n_prompt - 1 of every stream in one rows-mode launch - the shape of a verify_round with
+    //      nothing to verify - instead of n_prompt steps: the weights are streamed once, the cross attention reads a stream's K / V^T
+    //      once (k_decode.hip: dec_cross_attn_rows_kernel), and the sampler runs for the LAST position only, as the ordinary
+    //      sampler on that position's rows of the logits.  A row's bits do not depend on the rows that share its launch, and the
+    //      sampler of a prompt position changes nothing but the device position, so the token at n_prompt, the self caches, the
+    //      alignment rows, finished[], last_ts[] and the position are the step path's; the loop goes on from position n_prompt. ----
+    fill_row_tables(c, B, hseq, P, 0, n_prompt - 1, false, 0, 0);
+    HIPCHK(c, hipMemcpyAsync(c->row_ids, c->h_rows.tok, sizeof(int) * (size_t)n_prompt * B, hipMemcpyHostToDevice, st));
+    DecodeOpts rows; rows.rows_streams = B; rows.ids = c->row_ids;
+    c->dec_key_bound = key_bound(n_prompt, max_len);
+    r = decode_core(c, n_prompt * B, st, rows);
+    if (r != TW_OK) return r;
+    HIPCHK(c, launch_advance(c->stt, n_prompt - 1, st));
+    SamplerArgs sl = sa;
+    sl.logits = c->logits + (size_t)(n_prompt - 1) * B * c->V;
+    HIPCHK(c, launch_sampler(sl, st));
+    c->last_prompt_rows[0] = 1; c->last_prompt_rows[1] = n_prompt;
+    s_start = n_prompt;
+  }
   // two steps per graph launch: measured +2 % at one turbo stream, +0.3 % at 16 large-v3 streams (4 per launch: +3 % / +0.8 %, but
   // up to 7 steps past the last <eos> instead of 5); the finished flags are read LAG launches behind so the host never waits
   constexpr int group = 2;
@@ -1636,7 +1667,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
   }
   toc(c, 3, st);
   ht_loop = ht_ms();
-  c->last_steps = steps;
+  c->last_steps = steps + (prompt_rows ? n_prompt : 0);   // positions consumed by the call, the prompt's as steps or as rows
   HIPCHK(c, hipMemcpyAsync(hseq, c->seq, sizeof(int) * (size_t)B * P, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (host_timing) {
@@ -2007,6 +2038,13 @@ int tw_last_draft(tw_ctx* c, int32_t* offered, int32_t* accepted, int32_t* launc
   if (accepted) *accepted = c->last_draft[1];
   if (launches) *launches = c->last_draft[2];
   if (rounds) *rounds = c->last_draft[3];
+  return TW_OK;
+}
+
+int tw_last_prompt_rows(tw_ctx* c, int32_t* launches, int32_t* positions) {
+  if (!c) return TW_EINVAL;
+  if (launches) *launches = c->last_prompt_rows[0];
+  if (positions) *positions = c->last_prompt_rows[1];
   return TW_OK;
 }
 

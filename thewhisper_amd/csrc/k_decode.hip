@@ -1250,6 +1250,176 @@ __global__ __launch_bounds__(512) void dec_cross_attn_kernel(const T* __restrict
   }
 }
 
+// Rows flavour of dec_cross_attn_kernel (rows mode with more than one position per stream: prefill_core, verify_round,
+// tw_score_tokens).  One workgroup per (stream, head, group of up to 16 of the stream's positions): column j of the MFMA B operands
+// is position g * 16 + j of the stream, i.e. row srow + (g * 16 + j) * rows_streams of the launch, so ONE pass over the head's K / V^T
+// serves 16 queries with the matrix instructions the single-query kernel spends on one (there every column carries the same query).
+// Every column is computed by that kernel's expression tree - a column of an MFMA depends on its own B column only; column max
+// over the kq lane groups, then over the wavefronts in index order; expf(sc - M), one key per lane; tw_wave_sum, then the wavefronts
+// in index order; probabilities rounded by pack16 before P.V; partial context vectors added over the wavefronts in index order,
+// then x 1/L - so a row's bits are the one-position step's.  Columns behind the group's last position repeat that position and are
+// not written.
+// LDS (dynamic): scores float[16][Tp + 4] | partial context vectors float[8][16][68] | column max float[8][16] | normaliser
+// float[8][16] | query rows T[16][64]: 71 KiB at Tp = 512 (two workgroups per CU), 135 KiB at Tp = 1536 (one).
+template <typename T, bool SINGLE, bool FQ>
+__global__ __launch_bounds__(512) void dec_cross_attn_rows_kernel(const T* __restrict__ ck, const T* __restrict__ cv, int H, int Tp,
+                                                                   int Tlen, int rows_streams, int n_pos, const T* __restrict__ q,
+                                                                   T* __restrict__ out, const int* __restrict__ align_slot,
+                                                                   float* __restrict__ align, int Ha, int P,
+                                                                   const DecState* __restrict__ stt, FusedQ fq) {
+  constexpr int NW = 8, WS = 68;
+  constexpr int E = ElemTraits<T>::kPer16B;
+  constexpr int DS = 64 / (4 * E);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int S = Tp + 4;
+  float* sc = reinterpret_cast<float*>(smem);   // [16][S] scores -> unnormalised probabilities
+  float* wo = sc + 16 * S;                      // [NW][16][WS]
+  float* redm = wo + NW * 16 * WS;              // [NW][16]
+  float* wl = redm + NW * 16;                   // [NW][16]
+  T* qst = reinterpret_cast<T*>(wl + NW * 16);  // [16][64]
+  const int h = blockIdx.x, srow = blockIdx.y, p0 = blockIdx.z * 16;
+  const int nc = min(16, n_pos - p0);           // columns in use
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, kq = lane >> 4;
+  const long long base = ((long long)srow * H + h) * Tp * 64;
+  const T* kf = ck + base;
+  const T* vtf = cv + base;
+  const int n_keys = Tlen, n_bound = Tp;
+  const int n_chunks = SINGLE ? 1 : (n_bound + NW * 64 - 1) / (NW * 64);
+  const int last64 = n_bound / 64 - 1;
+  u32x4_t qf[DS], kfr[4 * DS], vfr[4 * DS];
+  auto load_k = [&](int g64) {
+    const T* p = kf + ((long long)min(g64, last64) * (4 * DS) * 64 + lane) * E;
+#pragma unroll
+    for (int i = 0; i < 4 * DS; ++i) kfr[i] = *reinterpret_cast<const u32x4_t*>(p + (long long)i * 64 * E);
+  };
+  auto load_v = [&](int g64) {
+    const T* p = vtf + ((long long)min(g64, last64) * (4 * DS) * 64 + lane) * E;
+#pragma unroll
+    for (int i = 0; i < 4 * DS; ++i) vfr[i] = *reinterpret_cast<const u32x4_t*>(p + (long long)i * 64 * E);
+  };
+  auto row_of = [&](int j) { return srow + (p0 + min(j, nc - 1)) * rows_streams; };   // launch row of column j
+  load_k(wave);
+  if constexpr (FQ) {
+    // the group's query rows, once per workgroup: wavefront w builds the rows of columns w and w + 8
+    QRaw<T> qr[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) fq_request<T>(qr[i], fq, row_of(wave + 8 * i), h, lane);
+    if (SINGLE) load_v(wave);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) fq_finish<T>(qr[i], fq, lane, qst + (wave + 8 * i) * 64);
+    __syncthreads();
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const u32x4_t*>(qst + fr * 64 + ds * 4 * E + kq * E);
+  } else {
+    const T* qrow = q + ((long long)row_of(fr) * H + h) * 64;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const u32x4_t*>(qrow + ds * 4 * E + kq * E);
+    if (SINGLE) load_v(wave);
+  }
+
+  // ---- scores: lane (fr, kq) holds keys kq * 4 + r of the tile for column fr ----
+  float m = -1.0e30f;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int g64 = c * NW + wave;
+    if (c > 0) load_k(g64);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ds = 0; ds < DS; ++ds) acc = sk_mfma<T>(kfr[a * DS + ds], qf[ds], acc);
+      f32x4_t sv4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = g64 * 64 + a * 16 + kq * 4 + r;
+        const float sv = (t < n_keys) ? acc[r] : -1.0e30f;
+        m = fmaxf(m, sv);
+        sv4[r] = sv;
+      }
+      if (g64 * 64 < n_bound) *reinterpret_cast<f32x4_t*>(sc + fr * S + g64 * 64 + a * 16 + kq * 4) = sv4;
+    }
+  }
+  m = tw_xor32_max(tw_xor16_max(m));
+  if (kq == 0) redm[wave * 16 + fr] = m;
+  __syncthreads();
+  float Mc = redm[fr];   // lane's column
+#pragma unroll
+  for (int w = 1; w < NW; ++w) Mc = fmaxf(Mc, redm[w * 16 + fr]);
+
+  // ---- probabilities of this wavefront's own keys, every column, and P.V ----
+  f32x4_t o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float ls[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) ls[j] = 0.f;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int g64 = c * NW + wave;
+    if (!SINGLE) load_v(g64);
+    const int t0 = g64 * 64 + lane;  // one key per lane
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float M = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Mc), j));
+      float pr = 0.f;
+      if (t0 < n_bound) {
+        pr = (t0 < n_keys) ? expf(sc[j * S + t0] - M) : 0.f;
+        sc[j * S + t0] = pr;
+      }
+      ls[j] += pr;
+    }
+#pragma unroll
+    for (int ks = 0; ks < DS; ++ks) {
+      float pv[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int t = g64 * 64 + ks * 4 * E + kq * E + e;
+        pv[e] = (t < n_bound) ? sc[fr * S + t] : 0.f;  // same wavefront wrote these: LDS operations of a wavefront stay in order
+      }
+      const u32x4_t pf = pack16<T>(pv);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = sk_mfma<T>(vfr[ks * 4 + dt], pf, o[dt]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    // lane 0's sum, as in the single-query kernel: tw_wave_sum adds the four quads of a row in another order in odd quads
+    // than in even ones, so the lanes of a wavefront do not all hold the same bits
+    const float l = tw_wave_sum(ls[j]);
+    if (lane == 0) wl[wave * 16 + j] = l;
+  }
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4_t*>(wo + (wave * 16 + fr) * WS + dt * 16 + kq * 4) = o[dt];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {   // 16 columns x 64 dims over 512 threads
+    const int j = (tid >> 6) + 8 * i, k = tid & 63;
+    float L = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) L += wl[w * 16 + j];
+    const float inv = 1.0f / L;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += wo[(w * 16 + j) * WS + k];
+    if (j < nc) {
+      const int b = srow + (p0 + j) * rows_streams;
+      out[(long long)(b >> 4) * 16 * H * 64 + tw_xt_index<T>(b & 15, h * 64 + k)] = (T)(v * inv);
+    }
+  }
+  const int slot = align_slot ? align_slot[h] : -1;
+  if (slot >= 0) {  // A11 side output: every column writes the softmax row of its own (stream, position)
+    const int pos = stt->pos;
+    for (int j = 0; j < nc; ++j) {
+      float L = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) L += wl[w * 16 + j];
+      const float inv = 1.0f / L;
+      float* row = align + (((long long)srow * Ha + slot) * P + pos + p0 + j) * Tlen;
+      for (int t = tid; t < Tlen; t += 512) row[t] = sc[j * S + t] * inv;
+    }
+  }
+}
+
 template <int G, bool FQ>
 __global__ __launch_bounds__(512) void dec_cross_attn_kv8_kernel(const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                   const unsigned char* __restrict__ ksc,
@@ -2781,6 +2951,28 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
     if (f) CA8_PICK(true); else CA8_PICK(false);
 #undef CA8_PICK
 #undef CA8_GO
+    return hipGetLastError();
+  }
+  if (rows_streams > 0 && B > rows_streams) {   // several positions per stream: one K / V^T pass per (stream, head, 16 positions)
+    if (B % rows_streams != 0 || Tp > 1536) return hipErrorInvalidValue;
+    const int n_pos = B / rows_streams;
+    const dim3 grid(H, rows_streams, (n_pos + 15) / 16);
+    const size_t esz = dtype == 0 ? 4 : 2;
+    const size_t ldsr = ((size_t)16 * (Tp + 4) + 8 * 16 * 68 + 2 * 8 * 16) * sizeof(float) + 16 * 64 * esz;
+    constexpr int lds_cap = 16 * (1536 + 4) * 4 + 8 * 16 * 68 * 4 + 2 * 8 * 16 * 4 + 16 * 64 * 4;
+    static_assert(lds_cap <= 160 * 1024, "LDS of a compute unit");
+#define CAR_GO(TT, SV, FV) do {                                                                                                        \
+      static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_cross_attn_rows_kernel<TT, SV, FV>),       \
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);                        \
+      if (attr != hipSuccess) return attr;                                                                                             \
+      hipLaunchKernelGGL((dec_cross_attn_rows_kernel<TT, SV, FV>), grid, dim3(512), ldsr, st, (const TT*)ck, (const TT*)cv, H, Tp, T,  \
+                         rows_streams, n_pos, (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq);                     \
+    } while (0)
+#define CAR_PICK(TT) do { if (single) { if (f) CAR_GO(TT, true, true); else CAR_GO(TT, true, false); }                               \
+                          else { if (f) CAR_GO(TT, false, true); else CAR_GO(TT, false, false); } } while (0)
+    if (dtype == 1) CAR_PICK(bf16_t); else if (dtype == 2) CAR_PICK(f16_t); else CAR_PICK(float);
+#undef CAR_PICK
+#undef CAR_GO
     return hipGetLastError();
   }
   const size_t lds = (size_t)Tp * sizeof(float);

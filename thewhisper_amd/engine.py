@@ -742,6 +742,13 @@ class WhisperEngine:
         rc = self.lib.tw_set_alignment(self.ctx, a.shape[0], a.shape[2], a.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
         self._chk(rc, "tw_set_alignment")
 
+    def last_prompt_rows(self) -> Dict[str, int]:
+        """How the last generate call consumed its prompt (tw_last_prompt_rows): ``launches`` rows-mode launches (0: one position per
+        step) that took ``positions`` prompt positions."""
+        v = [C.c_int32(0) for _ in range(2)]
+        self._chk(self.lib.tw_last_prompt_rows(self.ctx, *[C.byref(x) for x in v]), "tw_last_prompt_rows")
+        return {"launches": int(v[0].value), "positions": int(v[1].value)}
+
     def last_timings(self) -> Dict[str, float]:
         ms = (C.c_float * 5)()
         steps = C.c_int32(0)

@@ -450,6 +450,42 @@ int tw_generate_beam(tw_ctx* ctx, int32_t n_clips, const int32_t* prompt_host /*
                      int32_t* out_nbest_ids_host /*[n_clips, K, max_length], may be NULL*/, float* out_nbest_score_host /*[n_clips, K], may be NULL*/,
                      void* stream);
 
+/* tw_generate_beam with the alignment rows of every hypothesis, for token and word timestamps of a beam result.  Replaces:
+ * WhisperGenerationMixin._extract_token_timestamps on a beam output (HF:models/whisper/generation_whisper.py:265-301: the
+ * cross-attention rows of every beam at every step, gathered along beam_indices) - without a second pass through the decoder.
+ *
+ * opts->want_alignment == 0: the call IS tw_generate_beam, launch for launch, with the same bits (out_hyp_len_host is still filled).
+ * want_alignment == 1: every step (the prompt steps too) records the alignment-head rows of every beam where the beam sits - row
+ * (slot, position) of the buffer tw_get_alignment reads is written once and never moved while the loop runs - and the loop keeps the
+ * ancestry: per step the source beam of every running beam (step 5's beam_idx), per finished entry the beam whose logits produced
+ * its last token; the entry keeps it as it moves through the finished set (step 6).  Ids and scores are tw_generate_beam's, bit for
+ * bit.  Before the call returns ONE more launch gathers the rows in place among the K slots of each clip.
+ *
+ * THE RULE.  Hypothesis h of `len` tokens (prompt included), n0 = n_prompt:
+ *   - its alignment row at position p, 0 <= p <= len - 2, is the row that the beam which produced token h[p + 1] recorded at the
+ *     step that consumed position p;
+ *   - its DTW matrix (tw_token_timestamps_each) is rows n0 .. len - 2: N = len - 1 - n0 rows of its own, no row of any other
+ *     hypothesis or clip; N <= 0 gives all zeros (HF :338-339); a placeholder (score <= -1e9, nothing generated) is such a row;
+ *   - the result of a clip depends neither on its slot nor on its batch-mates.
+ * That is: a hypothesis gets the timestamps HF gives it when its clip is decoded ALONE (the precedent is the ragged-prompt rule of
+ * tw_generate_greedy_ragged).  Deviation from HF's BATCHED call: past a hypothesis's end HF replaces beam_indices == -1 by 0, i.e.
+ * by global row 0 (beam 0 of clip 0), and those rows enter the hypothesis's z-score over the token axis and its DTW.  Checked on the
+ * CPU with transformers 5.15.0 on the 139 (case, clip) pairs of tests/beam_judge.py: for all 76 clips whose best hypothesis is
+ * shorter than the longest of its batch, HF's batched token timestamps differ from HF's timestamps for the same clip decoded alone;
+ * on all 139, HF's batch-of-one timestamps equal the numpy oracle's (a teacher-forced decode of the best hypothesis, then its DTW)
+ * to 1e-6.
+ *
+ * Afterwards slot k * n_clips + c holds rows 0 .. len - 2 of hypothesis k of clip c, so the best hypotheses sit in slots
+ * 0 .. n_clips - 1; rows of a placeholder and rows at or behind len - 1 are unspecified.  tw_get_alignment and tw_score_tokens work
+ * as after a greedy call with want_alignment (tw_score_tokens leaves the rows alone).  The ancestry tables live in context-owned
+ * device memory beside the beam state (allocated by the first such call, freed by tw_destroy).  No atomics.
+ * out_hyp_len_host [n_clips, K] (may be NULL): len of every hypothesis (n_prompt for a placeholder).
+ * TW_EINVAL as tw_generate_beam, except that want_alignment == 1 is accepted - and refused when the context has no alignment heads. */
+int tw_generate_beam_aligned(tw_ctx* ctx, int32_t n_clips, const int32_t* prompt_host /*[n_clips, n_prompt]*/, int32_t n_prompt,
+                             const tw_greedy_opts* opts, const tw_beam_opts* bopts, int32_t* out_ids_host, int32_t* out_len_host /*[2]*/,
+                             float* out_score_host, int32_t* out_nbest_ids_host, float* out_nbest_score_host,
+                             int32_t* out_hyp_len_host /*[n_clips, K], may be NULL*/, void* stream);
+
 /* Of the most recent tw_generate_greedy with n_draft > 0 (all streams together): draft tokens offered, draft tokens confirmed, rows-mode
  * launches and verify rounds it took.  Any pointer may be NULL.  No reference counterpart (see tw_greedy_opts::n_draft). */
 int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* launches, int32_t* rounds);
@@ -502,6 +538,15 @@ int tw_score_tokens(tw_ctx* ctx, int32_t B, const int32_t* ids_host, int32_t ld,
  * (thewhisper_amd/shortform.py::hf_kept_columns).  out_ts_host: float32 [B, seq_len] seconds (seq_len = out_len of the greedy call). */
 int tw_token_timestamps(tw_ctx* ctx, int32_t B, int32_t n_prompt, int32_t seq_len, const int32_t* num_frames_host,
                         double time_precision, float* out_ts_host, void* stream);
+/* tw_token_timestamps for rows of different lengths (the hypotheses of tw_generate_beam_aligned): seq_len_host[b] tokens in row b,
+ * out_ts_host float32 [B, ld].  Row b is computed on its own N_b = seq_len[b] - 1 - n_prompt rows (positions n_prompt ..
+ * seq_len[b] - 2 of slot b) and is, in its first seq_len[b] entries, bit for bit what tw_token_timestamps returns for that row alone
+ * with seq_len = seq_len[b]: entries below n_prompt are 0, entries from seq_len[b] - 1 to ld - 1 repeat the row's last jump time,
+ * N_b <= 0 gives zeros.  With every length equal to ld the call is tw_token_timestamps.  The three kernels take a nullable per-row
+ * length; without it they run the code of the common-length call.
+ * TW_EINVAL, before anything is enqueued: a seq_len[b] above ld or above target_positions (or negative), n_prompt < 1, ld < 1. */
+int tw_token_timestamps_each(tw_ctx* ctx, int32_t B, int32_t n_prompt, const int32_t* seq_len_host /*[B]*/, int32_t ld,
+                             const int32_t* num_frames_host, double time_precision, float* out_ts_host /*[B, ld]*/, void* stream);
 /* Debug/parity access: copy the recorded alignment rows [B, n_align_heads, n_rows, T] (float32) to host. */
 int tw_get_alignment(tw_ctx* ctx, int32_t B, int32_t n_rows, float* out_host, void* stream);
 /* Its mirror: copy host float32 [B, n_align_heads, n_rows, T] into rows 0 .. n_rows-1 of slots 0 .. B-1 of the recorded-alignment

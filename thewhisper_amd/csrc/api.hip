@@ -138,6 +138,9 @@ struct tw_ctx {
   // tw_generate_beam: the state tables of the call (BeamTab: scores, finished set, flags, penalty table, finished hypotheses), their
   // pinned image (up with the initial state, down with the result) and the slice partials, allocated by the first beam call of the context
   int* beam_tab = nullptr; int* h_beam = nullptr; BeamPartial* beam_parts = nullptr;
+  // tw_generate_beam_aligned: the ancestry of the alignment rows (BeamArgs::back [512][64], then fin_last [64]), allocated by the first
+  // such call with want_alignment
+  int* beam_anc = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
   int last_prompt_rows[2] = {0, 0};   // of the last call of the generate family: rows launches its prompt took, positions they consumed
   size_t row_ids_cap = 0;
@@ -160,6 +163,7 @@ struct tw_ctx {
   float *zbuf = nullptr, *mat = nullptr, *out_ts = nullptr;
   signed char* trace = nullptr;
   int* n_cols = nullptr;
+  int* dtw_len = nullptr;   // tw_token_timestamps_each: the streams' lengths [Bmax], allocated by its first call
 
   // graph replay of one decode step
   // one captured step per 64-key bucket of the self-attention length (the step at position s only has to read keys
@@ -1762,9 +1766,10 @@ size_t beam_tab_words(const tw_ctx* c) { return kBeamFinSeq + (size_t)64 * c->P;
 
 // The beam loop (THE RULE: include/thewhisper.h).  Not captured: a beam step is issued launch by launch in use_graph contexts too, so
 // the two settings run the same launches, and the captured greedy step graphs of the context are left alone.
-int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_beam_opts* bo,
-                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_nbest_ids, float* out_nbest_score, void* stream) {
-  const char* fn = "tw_generate_beam";
+// tw_generate_beam (aligned_entry false: want_alignment is refused) and tw_generate_beam_aligned; fn names the caller in messages
+static int generate_beam_checked(const char* fn, bool aligned_entry, tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prompt,
+                                 const tw_greedy_opts* o, const tw_beam_opts* bo, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                 int32_t* out_nbest_ids, float* out_nbest_score, int32_t* out_hyp_len, void* stream) {
   if (!c || !prompt || !o || !bo || !out_ids || !out_len) return fail(c, TW_EINVAL, "%s: null argument", fn);
   TW_ON_DEVICE(c);
   const int K = bo->num_beams;
@@ -1773,8 +1778,11 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
     return fail(c, TW_EINVAL, "%s: %d clips x %d beams exceed max_batch %d (or 64 rows)", fn, n, K, c->Bmax);
   if (!std::isfinite(bo->length_penalty)) return fail(c, TW_EINVAL, "%s: length_penalty is NaN or infinite", fn);
   if (bo->early_stopping != 0 && bo->early_stopping != 1) return fail(c, TW_EINVAL, "%s: early_stopping %d outside {0, 1}", fn, bo->early_stopping);
-  if (o->want_alignment || o->n_forced != 0 || o->n_draft != 0)
+  if ((o->want_alignment && !aligned_entry) || o->n_forced != 0 || o->n_draft != 0)
     return fail(c, TW_EINVAL, "%s: want_alignment, n_forced and n_draft do not go with beams", fn);
+  if (o->want_alignment != 0 && o->want_alignment != 1) return fail(c, TW_EINVAL, "%s: want_alignment %d outside {0, 1}", fn, o->want_alignment);
+  const bool rec = o->want_alignment != 0;   // record the alignment rows and the ancestry; gather behind the loop
+  if (rec && c->Ha == 0) return fail(c, TW_EINVAL, "%s: want_alignment but the context has no alignment heads", fn);
   if (c->w8) return fail(c, TW_EINVAL, "%s: fp8 contexts are not supported", fn);
   if (c->P > kBeamSeqMax) return fail(c, TW_EINVAL, "%s: target_positions %d above %d", fn, c->P, kBeamSeqMax);
   if (n > c->cross_B) return fail(c, TW_ESTATE, "%s: %d clips but cross K/V holds %d", fn, n, c->cross_B);
@@ -1794,6 +1802,7 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
   if (!c->beam_tab) ALLOC(c, c->beam_tab, sizeof(int) * words, true);
   if (!c->beam_parts) ALLOC(c, c->beam_parts, sizeof(BeamPartial) * 64 * 32, true);
   if (!c->h_beam) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_beam), sizeof(int) * words));
+  if (rec && !c->beam_anc) ALLOC(c, c->beam_anc, sizeof(int) * ((size_t)kBeamSeqMax * 64 + 64), true);
 
   // ---- initial state, staged in pinned memory (not touched again before the synchronisation at the end of the call) ----
   GenStage& hs = *c->h_stage;
@@ -1843,9 +1852,15 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
   ba.run_score = tf + kBeamRunScore; ba.fin_score = tf + kBeamFinScore; ba.pen = tf + kBeamPen;
   ba.fin_flag = c->beam_tab + kBeamFinFlag; ba.fin_len = c->beam_tab + kBeamFinLen; ba.open = c->beam_tab + kBeamOpen;
   ba.done = c->beam_tab + kBeamDone; ba.beam_idx = c->beam_tab + kBeamIdx; ba.fin_seq = c->beam_tab + kBeamFinSeq;
+  if (rec) {
+    ba.back = c->beam_anc; ba.fin_last = c->beam_anc + (size_t)kBeamSeqMax * 64;
+    HIPCHK(c, hipMemsetAsync(ba.fin_last, 0, sizeof(int) * 64, st));
+  }
 
   const int Pp = (P + 63) / 64 * 64;
-  DecodeOpts step; step.record_alignment = false;   // embeds from cur_ids; the alignment rows of an earlier call stay as they are
+  // embeds from cur_ids; without want_alignment the alignment rows of an earlier call stay as they are, with it every beam's rows
+  // are recorded where the beam sits (prompt steps included) and gathered along the ancestry once the loop is over
+  DecodeOpts step; step.record_alignment = rec;
   tic(c, 3, st);
   constexpr int LAG = 2;
   int steps = 0;
@@ -1876,6 +1891,7 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
   }
   toc(c, 3, st);
   c->last_steps = steps;
+  if (rec) HIPCHK(c, launch_beam_align_gather(c->align, c->Ha, P, c->T, max_len - 1, ba, st));
   HIPCHK(c, hipMemcpyAsync(hb, c->beam_tab, sizeof(int) * (kBeamFinSeq + (size_t)rows * P), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
 
@@ -1897,6 +1913,7 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
     for (int k = 0; k < K; ++k) {
       if (out_nbest_ids) emit(k * n + b, out_nbest_ids + ((size_t)b * K + k) * out_ld);
       if (out_nbest_score) out_nbest_score[(size_t)b * K + k] = hbf[kBeamFinScore + k * n + b];
+      if (out_hyp_len) out_hyp_len[(size_t)b * K + k] = std::min(std::max(hb[kBeamFinLen + k * n + b], n_prompt), max_len);
     }
   }
   out_len[0] = L_best;   // (two entries, always: the header says so)
@@ -1904,6 +1921,19 @@ int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prom
   c->last_seq_len = L_best;
   c->last_n_prompt = n_prompt;
   return TW_OK;
+}
+
+int tw_generate_beam(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_beam_opts* bo,
+                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_nbest_ids, float* out_nbest_score, void* stream) {
+  return generate_beam_checked("tw_generate_beam", false, c, n, prompt, n_prompt, o, bo, out_ids, out_len, out_score, out_nbest_ids,
+                               out_nbest_score, nullptr, stream);
+}
+
+int tw_generate_beam_aligned(tw_ctx* c, int32_t n, const int32_t* prompt, int32_t n_prompt, const tw_greedy_opts* o, const tw_beam_opts* bo,
+                             int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_nbest_ids, float* out_nbest_score,
+                             int32_t* out_hyp_len, void* stream) {
+  return generate_beam_checked("tw_generate_beam_aligned", true, c, n, prompt, n_prompt, o, bo, out_ids, out_len, out_score, out_nbest_ids,
+                               out_nbest_score, out_hyp_len, stream);
 }
 
 // tw_generate_sample and tw_generate_sample_filtered (fn names the caller in messages); fo == nullptr: no filter
@@ -2078,6 +2108,22 @@ int tw_set_alignment(tw_ctx* c, int32_t B, int32_t n_rows, const float* in_host,
   return TW_OK;
 }
 
+// Columns of the alignment matrix a stream keeps (num_frames NULL: all T).  HF crops with the Python slice
+// `weights[..., : num_frames // 2]` (HF:models/whisper/generation_whisper.py:346-349): floor division, and a NEGATIVE bound
+// (num_frames - seek < 0 happens in the seek loop for clips shorter than the chunk) counts from the end.  Reproduced literally so
+// token timestamps stay identical to the reference.
+static int kept_columns(int T, const int32_t* num_frames) {
+  int nc = T;
+  if (num_frames) {
+    const int nf = *num_frames;
+    nc = (nf >= 0) ? nf / 2 : -((-nf + 1) / 2);   // floor(nf / 2)
+    if (nc < 0) nc += T;
+  }
+  if (nc > T) nc = T;
+  if (nc < 0) nc = 0;    // nothing left: HF's DTW on the empty matrix puts every token at time index -1 (dtw_kernel)
+  return nc;
+}
+
 int tw_token_timestamps(tw_ctx* c, int32_t B, int32_t n_prompt, int32_t seq_len, const int32_t* num_frames_host,
                         double time_precision, float* out_ts_host, void* stream) {
   if (!c || !out_ts_host) return fail(c, TW_EINVAL, "tw_token_timestamps: null argument");
@@ -2087,20 +2133,7 @@ int tw_token_timestamps(tw_ctx* c, int32_t B, int32_t n_prompt, int32_t seq_len,
     return fail(c, TW_EINVAL, "bad B/n_prompt/seq_len (%d,%d,%d)", B, n_prompt, seq_len);
   hipStream_t st = pick_stream(c, stream);
   std::vector<int> cols(B);
-  for (int b = 0; b < B; ++b) {
-    // HF crops with the Python slice `weights[..., : num_frames // 2]` (HF:models/whisper/generation_whisper.py:346-349):
-    // floor division, and a NEGATIVE bound (num_frames - seek < 0 happens in the seek loop for clips shorter than the
-    // chunk) counts from the end.  Reproduced literally so token timestamps stay identical to the reference.
-    int nc = c->T;
-    if (num_frames_host) {
-      const int nf = num_frames_host[b];
-      nc = (nf >= 0) ? nf / 2 : -((-nf + 1) / 2);   // floor(nf / 2)
-      if (nc < 0) nc += c->T;
-    }
-    if (nc > c->T) nc = c->T;
-    if (nc < 0) nc = 0;    // nothing left: HF's DTW on the empty matrix puts every token at time index -1 (dtw_kernel)
-    cols[b] = nc;
-  }
+  for (int b = 0; b < B; ++b) cols[b] = kept_columns(c->T, num_frames_host ? &num_frames_host[b] : nullptr);
   HIPCHK(c, hipMemcpy(c->n_cols, cols.data(), sizeof(int) * B, hipMemcpyHostToDevice));
   DtwArgs a{};
   a.align = c->align; a.Ha = c->Ha; a.P = c->P; a.T = c->T; a.B = B; a.n_prompt = n_prompt; a.n_rows = seq_len - 1;
@@ -2112,6 +2145,48 @@ int tw_token_timestamps(tw_ctx* c, int32_t B, int32_t n_prompt, int32_t seq_len,
   toc(c, 4, st);
   HIPCHK(c, hipMemcpyAsync(out_ts_host, c->out_ts, sizeof(float) * (size_t)B * seq_len, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
+  return TW_OK;
+}
+
+int tw_token_timestamps_each(tw_ctx* c, int32_t B, int32_t n_prompt, const int32_t* seq_len_host, int32_t ld, const int32_t* num_frames_host,
+                             double time_precision, float* out_ts_host, void* stream) {
+  const char* fn = "tw_token_timestamps_each";
+  if (!c || !out_ts_host || !seq_len_host) return fail(c, TW_EINVAL, "%s: null argument", fn);
+  TW_ON_DEVICE(c);
+  if (c->Ha == 0) return fail(c, TW_EINVAL, "context has no alignment heads");
+  if (B < 1 || B > c->Bmax || ld < 1 || n_prompt < 1) return fail(c, TW_EINVAL, "%s: bad B/n_prompt/ld (%d,%d,%d)", fn, B, n_prompt, ld);
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (seq_len_host[b] < 0 || seq_len_host[b] > ld || seq_len_host[b] > c->P)
+      return fail(c, TW_EINVAL, "%s: seq_len[%d] = %d outside [0, min(ld = %d, target_positions = %d)]", fn, b, seq_len_host[b], ld, c->P);
+    longest = std::max(longest, seq_len_host[b]);
+  }
+  hipStream_t st = pick_stream(c, stream);
+  if (!c->dtw_len) ALLOC(c, c->dtw_len, sizeof(int) * c->Bmax, true);
+  std::vector<int> cols(B);
+  for (int b = 0; b < B; ++b) cols[b] = kept_columns(c->T, num_frames_host ? &num_frames_host[b] : nullptr);
+  HIPCHK(c, hipMemcpy(c->n_cols, cols.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->dtw_len, seq_len_host, sizeof(int) * B, hipMemcpyHostToDevice));
+  const int dld = std::min((int)ld, c->P + 1);   // entries per row on the device (out_ts holds P + 1); the rest repeats on the host
+  DtwArgs a{};
+  a.align = c->align; a.Ha = c->Ha; a.P = c->P; a.T = c->T; a.B = B; a.n_prompt = n_prompt; a.n_rows = std::max(longest, n_prompt + 1) - 1;
+  a.n_cols = c->n_cols; a.median_width = 7; a.zbuf = c->zbuf; a.mat = c->mat; a.trace = c->trace; a.out_ts = c->out_ts;
+  a.time_precision = time_precision;
+  a.row_len = c->dtw_len; a.out_ld = dld;
+  if (a.n_rows + 1 > c->P) a.n_rows = c->P - 1;   // (n_prompt >= target_positions: every row then has N_b <= 0)
+  tic(c, 4, st);
+  HIPCHK(c, launch_token_timestamps(a, st));
+  toc(c, 4, st);
+  if (dld == ld) {
+    HIPCHK(c, hipMemcpyAsync(out_ts_host, c->out_ts, sizeof(float) * (size_t)B * ld, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  } else {
+    std::vector<float> tmp((size_t)B * dld);
+    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->out_ts, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+      for (int k = 0; k < ld; ++k) out_ts_host[(size_t)b * ld + k] = tmp[(size_t)b * dld + std::min(k, dld - 1)];
+  }
   return TW_OK;
 }
 

@@ -2508,11 +2508,15 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(BeamArgs ba) {
       const int r = tid * n + c;
       a.cur_ids[r] = a.seq[r * ld + cur];
       ba.beam_idx[r] = tid;
+      if (ba.back) ba.back[(cur - 1) * 64 + r] = tid;
     }
     return;
   }
   if (ba.done[c] != 0) {   // frozen
-    if (tid < K) ba.beam_idx[tid * n + c] = tid;
+    if (tid < K) {
+      ba.beam_idx[tid * n + c] = tid;
+      if (ba.back) ba.back[(cur - 1) * 64 + tid * n + c] = tid;
+    }
     return;
   }
   for (int idx = tid; idx < K * (cur + 1); idx += 512) {
@@ -2638,6 +2642,11 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(BeamArgs ba) {
     }
     ba.open[c] = open1 ? 1 : 0;
     ba.done[c] = (!open1 || (ba.early && all_new_fin) || all_hit) ? 1 : 0;   // step 9
+    if (ba.fin_last) {   // a finished entry keeps the beam that produced its last token as it moves through the set
+      int old_last[kBeamMax];
+      for (int kk = 0; kk < K; ++kk) old_last[kk] = ba.fin_last[kk * n + c];
+      for (int kk = 0; kk < K; ++kk) ba.fin_last[kk * n + c] = fin_src[kk] < K ? old_last[fin_src[kk]] : cand_b[fin_src[kk] - K];
+    }
   }
   __syncthreads();
   // ---- the new histories, gathered from the LDS copies ----
@@ -2657,6 +2666,74 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(BeamArgs ba) {
     a.cur_ids[r] = tok;
     ba.beam_idx[r] = src;
     ba.run_score[r] = run_new_s[tid];
+    if (ba.back) ba.back[(cur - 1) * 64 + r] = src;
+  }
+}
+
+// The alignment rows follow the finished hypotheses (tw_generate_beam_aligned), in place, one launch behind the loop.  The cross
+// attention wrote row (slot, position) once, for the beam that sat in the slot when the position was consumed, and the loop never moved
+// a row; BeamArgs::back holds who continued whom.  Hypothesis k of a clip, of `len` tokens: its row at position len - 2 is in the slot
+// fin_last[k], and the row at position p - 1 in slot back[p - 1][slot of p].  Workgroup = (PCH positions, alignment head, clip): the
+// clip's back-pointers from the chunk's first position on are staged in LDS as bytes (4 KiB for 512 positions), thread k walks
+// hypothesis k down to the chunk and leaves the source slot of each of its positions (-1: nothing to copy - the row is in place, behind
+// the hypothesis's end, or the entry is a placeholder).  Then, per position, a thread loads the elements it owns from ALL K sources
+// before it stores any: two hypotheses may share a source and a destination may be another one's source (beam_reorder_kernel's
+// pattern; no other thread touches those addresses).  VEC 4: 16-byte accesses, taken only when T % 4 == 0 (every row then starts on a
+// 16-byte boundary); VEC 1 otherwise.  No atomics.
+constexpr int kAlignGatherPos = 4;
+template <int VEC>
+__global__ __launch_bounds__(256) void beam_align_gather_kernel(float* align, int Ha, int P, int T, int n_pos, BeamArgs ba) {
+  __shared__ unsigned char sh_back[kBeamSeqMax][kBeamMax];
+  __shared__ int sh_src[kAlignGatherPos][kBeamMax];
+  using vec_t = typename std::conditional<VEC == 4, u32x4_t, float>::type;
+  const int p0 = blockIdx.x * kAlignGatherPos, h = blockIdx.y, c = blockIdx.z, n = ba.n_clips, K = ba.K;
+  const int tid = threadIdx.x;
+  const int n0 = ba.s.stt->n_prompt;
+  const int hi = min(n_pos, kBeamSeqMax);   // positions [p0, hi) may be walked
+  for (int idx = tid; idx < (hi - p0) * K; idx += 256) {
+    const int s = p0 + idx / K, k = idx % K;
+    const int b = ba.back[s * 64 + k * n + c];
+    sh_back[s][k] = (unsigned char)((b >= 0 && b < K) ? b : k);
+  }
+  if (tid < kAlignGatherPos * kBeamMax) sh_src[tid / kBeamMax][tid % kBeamMax] = -1;
+  __syncthreads();
+  if (tid < K) {
+    const int r = tid * n + c;
+    const int len = min(max(ba.fin_len[r], n0), ba.max_len);
+    const bool live = ba.fin_score[r] > -1e9f && len >= 2;
+    int b = ba.fin_last[r];
+    b = (b >= 0 && b < K) ? b : tid;
+    if (live && len - 2 >= p0) {
+      for (int p = min(len - 2, hi - 1); p >= p0; --p) {   // (len - 2 <= hi - 1 always: a finished entry ends inside the loop's positions)
+        if (p < p0 + kAlignGatherPos && b != tid) sh_src[p - p0][tid] = b;
+        if (p > p0) b = sh_back[p - 1][b];
+      }
+    }
+  }
+  __syncthreads();
+  const int TV = T / VEC;
+  for (int pl = 0; pl < kAlignGatherPos; ++pl) {
+    const int p = p0 + pl;
+    if (p >= hi) break;
+    int src[kBeamMax];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < kBeamMax; ++k) {
+      src[k] = sh_src[pl][k];
+      any = any || src[k] >= 0;
+    }
+    if (!any) continue;   // (workgroup-uniform)
+    vec_t* base = reinterpret_cast<vec_t*>(align + ((long long)h * P + p) * T);
+    const long long slot_vec = (long long)Ha * P * T / VEC;
+    for (int t = tid; t < TV; t += 256) {
+      vec_t val[kBeamMax];
+#pragma unroll
+      for (int k = 0; k < kBeamMax; ++k)
+        if (src[k] >= 0) val[k] = base[(long long)(src[k] * n + c) * slot_vec + t];
+#pragma unroll
+      for (int k = 0; k < kBeamMax; ++k)
+        if (src[k] >= 0) base[(long long)(k * n + c) * slot_vec + t] = val[k];
+    }
   }
 }
 
@@ -3127,6 +3204,18 @@ hipError_t launch_beam_cross_copy(void* ck, void* cv, long long layer_bytes, lon
   const long long slot_vec = slot_bytes / 16;
   hipLaunchKernelGGL(beam_cross_copy_kernel, dim3((unsigned)((slot_vec + 1023) / 1024), (K - 1) * n_clips, Ld * 2), dim3(256), 0, st, (u32x4_t*)ck,
                      (u32x4_t*)cv, layer_bytes / 16, slot_vec, n_clips);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_align_gather(float* align, int Ha, int P, int T, int n_pos, const BeamArgs& a, hipStream_t st) {
+  if (!align || !a.back || !a.fin_last || !a.fin_len || !a.fin_score || !a.s.stt || Ha < 1 || T < 1 || a.K < 2 || a.K > kBeamMax ||
+      a.n_clips < 1 || a.n_clips * a.K > 64 || n_pos < 1 || n_pos >= P || P > kBeamSeqMax || a.max_len != n_pos + 1)
+    return hipErrorInvalidValue;
+  const dim3 grid((n_pos + kAlignGatherPos - 1) / kAlignGatherPos, Ha, a.n_clips);
+  if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(align) & 15) == 0)
+    hipLaunchKernelGGL(beam_align_gather_kernel<4>, grid, dim3(256), 0, st, align, Ha, P, T, n_pos, a);
+  else
+    hipLaunchKernelGGL(beam_align_gather_kernel<1>, grid, dim3(256), 0, st, align, Ha, P, T, n_pos, a);
   return hipGetLastError();
 }
 

@@ -14,12 +14,24 @@
 
 namespace {
 
+// EACH (DtwArgs::row_len set, tw_token_timestamps_each): stream b uses its own N_b = row_len[b] - 1 - n_prompt rows; the workspaces keep
+// the strides of the call's longest row (a.n_rows), so a row's arithmetic is the one a call for it alone runs.  EACH == false is the
+// code of the common-length call, unchanged.
+template <bool EACH>
+__device__ __forceinline__ int dtw_rows(const DtwArgs& a, int b) {
+  if constexpr (EACH) return a.row_len[b] - 1 - a.n_prompt;
+  else return a.n_rows - a.n_prompt;
+}
+
+template <bool EACH>
 __global__ void align_zscore_kernel(DtwArgs a) {
   const int b = blockIdx.z, hd = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int M = a.n_cols[b];
-  const int N = a.n_rows - a.n_prompt;
+  const int N = dtw_rows<EACH>(a, b);
+  const int NS = a.n_rows - a.n_prompt;   // workspace stride (== N unless EACH)
   if (j >= M) return;
+  if (EACH && N <= 0) return;
   const float* src = a.align + (((long long)b * a.Ha + hd) * a.P + a.n_prompt) * a.T + j;
   float s = 0.f;
   for (int i = 0; i < N; ++i) s += src[(long long)i * a.T];
@@ -27,7 +39,7 @@ __global__ void align_zscore_kernel(DtwArgs a) {
   float q = 0.f;
   for (int i = 0; i < N; ++i) { const float c = src[(long long)i * a.T] - mean; q += c * c; }
   const float sd = sqrtf(q / (float)N);
-  float* dst = a.zbuf + (((long long)b * a.Ha + hd) * N) * a.T + j;
+  float* dst = a.zbuf + (((long long)b * a.Ha + hd) * NS) * a.T + j;
   for (int i = 0; i < N; ++i) dst[(long long)i * a.T] = (src[(long long)i * a.T] - mean) / sd;
 }
 
@@ -40,12 +52,14 @@ __device__ __forceinline__ void cswap(float& x, float& y) {
   x = lo; y = hi;
 }
 
+template <bool EACH>
 __global__ void align_median_mean_kernel(DtwArgs a) {
   const int b = blockIdx.z, i = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int M = a.n_cols[b];
-  const int N = a.n_rows - a.n_prompt;
+  const int N = a.n_rows - a.n_prompt;   // workspace stride; the grid has one y per row of the longest stream
   if (j >= M) return;
+  if (EACH && i >= dtw_rows<EACH>(a, b)) return;
   const int pad = a.median_width / 2;  // width 7 supported (config.median_filter_width default)
   float acc = 0.f;
   for (int hd = 0; hd < a.Ha; ++hd) {
@@ -76,23 +90,25 @@ __global__ void align_median_mean_kernel(DtwArgs a) {
   a.mat[((long long)b * N + i) * a.T + j] = acc / (float)a.Ha;
 }
 
+template <bool EACH>
 __global__ __launch_bounds__(512) void dtw_kernel(DtwArgs a) {
   __shared__ float diag[3][512];
   __shared__ float jump[512];
   const int b = blockIdx.x;
   const int i = threadIdx.x;
   const int M = a.n_cols[b];
-  const int N = a.n_rows - a.n_prompt;
-  float* ts = a.out_ts + (long long)b * (a.n_rows + 1);
+  const int N = dtw_rows<EACH>(a, b);
+  const int n_out = EACH ? a.out_ld : a.n_rows + 1;   // entries of the stream's output row
+  float* ts = a.out_ts + (long long)b * n_out;
   if (N <= 0 || M <= 0) {
     // M == 0 (every column cropped away): the reference still runs its DTW, on an [N, 0] matrix - the back-trace walks the
     // token axis at time index -1 (HF:models/whisper/generation_whisper.py:88-115), so every generated token (and the
     // duplicate of the last one) gets -1 * time_precision; the prompt positions stay 0
     const float v = (N > 0) ? (float)(-1.0 * a.time_precision) : 0.f;
-    for (int k = i; k < a.n_rows + 1; k += 512) ts[k] = k >= a.n_prompt ? v : 0.f;
+    for (int k = i; k < n_out; k += 512) ts[k] = k >= a.n_prompt ? v : 0.f;
     return;
   }
-  const float* mat = a.mat + (long long)b * N * a.T;
+  const float* mat = a.mat + (long long)b * (a.n_rows - a.n_prompt) * a.T;
   signed char* trace = a.trace + (long long)b * (long long)(a.P + 1) * (a.T + 1);
   const int W = M + 1;
   const float INF = INFINITY;
@@ -136,7 +152,7 @@ __global__ __launch_bounds__(512) void dtw_kernel(DtwArgs a) {
     }
   }
   __syncthreads();
-  for (int k = i; k < a.n_rows + 1; k += 512) {
+  for (int k = i; k < n_out; k += 512) {
     float v = 0.f;
     if (k >= a.n_prompt) {
       const int r = k - a.n_prompt;
@@ -148,20 +164,28 @@ __global__ __launch_bounds__(512) void dtw_kernel(DtwArgs a) {
 
 }  // namespace
 
+template <bool EACH>
+static hipError_t token_timestamps_go(const DtwArgs& a, hipStream_t st) {
+  const int N = a.n_rows - a.n_prompt;   // EACH: of the longest stream
+  if (N > 0) {
+    dim3 g1((a.T + 255) / 256, a.Ha, a.B);
+    hipLaunchKernelGGL(align_zscore_kernel<EACH>, g1, dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    dim3 g2((a.T + 255) / 256, N, a.B);
+    hipLaunchKernelGGL(align_median_mean_kernel<EACH>, g2, dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(dtw_kernel<EACH>, dim3(a.B), dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_token_timestamps(const DtwArgs& a, hipStream_t st) {
   const int N = a.n_rows - a.n_prompt;
   if (a.B <= 0) return hipSuccess;
   if (N > 511 || a.median_width != 7) return hipErrorInvalidValue;
-  if (N > 0) {
-    dim3 g1((a.T + 255) / 256, a.Ha, a.B);
-    hipLaunchKernelGGL(align_zscore_kernel, g1, dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    dim3 g2((a.T + 255) / 256, N, a.B);
-    hipLaunchKernelGGL(align_median_mean_kernel, g2, dim3(256), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dtw_kernel, dim3(a.B), dim3(512), 0, st, a);
-  return hipGetLastError();
+  if (!a.row_len) return token_timestamps_go<false>(a, st);
+  if (a.out_ld < 1 || a.n_rows + 1 > a.P || a.n_prompt < 1) return hipErrorInvalidValue;
+  return token_timestamps_go<true>(a, st);
 }

@@ -493,6 +493,10 @@ struct BeamArgs {
   int* done;                 // [n_clips]
   int* beam_idx;             // [rows]: the beam whose cache rows beam k continues from (identity while the prompt lasts and once done)
   const float* pen;          // [seq_ld + 1]: pen[g] = (float)pow((double)g, (double)length_penalty), host-tabulated
+  // tw_generate_beam_aligned with want_alignment (both NULL otherwise: the step then stores nothing more).  The ancestry of the
+  // alignment rows, which are recorded per (slot, position) and never moved while the loop runs:
+  int* back;                 // [kBeamSeqMax][64]: back[s][row] = beam_idx[row] as the step that consumed position s left it
+  int* fin_last;             // [rows]: the beam whose logits produced the last token of finished hypothesis k (it moves with the entry)
 };
 // part + finish; the position is NOT advanced (the reorder reads it): launch_beam_reorder, then launch_advance
 hipError_t launch_beam_step(const BeamArgs& a, bool in_prompt, hipStream_t st);
@@ -503,6 +507,10 @@ hipError_t launch_beam_reorder(int dtype, void* kc, void* vc, long long layer_st
 // cross K / V of clip c (slot c) -> slots k * n_clips + c, k = 1 .. K-1, every layer, one launch of 16-byte copies; the source slots
 // are only read
 hipError_t launch_beam_cross_copy(void* ck, void* cv, long long layer_bytes, long long slot_bytes, int Ld, int n_clips, int K, hipStream_t st);
+// alignment rows follow the finished hypotheses (beam_align_gather_kernel), one launch, in place: afterwards slot k * n_clips + c of
+// align [slots][Ha][P][T] holds rows 0 .. fin_len - 2 of finished hypothesis k of clip c (placeholders are left alone).  n_pos: the
+// positions the loop consumed at most (max_len - 1)
+hipError_t launch_beam_align_gather(float* align, int Ha, int P, int T, int n_pos, const BeamArgs& a, hipStream_t st);
 
 // A11: alignment rows -> token timestamps
 struct DtwArgs {
@@ -515,6 +523,10 @@ struct DtwArgs {
   signed char* trace;  // [B][(N+1)*(T+1)]
   float* out_ts;   // [B][n_rows + 1]
   double time_precision;
+  // tw_token_timestamps_each: row_len[b] = tokens of stream b (device, [B]; NULL = every stream has n_rows + 1 and the kernels run the
+  // common-length code).  With it, n_rows = (longest row_len) - 1 sizes the grid and the workspace strides, stream b uses rows
+  // [n_prompt, row_len[b] - 1), and out_ts is [B][out_ld]: entries from row_len[b] - 1 on repeat the stream's last jump time.
+  const int* row_len; int out_ld;
 };
 hipError_t launch_token_timestamps(const DtwArgs& a, hipStream_t st);
 

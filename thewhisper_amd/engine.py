@@ -613,19 +613,23 @@ class WhisperEngine:
     def generate_beam(self, prompt: np.ndarray, num_beams: int, length_penalty: float = 1.0, early_stopping: bool = False, *,
                       max_new_tokens: int = 128, min_new_tokens: int = 0, max_length: int = 448, eos_id: int = 50257, pad_id: int = 50257,
                       timestamps: bool = False, no_timestamps_id: int = 50364, max_initial_timestamp_index: Optional[int] = 50,
-                      begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = ()) -> Dict[str, np.ndarray]:
+                      begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = (),
+                      want_alignment: bool = False) -> Dict[str, np.ndarray]:
         """Beam search with ``num_beams`` (2..8) beams per row of ``prompt`` (tw_generate_beam, where the rule - HF's
         ``GenerationMixin._beam_search`` - is stated).  Needs ``max_batch >= rows x num_beams``.  ``sequences`` int64 [n, L]: the best
         hypotheses; ``scores`` float32 [n]; ``nbest_sequences`` int64 [n, K, Ln] and ``nbest_scores`` float32 [n, K]: every hypothesis in
         descending score (a score <= -1e9 marks a placeholder).  Everything behind a hypothesis's end is ``pad_id``.  The other
-        keywords are ``generate_greedy``'s processors."""
+        keywords are ``generate_greedy``'s processors.  ``lengths`` int32 [n] and ``nbest_lengths`` int32 [n, K]: the tokens of every
+        hypothesis, prompt included (the prompt's for a placeholder).
+        ``want_alignment``: the call is tw_generate_beam_aligned - same ids and scores, and afterwards slot ``k * n + c`` of the
+        alignment buffer holds the rows of hypothesis k of clip c (``beam_token_timestamps``, ``get_alignment``)."""
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         n, n0 = prompt.shape
         K = int(num_beams)
         if early_stopping not in (False, True, 0, 1):
             raise ValueError(f"early_stopping must be False or True, got {early_stopping!r}")
         o, _keep = self._greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress,
-                                     min_new_tokens, max_new_tokens, max_length)
+                                     min_new_tokens, max_new_tokens, max_length, bool(want_alignment))
         bo = _cabi.tw_beam_opts()
         bo.num_beams, bo.length_penalty, bo.early_stopping = K, float(length_penalty), 1 if early_stopping else 0
         ld = int(max_length)
@@ -635,14 +639,16 @@ class WhisperEngine:
         nscore = np.zeros((n, max(K, 1)), dtype=np.float32)
         out_len = (C.c_int32 * 2)(0, 0)
         i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-        rc = self.lib.tw_generate_beam(self.ctx, n, prompt.ctypes.data_as(i32p), n0, C.byref(o), C.byref(bo), out.ctypes.data_as(i32p),
-                                       out_len, score.ctypes.data_as(f32p), nbest.ctypes.data_as(i32p), nscore.ctypes.data_as(f32p),
-                                       self._loop_stream())
-        self._chk(rc, "tw_generate_beam")
+        hyp_len = np.full((n, max(K, 1)), n0, dtype=np.int32)
+        rc = self.lib.tw_generate_beam_aligned(self.ctx, n, prompt.ctypes.data_as(i32p), n0, C.byref(o), C.byref(bo),
+                                               out.ctypes.data_as(i32p), out_len, score.ctypes.data_as(f32p), nbest.ctypes.data_as(i32p),
+                                               nscore.ctypes.data_as(f32p), hyp_len.ctypes.data_as(i32p), self._loop_stream())
+        self._chk(rc, "tw_generate_beam_aligned")
         self._release_held()
         L, Ln = int(out_len[0]), int(out_len[1])
+        self._last_beam = {"n": n, "K": K, "n_prompt": n0, "lengths": hyp_len.copy(), "L": L, "Ln": Ln, "aligned": bool(want_alignment)}
         return {"sequences": out[:, :L].astype(np.int64), "scores": score, "nbest_sequences": nbest[:, :, :Ln].astype(np.int64),
-                "nbest_scores": nscore, "length": L}
+                "nbest_scores": nscore, "length": L, "lengths": hyp_len[:, 0].copy(), "nbest_lengths": hyp_len}
 
     # ---- temperature sampling ----------------------------------------------------------------
     def generate_sample(self, prompt: np.ndarray, temperature, seed, offset=None, *, max_new_tokens: int = 128, min_new_tokens: int = 0,
@@ -726,6 +732,41 @@ class WhisperEngine:
                                           out.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
         self._chk(rc, "tw_token_timestamps")
         return out
+
+    def token_timestamps_each(self, seq_lens: Sequence[int], n_prompt: int, num_frames: Optional[Sequence[int]] = None,
+                              time_precision: float = 0.02, ld: Optional[int] = None) -> np.ndarray:
+        """``token_timestamps`` for rows of different lengths (tw_token_timestamps_each): row b of the alignment buffer holds
+        ``seq_lens[b]`` tokens; float32 [B, ld] (``ld``: the longest row unless given).  A row's first ``seq_lens[b]`` entries are what
+        ``token_timestamps`` returns for it alone; the entries behind repeat its last one; a row with nothing generated is zeros."""
+        lens = np.ascontiguousarray(np.asarray(seq_lens, dtype=np.int32).reshape(-1))
+        B = int(lens.shape[0])
+        ld = int(ld) if ld is not None else max(int(lens.max()), 1)
+        out = np.zeros((B, ld), dtype=np.float32)
+        nf = None
+        if num_frames is not None:
+            nf = (C.c_int32 * B)(*[int(x) for x in num_frames])
+        rc = self.lib.tw_token_timestamps_each(self.ctx, B, int(n_prompt), lens.ctypes.data_as(C.POINTER(C.c_int32)), ld, nf,
+                                               float(time_precision), out.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
+        self._chk(rc, "tw_token_timestamps_each")
+        return out
+
+    def beam_token_timestamps(self, nbest: bool = False, num_frames: Optional[Sequence[int]] = None,
+                              time_precision: float = 0.02) -> np.ndarray:
+        """Token timestamps of the most recent ``generate_beam(want_alignment=True)``: float32 [n, L] for the best hypotheses, or
+        [n, K, Ln] for every hypothesis (``nbest``) - each by the rule of tw_generate_beam_aligned, i.e. on its own rows, as if its clip
+        had been decoded alone.  ``num_frames``: one value per clip."""
+        st = getattr(self, "_last_beam", None)
+        if st is None or not st["aligned"]:
+            raise RuntimeError("beam_token_timestamps needs a generate_beam(want_alignment=True) call before it")
+        n, K, n0 = st["n"], st["K"], st["n_prompt"]
+        if num_frames is not None and len(num_frames) != n:
+            raise ValueError(f"num_frames has {len(num_frames)} entries for {n} clips")
+        if not nbest:
+            return self.token_timestamps_each(st["lengths"][:, 0], n0, num_frames, time_precision, ld=st["L"])
+        lens = st["lengths"].T.reshape(-1)             # slot k * n + c
+        nf = None if num_frames is None else [int(num_frames[c]) for _ in range(K) for c in range(n)]
+        ts = self.token_timestamps_each(lens, n0, nf, time_precision, ld=st["Ln"])
+        return np.ascontiguousarray(ts.reshape(K, n, -1).transpose(1, 0, 2))
 
     def get_alignment(self, B: int, n_rows: int) -> np.ndarray:
         out = np.zeros((B, len(self.alignment_heads), n_rows, self.T), dtype=np.float32)

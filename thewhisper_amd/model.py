@@ -12,7 +12,8 @@ slicing - per chunk, host side) and replaces everything underneath it:
   loop with the Whisper logits processors on the GPU (A2-A10).
 * ``_extract_token_timestamps`` is overridden with the on-device median-filter + DTW (A11).
 
-Beam search (``num_beams`` 2..8) runs on the device once ``model.beam_search = True`` (opt-in; ``_beam_generate``).  Unsupported
+Beam search (``num_beams`` 2..8) runs on the device once ``model.beam_search = True`` (opt-in; ``_beam_generate``); with
+``model.beam_token_timestamps = True`` as well, token / word timestamps of a beam call are served from per-row lengths.  Unsupported
 generation options (sampling through this seam, custom processors ...) raise ``NotImplementedError``: there is no eager/CPU fallback.
 """
 from __future__ import annotations
@@ -177,8 +178,11 @@ class _EngineGreedyMixin(GenerationMixin):
 
     def _beam_generate(self, eng, gc, inputs, decoder_input_ids, num_beams, opts, bias, repeat, n_pad, kwargs, limits):
         """``num_beams`` > 1 with ``beam_search = True``: HF's ``_beam_search`` on the device (tw_generate_beam), the best hypothesis per
-        row.  What the beam call cannot do is refused by name."""
-        if getattr(gc, "return_token_timestamps", False) or kwargs.get("return_token_timestamps"):
+        row.  What the beam call cannot do is refused by name.  ``return_token_timestamps`` with ``beam_token_timestamps = True``: the
+        call records and gathers the alignment rows (tw_generate_beam_aligned) and leaves the rows' lengths for
+        ``_extract_token_timestamps``."""
+        want_align = bool(getattr(gc, "return_token_timestamps", False) or kwargs.get("return_token_timestamps"))
+        if want_align and not getattr(self, "beam_token_timestamps", False):
             raise NotImplementedError("return_token_timestamps with num_beams > 1: a beam result has no alignment rows on the MI355X engine")
         if bias:
             raise NotImplementedError("sequence_bias with num_beams > 1")
@@ -196,9 +200,13 @@ class _EngineGreedyMixin(GenerationMixin):
         eng.encode(inputs)
         eng.cross_kv(B)
         prompt = decoder_input_ids.detach().to("cpu", torch.int32).numpy()
+        if want_align:   # (only then: an engine without the keyword keeps serving the plain beam call)
+            opts = dict(opts, want_alignment=True)
         out = eng.generate_beam(prompt, num_beams, 1.0 if lp is None else float(lp), bool(early), **limits, **opts)
         seq = torch.from_numpy(out["sequences"]).to(decoder_input_ids.device, torch.long)
         self._last_greedy = {"B": B, "n_prompt": int(prompt.shape[1]), "len": int(seq.shape[1])}
+        if want_align:   # _extract_token_timestamps serves this call from per-row lengths
+            self._last_greedy["lengths"] = [int(x) for x in out["lengths"]]
         if getattr(gc, "return_dict_in_generate", False):
             from transformers.generation.utils import GenerateBeamEncoderDecoderOutput
 
@@ -400,6 +408,10 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
     #: opt-in: ``num_beams`` 2..8 runs HF's beam search on the device (tw_generate_beam) and returns the best hypothesis per row; False:
     #: ``num_beams > 1`` raises NotImplementedError as before.  Needs an engine with ``max_batch >= batch x num_beams``.
     beam_search: bool = False
+    #: opt-in, with ``beam_search``: ``return_token_timestamps`` of a beam call is served (tw_generate_beam_aligned records every beam's
+    #: alignment rows and gathers them along the ancestry; each row is timed as HF times it when its clip is decoded alone - NOT as HF's
+    #: batched beam call, which mixes row 0 of the batch into the shorter hypotheses).  False: the NotImplementedError as before.
+    beam_token_timestamps: bool = False
 
     _FAST_KW = {"input_features", "attention_mask", "generation_config", "return_timestamps", "return_token_timestamps",
                 "return_segments", "language", "task", "is_multilingual", "use_cache", "num_beams", "do_sample",
@@ -541,6 +553,11 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         from .shortform import columns_as_num_frames, hf_kept_columns
 
         nf = None if num_frames is None else columns_as_num_frames(hf_kept_columns(num_frames, B, int(eng.T)))
+        if st.get("lengths") is not None:
+            # a beam call (beam_token_timestamps): every best hypothesis on its own rows, as HF times it when its clip is decoded alone
+            # (tw_generate_beam_aligned, THE RULE; HF's batched call mixes global row 0 into the shorter hypotheses)
+            ts = eng.token_timestamps_each(st["lengths"], n_in, nf, time_precision, ld=L)
+            return torch.from_numpy(ts).to(seq.device)
         if L - 1 <= n_in:  # one generated token: no cross-attention rows after the prompt -> zeros (HF :341-344)
             return torch.zeros((B, L), dtype=torch.float32, device=seq.device)
         ts = eng.token_timestamps(B, n_in, L, nf, time_precision)

@@ -46,6 +46,7 @@ class AMDWhisperBackend:
         hotword_boost: Optional[float] = None,
         repetition_penalty: Optional[float] = None,
         no_repeat_ngram_size: Optional[int] = None,
+        num_beams: Optional[int] = None,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -100,9 +101,36 @@ class AMDWhisperBackend:
         this backend applies them on the device (tw_generate_greedy_repeat, where the rule is stated: HF's two processors behind the
         sequence bias and ahead of Whisper's own).  They travel as generate options, so they are part of the learned short-form plan.
         ``draft_previous_tick`` stays on - the call returns the same ids whatever the draft - and hotwords go with them.  Not together
-        with ``temperature_fallback`` or ``token_scores``: the sampler and the re-scoring pass do not know the rule."""
+        with ``temperature_fallback`` or ``token_scores``: the sampler and the re-scoring pass do not know the rule.
+
+        ``num_beams`` (opt-in; 2..8): every decode is a beam search on the device with word timestamps of the best hypothesis
+        (tw_generate_beam_aligned; the model's ``beam_search`` and ``beam_token_timestamps`` are switched on and ``num_beams`` goes into
+        the generate options).  One chunk takes ``num_beams`` engine rows: ``batch_size >= num_beams`` is needed.  The calls run HF's
+        control flow around the engine call.  ``draft_previous_tick=None`` resolves to off (a draft does not go with beams), an explicit
+        ``True`` raises ``ValueError``; hotwords, the repeat options, ``token_scores``, ``temperature_fallback`` and
+        ``reuse_committed_prefix`` are refused by name."""
         from .asr_pipeline import ASRPipeline
 
+        self.num_beams: Optional[int] = None
+        if num_beams is not None and (isinstance(num_beams, bool) or num_beams != 1):
+            if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 2 <= int(num_beams) <= 8:
+                raise ValueError(f"num_beams must be an integer in 2..8 (or None / 1 for greedy), got {num_beams!r}")
+            K = int(num_beams)
+            for name, on in (("hotwords", hotwords is not None or hotword_boost is not None),
+                             ("repetition_penalty", repetition_penalty is not None),
+                             ("no_repeat_ngram_size", no_repeat_ngram_size is not None), ("token_scores", bool(token_scores)),
+                             ("temperature_fallback", temperature_fallback is not None),
+                             ("reuse_committed_prefix", bool(reuse_committed_prefix))):
+                if on:
+                    raise ValueError(f"num_beams={K} and {name} do not go together (the beam call takes none of these options)")
+            if draft_previous_tick:
+                raise ValueError(f"num_beams={K} and draft_previous_tick do not go together (a draft is verified against the greedy choice)")
+            draft_previous_tick = False
+            have = (asr_pipeline.model.engine.max_batch if asr_pipeline is not None else int(pipeline_kwargs.get("batch_size") or 1))
+            if have < K:
+                raise ValueError(f"num_beams={K} needs {K} engine rows per chunk, the pipeline holds {have}: construct it with batch_size={K} "
+                                 "(or more, for several chunks per call)")
+            self.num_beams = K
         if torch_dtype is None:
             # as the reference (R:...:369-370): float16 - a float16 context since round 4 (model.py: build_engine); bf16 before
             torch_dtype = torch.float16
@@ -121,6 +149,9 @@ class AMDWhisperBackend:
             revision=revision,
             **pipeline_kwargs,
         )
+        if self.num_beams is not None:
+            self.asr_pipeline.model.beam_search = True
+            self.asr_pipeline.model.beam_token_timestamps = True
         if draft_previous_tick is None:
             draft_previous_tick = not reuse_committed_prefix
         if reuse_committed_prefix and draft_previous_tick:
@@ -175,6 +206,8 @@ class AMDWhisperBackend:
             return
         if boost is None:
             raise ValueError("hotwords need hotword_boost (natural-log units on the logits; there is no default)")
+        if getattr(self, "num_beams", None):
+            raise ValueError(f"num_beams={self.num_beams} and hotwords do not go together (the beam call takes no sequence bias)")
         for name in ("temperature_fallback", "token_scores", "reuse_committed_prefix"):
             if getattr(self, name, None):
                 raise ValueError(f"hotwords and {name} do not go together (the sampler and the re-scoring pass do not know the bias)")
@@ -198,7 +231,7 @@ class AMDWhisperBackend:
         return resample(audio, int(sample_rate), self.sample_rate, kernel=self._resample_kernel), self.sample_rate
 
     def _generate_kwargs(self) -> Dict[str, Any]:
-        kw = {"use_cache": True, "num_beams": 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
+        kw = {"use_cache": True, "num_beams": self.num_beams or 1, "do_sample": False, "max_new_tokens": 128, "language": self.language}
         if self.repetition_penalty is not None:
             kw["repetition_penalty"] = self.repetition_penalty
         if self.no_repeat_ngram_size is not None:
@@ -368,6 +401,8 @@ class AMDWhisperBackend:
     def job_codec(self) -> "Optional[JobCodec]":
         """Per-request pre/post-processing around ``shortform.run_pass`` (what ``serving.BatchingHub`` schedules), or None
         when this backend's call cannot run the restated short-form loop (it then serves whole-call batches)."""
+        if self.num_beams is not None:
+            return None       # beam calls run HF's control flow (model._plan_key is None for them)
         try:
             return JobCodec(self)
         except _NotEligible:

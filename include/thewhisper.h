@@ -168,6 +168,40 @@ int tw_logmel(tw_ctx* ctx, const float* pcm_dev, int64_t pcm_stride, const int32
 int tw_encode(tw_ctx* ctx, const void* mel_dev, int32_t mel_dtype, int32_t B, void* out_hidden_dev,
               int32_t out_dtype, void* stream);
 
+/* Test instrument: tw_encode with taps.  Runs exactly the launches of tw_encode and copies named intermediate buffers of encoder
+ * layer `layer` into caller-supplied DEVICE buffers, each right after the launch that produced it (hipMemcpyAsync device-to-device
+ * on the call's stream).  A NULL member is not copied; with every member NULL (or taps == NULL) the call is tw_encode.  Every
+ * copy takes the WHOLE workspace buffer, sized for max_batch clips, not just the B clips of the call, so that a caller can see
+ * whether a launch wrote past its rows.  Element type: the context dtype, except the two float32 statistics buffers.  With
+ * Bm = max_batch, T = source_positions, d = d_model, H = heads, F = ffn, Tp = T rounded up to 64:
+ *   h1          [Bm, 2T+2, d]   conv1 + GELU, token-major, rows 0 and 2T+1 of every clip are the zero padding of conv2
+ *   xa_in       [Bm*T, d]       the layer's input (layer 0: conv2 + GELU + positions)
+ *   ln_stats_a  [Bm*T, d/32, 2] float32 (sum, sum of squares) per 32-column block of xa_in as stored; written only in contexts
+ *                               that fold the encoder's LayerNorms into the GEMMs (d_model % 64 == 0 and <= 1280)
+ *   q, k        [Bm, H, T, 64]  q carries the 1/8 scale
+ *   vt          [Bm, H, 64, Tp] V transposed, keys [T, Tp) zero
+ *   attn        [Bm*T, d]       softmax(q k^T) v, heads merged
+ *   xb          [Bm*T, d]       xa_in + out-projection
+ *   ln_stats_b  [Bm*T, d/32, 2] float32, of xb
+ *   ffnh        [Bm*T, F]       GELU(fc1)
+ *   xa_out      [Bm*T, d]       xb + fc2: the layer's output
+ *   enc_out     [Bm*T, d]       the encoder output slots after the final LayerNorm */
+typedef struct tw_encode_taps {
+  int32_t layer;
+  void *h1, *xa_in, *q, *k, *vt, *attn, *xb, *ffnh, *xa_out, *enc_out;
+  float *ln_stats_a, *ln_stats_b;
+} tw_encode_taps;
+int tw_encode_tapped(tw_ctx* ctx, const void* mel_dev, int32_t mel_dtype, int32_t B, void* out_hidden_dev,
+                     int32_t out_dtype, const tw_encode_taps* taps, void* stream);
+
+/* Host only, no GPU and no context needed: which kernel the encoder's launches take for a shape, so that a test can prove which
+ * code it reached.  tw_gemm_plan: dtype = TW_F32 / TW_BF16 / TW_F16, mode = 0 for a row-major output, 2 for the encoder's fused
+ * QKV projection, 3 for the cross K/V projection; C[M, N] = A[M, K] W[N, K]^T; *kernel = 1 (both operands through LDS, bm x 64
+ * tiles) or 2 (weights straight to registers, bm x 256 tiles), *bm = the tile height.  tw_enc_attention_plan: B streams of H
+ * heads and T frames; *queries_per_block = 64 or 128, *xcd = 1 when heads are pinned to XCDs.  Any output pointer may be NULL. */
+int tw_gemm_plan(int32_t dtype, int32_t mode, int32_t M, int32_t N, int32_t K, int32_t* kernel, int32_t* bm);
+int tw_enc_attention_plan(int32_t dtype, int32_t B, int32_t H, int32_t T, int32_t* queries_per_block, int32_t* xcd);
+
 /* A5.  Replaces: the lazy cross-attention K/V projection + EncoderDecoderCache.is_updated
  * (HF:models/whisper/modeling_whisper.py:312-335).  Projects the context's encoder output of slots
  * 0..B-1 into the per-layer cross K/V arenas, once per chunk. */

@@ -17,6 +17,23 @@ TW_BF16_MXFP8 = 3  # context dtype only: bf16 activations, MXFP8 decoder project
 TW_BF16_W8A16 = 4  # context dtype only: MXFP8 decoder projection weights widened to bf16 in registers, bf16 activations
 TW_MAX_ALIGN_HEADS = 32
 TW_PCM_F32, TW_PCM_S16 = 0, 1   # tw_resample input formats
+TW_EPI_ROWMAJOR, TW_EPI_QKV_ENC, TW_EPI_KV_CROSS = 0, 2, 3   # tw_gemm_plan epilogue modes
+
+
+def gemm_plan(dtype: int, mode: int, M: int, N: int, K: int):
+    """(kernel, tile height) the library's GEMM dispatch picks for this launch (tw_gemm_plan: host arithmetic, no GPU needed)."""
+    lib = load_library()
+    kernel, bm = C.c_int32(), C.c_int32()
+    check(lib, None, lib.tw_gemm_plan(dtype, mode, M, N, K, C.byref(kernel), C.byref(bm)), "tw_gemm_plan")
+    return kernel.value, bm.value
+
+
+def enc_attention_plan(dtype: int, B: int, H: int, T: int):
+    """(queries per workgroup, heads pinned to XCDs) of the encoder attention launch (tw_enc_attention_plan; no GPU needed)."""
+    lib = load_library()
+    qpb, xcd = C.c_int32(), C.c_int32()
+    check(lib, None, lib.tw_enc_attention_plan(dtype, B, H, T, C.byref(qpb), C.byref(xcd)), "tw_enc_attention_plan")
+    return qpb.value, xcd.value
 
 
 class tw_config(C.Structure):
@@ -60,6 +77,11 @@ class tw_beam_opts(C.Structure):
     _fields_ = [("num_beams", C.c_int32), ("length_penalty", C.c_float), ("early_stopping", C.c_int32)]
 
 
+class tw_encode_taps(C.Structure):
+    _fields_ = [("layer", C.c_int32)] + [(n, C.c_void_p) for n in ("h1", "xa_in", "q", "k", "vt", "attn", "xb", "ffnh", "xa_out",
+                                                                   "enc_out", "ln_stats_a", "ln_stats_b")]
+
+
 # every symbol declared in include/thewhisper.h: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -72,6 +94,9 @@ SYMBOLS = [
     ("tw_finalize_weights", C.c_int, [_P, _P]),
     ("tw_logmel", C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     ("tw_encode", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    ("tw_encode_tapped", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(tw_encode_taps), _P]),
+    ("tw_gemm_plan", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("tw_enc_attention_plan", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("tw_cross_kv", C.c_int, [_P, C.c_int32, _P]),
     ("tw_encode_at", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("tw_cross_kv_at", C.c_int, [_P, C.c_int32, C.c_int32, _P]),

@@ -788,8 +788,10 @@ int tw_logmel(tw_ctx* c, const float* pcm, int64_t pcm_stride, const int32_t* n_
 namespace {
 
 // encoder for B clips whose output goes to slots slot0 .. slot0+B-1 of enc_out (all other buffers are scratch from row 0)
+// `taps` (tw_encode_tapped, a test instrument): copies of whole workspace buffers right after the launch that wrote them; null on
+// every product path, where each tap below is one untaken branch
 int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_t slot0, void* out_hidden, int32_t out_dtype,
-                void* stream) {
+                void* stream, const tw_encode_taps* taps = nullptr) {
   if (!c || !mel) return fail(c, TW_EINVAL, "tw_encode: null argument");
   TW_ON_DEVICE(c);
   if (!c->finalized) return fail(c, TW_ESTATE, "tw_encode before tw_finalize_weights");
@@ -802,6 +804,12 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
   const int d = c->d, T = c->T, C = c->C, H = c->H, F = c->ffn, dt = c->dtype;
   const size_t e = c->esz;
   const bool fold = c->enc_fold;
+  if (taps && (taps->layer < 0 || taps->layer >= c->Le)) return fail(c, TW_EINVAL, "tw_encode_tapped: layer %d outside [0,%d)", taps->layer, c->Le);
+  if (taps && !fold && (taps->ln_stats_a || taps->ln_stats_b)) return fail(c, TW_EINVAL, "tw_encode_tapped: this context keeps no LayerNorm statistics");
+  const size_t rows_max = (size_t)c->Bmax * T;   // the workspace is sized for Bmax clips and a tap takes all of it
+  auto tap = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+  };
   tic(c, 1, st);
   HIPCHK(c, launch_mel_transpose(dt, mel_dtype, mel, c->melT, B, c->n_mels, 2 * T, C, st));
   {  // conv1 (k3,p1) + GELU as a GEMM over overlapping 3-row windows of the padded token-major mel
@@ -810,6 +818,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
     ep.c_map = RowMap{2 * T, (long long)(2 * T + 2) * d, d};
     ep.out = at(c->h1, d, e);
     HIPCHK(c, launch_gemm(dt, c->melT, RowMap{2 * T, (long long)(2 * T + 2) * C, C}, c->conv1_w, B * 2 * T, d, 3 * C, ep, st));
+    if (taps) HIPCHK(c, tap(taps->h1, c->h1, (size_t)c->Bmax * (2 * T + 2) * d * e));
   }
   {  // conv2 (k3,s2,p1) + GELU + positions: windows of 3 rows at stride 2 rows
     GemmEpilogue ep{};
@@ -823,6 +832,11 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
   const int M = B * T;
   for (int l = 0; l < c->Le; ++l) {
     const LayerW& L = c->enc[l];
+    const tw_encode_taps* tp = taps && taps->layer == l ? taps : nullptr;
+    if (tp) {   // the layer's input: what conv2 (l = 0) or the fc2 of layer l - 1 left
+      HIPCHK(c, tap(tp->xa_in, c->xa, rows_max * d * e));
+      HIPCHK(c, tap(tp->ln_stats_a, c->ln_stats_a, rows_max * (d / 32) * 8));
+    }
     // pre-LayerNorms: folded into the consuming GEMM (weights carry the gain, the epilogue applies mean / rstd from the partial row
     // statistics the producing GEMM left), or - without enc_fold - a launch that writes a normalised copy
     if (!fold) HIPCHK(c, launch_layernorm(dt, c->xa, L.ln1_g, L.ln1_b, c->lnbuf, M, d, st));
@@ -832,14 +846,24 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.out = c->qbuf; ep.out2 = c->kbuf; ep.out3 = c->vtbuf;
       if (fold) { ep.bias = nullptr; ep.stats_in = c->ln_stats_a; ep.stats_in_parts = d / 32; ep.ln_gw = L.qkv_gw; ep.ln_cb = L.qkv_cb; }
       HIPCHK(c, launch_gemm(dt, fold ? c->xa : c->lnbuf, plain_rows(d), L.wqkv, M, 3 * d, d, ep, st));
+      if (tp) {
+        HIPCHK(c, tap(tp->q, c->qbuf, rows_max * d * e));
+        HIPCHK(c, tap(tp->k, c->kbuf, rows_max * d * e));
+        HIPCHK(c, tap(tp->vt, c->vtbuf, (size_t)c->Bmax * H * 64 * c->Tp * e));
+      }
     }
     HIPCHK(c, launch_enc_attention(dt, c->qbuf, c->kbuf, c->vtbuf, c->attn, B, H, T, c->Tp, st));
+    if (tp) HIPCHK(c, tap(tp->attn, c->attn, rows_max * d * e));
     {
       GemmEpilogue ep{};
       ep.bias = L.bo; ep.mode = EPI_ROWMAJOR; ep.res = c->xa; ep.res_map = plain_rows(d); ep.c_map = plain_rows(d);
       ep.out = c->xb;
       if (fold) ep.stats_out = c->ln_stats_b;
       HIPCHK(c, launch_gemm(dt, c->attn, plain_rows(d), L.wo, M, d, d, ep, st));
+      if (tp) {
+        HIPCHK(c, tap(tp->xb, c->xb, rows_max * d * e));
+        HIPCHK(c, tap(tp->ln_stats_b, c->ln_stats_b, rows_max * (d / 32) * 8));
+      }
     }
     if (!fold) HIPCHK(c, launch_layernorm(dt, c->xb, L.ln2_g, L.ln2_b, c->lnbuf, M, d, st));
     {
@@ -847,6 +871,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.bias = L.b1; ep.gelu = 1; ep.mode = EPI_ROWMAJOR; ep.c_map = plain_rows(F); ep.out = c->ffnh;
       if (fold) { ep.bias = nullptr; ep.stats_in = c->ln_stats_b; ep.stats_in_parts = d / 32; ep.ln_gw = L.fc1_gw; ep.ln_cb = L.fc1_cb; }
       HIPCHK(c, launch_gemm(dt, fold ? c->xb : c->lnbuf, plain_rows(d), L.w1, M, F, d, ep, st));
+      if (tp) HIPCHK(c, tap(tp->ffnh, c->ffnh, rows_max * F * e));
     }
     {
       GemmEpilogue ep{};
@@ -854,10 +879,12 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.out = c->xa;
       if (fold && l + 1 < c->Le) ep.stats_out = c->ln_stats_a;
       HIPCHK(c, launch_gemm(dt, c->ffnh, plain_rows(F), L.w2, M, d, F, ep, st));
+      if (tp) HIPCHK(c, tap(tp->xa_out, c->xa, rows_max * d * e));
     }
   }
   void* enc_dst = at(c->enc_out, (size_t)slot0 * T * d, e);
   HIPCHK(c, launch_layernorm(dt, c->xa, c->enc_ln_g, c->enc_ln_b, enc_dst, M, d, st));
+  if (taps) HIPCHK(c, tap(taps->enc_out, c->enc_out, rows_max * d * e));
   toc(c, 1, st);
   if (out_hidden) HIPCHK(c, launch_convert(out_dtype, dt, enc_dst, out_hidden, (long long)M * d, 1.f, st));
   c->encoded_B = slot0 + B;
@@ -903,6 +930,32 @@ extern "C" {
 int tw_encode(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, void* out_hidden, int32_t out_dtype, void* stream) {
   if (c) { c->encoded_B = 0; c->cross_B = 0; }
   return encode_core(c, mel, mel_dtype, B, 0, out_hidden, out_dtype, stream);
+}
+
+int tw_encode_tapped(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, void* out_hidden, int32_t out_dtype,
+                     const tw_encode_taps* taps, void* stream) {
+  if (c) { c->encoded_B = 0; c->cross_B = 0; }
+  return encode_core(c, mel, mel_dtype, B, 0, out_hidden, out_dtype, stream, taps);
+}
+
+int tw_gemm_plan(int32_t dtype, int32_t mode, int32_t M, int32_t N, int32_t K, int32_t* kernel, int32_t* bm) {
+  if (dtype != TW_F32 && dtype != TW_BF16 && dtype != TW_F16) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: dtype %d is not TW_F32 / TW_BF16 / TW_F16", dtype);
+  if (mode != EPI_ROWMAJOR && mode != EPI_QKV_ENC && mode != EPI_KV_CROSS) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: mode %d", mode);
+  const int kt = dtype == TW_F32 ? 32 : 64;   // elements per K tile (k_gemm.hip)
+  if (M < 1 || N < 64 || N % 64 != 0 || K < kt || K % kt != 0) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: no GEMM for M=%d N=%d K=%d", M, N, K);
+  const GemmPlan p = gemm_plan(mode, M, N);
+  if (kernel) *kernel = p.kernel;
+  if (bm) *bm = p.bm;
+  return TW_OK;
+}
+
+int tw_enc_attention_plan(int32_t dtype, int32_t B, int32_t H, int32_t T, int32_t* queries_per_block, int32_t* xcd) {
+  if (dtype != TW_F32 && dtype != TW_BF16 && dtype != TW_F16) return fail(nullptr, TW_EINVAL, "tw_enc_attention_plan: dtype %d is not TW_F32 / TW_BF16 / TW_F16", dtype);
+  if (B < 1 || H < 1 || T < 1) return fail(nullptr, TW_EINVAL, "tw_enc_attention_plan: B=%d H=%d T=%d", B, H, T);
+  const EncAttnPlan p = enc_attention_plan(dtype, B, H, T);
+  if (queries_per_block) *queries_per_block = p.queries_per_block;
+  if (xcd) *xcd = p.xcd;
+  return TW_OK;
 }
 
 int tw_encode_at(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_t slot0, void* stream) {

@@ -302,16 +302,23 @@ __global__ __launch_bounds__(256, 2) void enc_attn_kernel(const T* __restrict__ 
 
 }  // namespace
 
+// Which variant a launch gets: the ONE copy of the choice (launch_enc_attention calls it; tw_enc_attention_plan reports it).
+EncAttnPlan enc_attention_plan(int dtype, int B, int H, int T) {
+  // 128 queries per workgroup when that still yields >= 2 workgroups per CU, else 64 (strict-f32 contexts: always 64).
+  const long long blocks128 = (long long)B * H * ((T + 127) / 128);
+  const bool big = (dtype == 1 || dtype == 2) && blocks128 >= 512;
+  // heads pinned to XCDs when there are at least 64 of them (with the 20 heads of one stream 4 XCDs would get three heads and 4 two:
+  // 5.68 -> 5.88 ms for one 30 s chunk)
+  return EncAttnPlan{big ? 128 : 64, B * H >= 64 ? 1 : 0};
+}
+
 hipError_t launch_enc_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int H,
                                 int T, int Tp, hipStream_t st) {
   if (B <= 0 || T <= 0 || Tp % 64 != 0 || Tp < T) return hipErrorInvalidValue;
-  // 128 queries per workgroup when that still yields >= 2 workgroups per CU, else 64.
-  const long long blocks128 = (long long)B * H * ((T + 127) / 128);
-  const bool big = blocks128 >= 512;
-  // heads pinned to XCDs when there are at least 64 of them (with the 20 heads of one stream 4 XCDs would get three heads and 4 two:
-  // 5.68 -> 5.88 ms for one 30 s chunk)
+  const EncAttnPlan plan = enc_attention_plan(dtype, B, H, T);
+  const bool big = plan.queries_per_block == 128;
   const int nbh = B * H;
-  const int xcd = nbh >= 64 ? 1 : 0;
+  const int xcd = plan.xcd;
   auto grid_for = [&](int nq) { return dim3((unsigned)((xcd ? 8 * ((nbh + 7) / 8) : nbh) * nq)); };
   if (dtype == 1) {
     if (big)

@@ -886,19 +886,10 @@ static hipError_t gemm_wreg_go(const void* A, RowMap amap, const void* W, int M,
   return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M, int N, int K,
-                                const GemmEpilogue& ep, hipStream_t st) {
-  constexpr int E = ElemTraits<T>::kPer16B;
-  if (M <= 0) return hipSuccess;
-  if (K % (8 * E) != 0 || N % 64 != 0) return hipErrorInvalidValue;
-  // Tile choice:
-  //   kernel 2: BM x 256 (BM = 80 ... 128), 4 wavefronts side by side, weights straight to registers, 3-stage activation ring - large M
-  //   kernel 1: 128 x 64 (3 stages) or 64 x 64 (4 stages), both operands through an LDS ring - small M (one to three streams)
-  if (ep.mode == EPI_KV_CROSS8) {   // fp8 cross-K/V epilogue: one head per wavefront, i.e. kernel 2 whatever the shape
-    if (ElemTraits<T>::kCode != 1 || N % 64 != 0) return hipErrorInvalidValue;
-    return gemm_wreg_go<T, 128, 4, 3>(A, amap, W, M, N, K, ep, st);
-  }
+// Which kernel and tile height a launch gets: the ONE copy of the choice (gemm_dispatch calls it; tw_gemm_plan reports it, so that a
+// test can prove which path a shape took).  kernel 2 = gemm_wreg_kernel with a bm x 256 tile, kernel 1 = gemm_kernel with bm x 64.
+GemmPlan gemm_plan(int mode, int M, int N) {
+  if (mode == EPI_KV_CROSS8) return GemmPlan{2, 128};   // fp8 cross-K/V epilogue: one head per wavefront, i.e. kernel 2 whatever the shape
   // kernel 2 from 512 128 x 128 tiles on: 128 x 256 tiles need >= 256 workgroups to cover the chip.  One 30 s chunk's fc1
   // (M = 1500, N = 5120: 480 tiles = 240 workgroups) is faster in 128 x 64 tiles (encoder 6.27 -> 6.00 ms, profiles/r03_gemm_tiles.txt)
   const long long b128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
@@ -917,7 +908,24 @@ static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M
       const long long cost = ((tiles + 255) / 256) * (bm + ovh);
       if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = bm; }
     }
-    switch (best) {
+    return GemmPlan{2, best};
+  }
+  return GemmPlan{1, M <= 1000 ? 64 : 128};   // (gemm_dispatch: why 64 x 64 up to 1000 rows)
+}
+
+template <typename T>
+static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M, int N, int K,
+                                const GemmEpilogue& ep, hipStream_t st) {
+  constexpr int E = ElemTraits<T>::kPer16B;
+  if (M <= 0) return hipSuccess;
+  if (K % (8 * E) != 0 || N % 64 != 0) return hipErrorInvalidValue;
+  // Tile choice:
+  //   kernel 2: BM x 256 (BM = 80 ... 128), 4 wavefronts side by side, weights straight to registers, 3-stage activation ring - large M
+  //   kernel 1: 128 x 64 (3 stages) or 64 x 64 (4 stages), both operands through an LDS ring - small M (one to three streams)
+  if (ep.mode == EPI_KV_CROSS8 && (ElemTraits<T>::kCode != 1 || N % 64 != 0)) return hipErrorInvalidValue;   // bf16 contexts only
+  const GemmPlan plan = gemm_plan(ep.mode, M, N);
+  if (plan.kernel == 2) {
+    switch (plan.bm) {
       case 80: return gemm_wreg_go<T, 80, 4, 3>(A, amap, W, M, N, K, ep, st);
       case 96: return gemm_wreg_go<T, 96, 4, 3>(A, amap, W, M, N, K, ep, st);
       case 112: return gemm_wreg_go<T, 112, 4, 3>(A, amap, W, M, N, K, ep, st);
@@ -932,7 +940,7 @@ static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M
   // fc2 39.5 -> 30, but fc1 18.4 -> 34 and QKV 15.3 -> 24.5 - with one workgroup per CU the wide projections run 2.5 rounds and the
   // launch is bound by the aggregate operand traffic of its small tiles (210 MB for fc1 at M = 500 = 6 TB/s), not by latency
   // (profiles/r04_gemm_deep_ring_ab.txt).
-  if (M <= 1000) return gemm_go<T, 64, 64, 2, 2, 4>(A, amap, W, M, N, K, ep, st);   // 64 KB: two workgroups per CU
+  if (plan.bm == 64) return gemm_go<T, 64, 64, 2, 2, 4>(A, amap, W, M, N, K, ep, st);   // 64 KB: two workgroups per CU
   return gemm_go<T, 128, 64, 2, 2, 3>(A, amap, W, M, N, K, ep, st);
 }
 

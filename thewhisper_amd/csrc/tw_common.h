@@ -204,6 +204,10 @@ struct GemmEpilogue {
 // C[M,N] = epi(A[M,K] * W[N,K]^T).  T = float or bf16.  K % 64 == 0 (bf16) / % 32 == 0 (f32), N % 64 == 0.
 hipError_t launch_gemm(int dtype, const void* A, RowMap amap, const void* W, int M, int N, int K,
                        const GemmEpilogue& ep, hipStream_t st);
+// the kernel (1: both operands through LDS, bm x 64 tiles; 2: weights to registers, bm x 256 tiles) and tile height launch_gemm
+// picks for an epilogue mode and shape: pure host arithmetic, no device needed
+struct GemmPlan { int kernel, bm; };
+GemmPlan gemm_plan(int mode, int M, int N);
 
 hipError_t launch_layernorm(int dtype, const void* x, const void* g, const void* b, void* y, int rows, int d,
                             hipStream_t st);
@@ -235,6 +239,9 @@ hipError_t launch_logmel(const float* pcm, long long pcm_stride, const int* n_va
 // encoder self-attention (non-causal, head_dim 64).  q,k: [B,H,T,64]; vt: [B,H,64,Tp]; out: [B*T, H*64]
 hipError_t launch_enc_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int H,
                                 int T, int Tp, hipStream_t st);
+// the variant launch_enc_attention picks: 64 or 128 queries per workgroup, heads pinned to XCDs or not (pure host arithmetic)
+struct EncAttnPlan { int queries_per_block, xcd; };
+EncAttnPlan enc_attention_plan(int dtype, int B, int H, int T);
 
 // ---- decoder (single new token per stream) ----
 struct DecState {   // lives in device memory so that a captured graph is position independent

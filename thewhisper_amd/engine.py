@@ -428,6 +428,44 @@ class WhisperEngine:
             self._publish()
         return out
 
+    def encode_tapped(self, mel: torch.Tensor, layer: int = 0, hidden_dtype: torch.dtype = torch.float32):
+        """Test instrument (tw_encode_tapped): ``encode(mel, return_hidden=True)`` that also returns the intermediate buffers of encoder
+        layer ``layer``, each copied on the device right after the launch that wrote it.  Returns ``(hidden [B, T, d], taps)``; every
+        tap is the WHOLE workspace buffer, sized for ``max_batch`` (Bm) clips whatever B is, in the context dtype (the statistics in
+        float32).  With T frames, d = d_model, H heads, F = ffn, Tp = T rounded up to 64:
+
+        ``h1`` [Bm, 2T+2, d] (conv1 + GELU; rows 0 and 2T+1 of a clip are conv2's zero padding) - ``xa_in`` [Bm*T, d] (the layer's
+        input; layer 0: conv2 + GELU + positions) - ``ln_stats_a`` [Bm*T, d/32, 2] ((sum, sum of squares) per 32-column block of
+        ``xa_in``) - ``q``, ``k`` [Bm, H, T, 64] (q scaled by 1/8) - ``vt`` [Bm, H, 64, Tp] - ``attn`` [Bm*T, d] - ``xb`` [Bm*T, d]
+        (after the out-projection and residual) - ``ln_stats_b`` [Bm*T, d/32, 2] - ``ffnh`` [Bm*T, F] - ``xa_out`` [Bm*T, d] (the
+        layer's output) - ``enc_out`` [Bm*T, d] (after the final LayerNorm).  Contexts that do not fold the encoder's LayerNorms
+        (d_model > 1280 or no multiple of 64) have no statistics taps."""
+        mel = mel.to(self.device).contiguous()
+        if mel.dtype not in _TORCH2TW:
+            mel = mel.float()
+        B = mel.shape[0]
+        if tuple(mel.shape[1:]) != (self.n_mels, 2 * self.T):
+            raise ValueError(f"Whisper expects the mel input features to be of length {2 * self.T}, but found {mel.shape[-1]}")
+        Bm, T, d, H, F = self.max_batch, self.T, self.d_model, self.dims["heads"], self.dims["ffn"]
+        Tp = (T + 63) // 64 * 64
+        shapes = {"h1": (Bm, 2 * T + 2, d), "xa_in": (Bm * T, d), "q": (Bm, H, T, 64), "k": (Bm, H, T, 64), "vt": (Bm, H, 64, Tp),
+                  "attn": (Bm * T, d), "xb": (Bm * T, d), "ffnh": (Bm * T, F), "xa_out": (Bm * T, d), "enc_out": (Bm * T, d)}
+        if d % 64 == 0 and d <= 1280:
+            shapes.update(ln_stats_a=(Bm * T, d // 32, 2), ln_stats_b=(Bm * T, d // 32, 2))
+        taps = {k: torch.empty(v, dtype=torch.float32 if k.startswith("ln_stats") else self.torch_dtype, device=self.device)
+                for k, v in shapes.items()}
+        st = _cabi.tw_encode_taps()
+        st.layer = int(layer)
+        for k, t in taps.items():
+            setattr(st, k, t.data_ptr())
+        out = torch.empty((B, T, d), dtype=hidden_dtype, device=self.device)
+        self._adopt(mel, out, *taps.values())
+        rc = self.lib.tw_encode_tapped(self.ctx, C.c_void_p(mel.data_ptr()), _TORCH2TW[mel.dtype], B, C.c_void_p(out.data_ptr()),
+                                       _TORCH2TW[hidden_dtype], C.byref(st), self._sp())
+        self._chk(rc, "tw_encode_tapped")
+        self._publish()
+        return out, taps
+
     def cross_kv(self, B: int, slot0: int = 0):
         if slot0:
             self._chk(self.lib.tw_cross_kv_at(self.ctx, B, int(slot0), self._sp()), "tw_cross_kv_at")

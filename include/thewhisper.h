@@ -335,6 +335,37 @@ int tw_generate_greedy_repeat(tw_ctx* ctx, int32_t B, const int32_t* prompt_host
 int tw_repeat_logits(int32_t device, float* logits_dev, int32_t V, int32_t rows, const int32_t* hist_host, int32_t ld,
                      const int32_t* n_hist_host, const tw_repeat_opts* ropts, void* stream);
 
+/* Language detection on the device (k_decode.hip: lang_detect_kernel): HF's detect_language (HF:models/whisper/generation_whisper.py:1610-1683)
+ * masks every non-language logit of the step at <|startoftranscript|> and takes the arg-max.  Here the kernel reads the n_lang listed
+ * logits only and nothing of the [rows, V] logits is copied back.
+ *
+ * THE RULE for row r and the listed ids (any order, not necessarily contiguous), x_j = logits[r][ids[j]]:
+ *   a NaN counts as -inf;  m = max_j x_j;
+ *   id = the SMALLEST TOKEN ID among the j with x_j == m (not the smallest list index): torch.argmax of HF's masked row - the first
+ *     occurrence over the vocabulary.  Logits outside the list never matter, however large;
+ *   p_j = exp(x_j - m) / s in float32, s = the float32 sum of the numerators in an order that depends on n_lang only - never on the
+ *     number of rows or on the row's index: a row's 32-bit patterns are the same alone and in a batch of 64;
+ *   m == -inf (nothing finite in the list): id = the smallest listed id and every p_j = 0.0f.  (A deviation: HF answers id 0 there.)
+ * One workgroup per row, no atomics.
+ *
+ * TW_EINVAL for both entries, before anything is enqueued (a context stays usable): a NULL logits / id-list / out_id pointer, n_lang
+ * outside 1 .. TW_LANG_MAX, a listed id (tw_detect_language: or sot_id) outside [0, V), a duplicate id, rows (B) below 1 or above what
+ * the call can hold (tw_language_logits: 65535; tw_detect_language: max_batch).  out_prob_host may be NULL: only the ids come back. */
+#define TW_LANG_MAX 128
+/* context-free, like tw_repeat_logits: the kernel on caller-supplied logits (device, float32 [rows, V], only read).  Test instrument and
+ * building block.  Returns after the stream has been synchronised. */
+int tw_language_logits(int32_t device, const float* logits_dev, int32_t V, int32_t rows, const int32_t* lang_ids_host, int32_t n_lang,
+                       int32_t* out_id_host, float* out_prob_host /* [rows, n_lang] or NULL */, void* stream);
+/* Rows 0 .. B-1 of the context's cross K/V (tw_encode + tw_cross_kv for at least B rows, else TW_ESTATE, as tw_decode_step): rewinds the
+ * decoder (the launches of tw_decoder_reset), runs ONE step on sot_id for every row (the launches of tw_decode_step) and applies the
+ * kernel to that step's logits.  Copies back B ints and, with out_prob_host, B * n_lang floats.  The id list goes to context-owned device
+ * memory allocated by the context's first call (tw_destroy frees it; a sibling owns its own).  Leaves the decoder at position 1, like a
+ * tw_decode_step; every tw_generate_* call rewinds the decoder, so a following decode is unaffected.  It OVERWRITES the alignment rows
+ * and the sampler state of a previous decode: the call belongs in front of the generate call of a pass, never between a generate call
+ * and its tw_token_timestamps. */
+int tw_detect_language(tw_ctx* ctx, int32_t B, int32_t sot_id, const int32_t* lang_ids_host, int32_t n_lang,
+                       int32_t* out_id_host, float* out_prob_host /* [B, n_lang] or NULL */, void* stream);
+
 /* tw_generate_greedy for rows whose prompts differ in length ("ragged prompts"): the batch is LEFT-padded to one length n_prompt, as HF
  * batches Whisper's previous-text prompts (HF:models/whisper/generation_whisper.py:1709-1772 pads decoder_input_ids on the left and passes
  * decoder_attention_mask = ids != pad), and n_pad_host[b] says how many leading entries of row b are padding.

@@ -113,6 +113,10 @@ SYMBOLS = [
                                             C.POINTER(tw_bias_opts), C.POINTER(tw_repeat_opts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_repeat_logits", C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                    C.POINTER(tw_repeat_opts), _P]),
+    ("tw_language_logits", C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_float), _P]),
+    ("tw_detect_language", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_float), _P]),
     ("tw_generate_sample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts), C.POINTER(tw_sample_opts),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("tw_generate_sample_filtered", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(tw_greedy_opts),

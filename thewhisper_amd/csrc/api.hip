@@ -135,6 +135,9 @@ struct tw_ctx {
   // tw_generate_greedy_ragged: the per-stream padding lengths [64] the ragged kernels read (tw_common.h: tw_row_pos) and their pinned
   // staging, allocated by the first ragged call of the context
   int* n_pad_tab = nullptr; int* h_n_pad = nullptr;
+  // tw_detect_language: ids [kLangMax] | out ids [Bmax] | out probabilities [Bmax][kLangMax] | the step's input ids [Bmax], on the device
+  // and pinned, allocated by the first call of the context
+  int* lang_tab = nullptr; int* h_lang = nullptr;
   // tw_generate_beam: the state tables of the call (BeamTab: scores, finished set, flags, penalty table, finished hypotheses), their
   // pinned image (up with the initial state, down with the result) and the slice partials, allocated by the first beam call of the context
   int* beam_tab = nullptr; int* h_beam = nullptr; BeamPartial* beam_parts = nullptr;
@@ -301,7 +304,7 @@ int tw_destroy(tw_ctx* c) {
   (void)hipDeviceSynchronize();
   for (auto& kv : c->step_graphs) (void)hipGraphExecDestroy(kv.second);
   for (void* p : c->allocs) (void)hipFree(p);
-  void* const pinned[] = {c->h_pinned, c->h_stage, c->h_seq, c->h_rows.tok, c->h_verify, c->h_score.masked, c->h_bias, c->h_repeat, c->h_n_pad, c->h_beam};
+  void* const pinned[] = {c->h_pinned, c->h_stage, c->h_seq, c->h_rows.tok, c->h_verify, c->h_score.masked, c->h_bias, c->h_repeat, c->h_n_pad, c->h_beam, c->h_lang};
   for (void* p : pinned)
     if (p) (void)hipHostFree(p);
   for (int i = 0; i < 5; ++i) {
@@ -2312,6 +2315,90 @@ int tw_repeat_logits(int32_t device, float* logits_dev, int32_t V, int32_t rows,
   (void)hipFree(dev);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail(nullptr, TW_EHIP, "%s: %s", fn, hipGetErrorString(e));
+  return TW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the refusals tw_language_logits and tw_detect_language share (include/thewhisper.h)
+int check_lang_list(tw_ctx* c, const char* fn, const int32_t* ids, int32_t n_lang, int32_t V) {
+  if (!ids) return fail(c, TW_EINVAL, "%s: null argument", fn);
+  if (n_lang < 1 || n_lang > TW_LANG_MAX) return fail(c, TW_EINVAL, "%s: n_lang = %d outside 1 .. %d", fn, n_lang, TW_LANG_MAX);
+  int sorted[TW_LANG_MAX];
+  for (int j = 0; j < n_lang; ++j) {
+    if (ids[j] < 0 || ids[j] >= V) return fail(c, TW_EINVAL, "%s: language id %d outside [0, %d)", fn, ids[j], V);
+    sorted[j] = ids[j];
+  }
+  std::sort(sorted, sorted + n_lang);
+  for (int j = 1; j < n_lang; ++j)
+    if (sorted[j] == sorted[j - 1]) return fail(c, TW_EINVAL, "%s: language id %d is listed twice", fn, sorted[j]);
+  return TW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tw_language_logits(int32_t device, const float* logits_dev, int32_t V, int32_t rows, const int32_t* lang_ids_host, int32_t n_lang,
+                       int32_t* out_id_host, float* out_prob_host, void* stream) {
+  const char* fn = "tw_language_logits";
+  if (!logits_dev || !lang_ids_host || !out_id_host) return fail(nullptr, TW_EINVAL, "%s: null argument", fn);
+  if (V < 1 || rows < 1 || rows > 65535) return fail(nullptr, TW_EINVAL, "%s: V = %d, rows = %d (rows 1 .. 65535)", fn, V, rows);
+  int r = check_lang_list(nullptr, fn, lang_ids_host, n_lang, V);
+  if (r != TW_OK) return r;
+  DeviceGuard guard(device);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // one block: ids [n_lang] | out ids [rows] | out probabilities [rows][n_lang]
+  const size_t words = (size_t)n_lang + rows + (size_t)rows * n_lang;
+  int* dev = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), sizeof(int) * words);
+  if (e != hipSuccess) return fail(nullptr, TW_ENOMEM, "%s: hipMalloc failed: %s", fn, hipGetErrorString(e));
+  int* out_id = dev + n_lang;
+  float* out_prob = reinterpret_cast<float*>(out_id + rows);
+  e = hipMemcpyAsync(dev, lang_ids_host, sizeof(int) * n_lang, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_lang_detect(logits_dev, V, rows, dev, n_lang, out_id, out_prob_host ? out_prob : nullptr, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_id_host, out_id, sizeof(int) * rows, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && out_prob_host) e = hipMemcpyAsync(out_prob_host, out_prob, sizeof(float) * (size_t)rows * n_lang, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(nullptr, TW_EHIP, "%s: %s", fn, hipGetErrorString(e));
+  return TW_OK;
+}
+
+int tw_detect_language(tw_ctx* c, int32_t B, int32_t sot_id, const int32_t* lang_ids_host, int32_t n_lang, int32_t* out_id_host,
+                       float* out_prob_host, void* stream) {
+  const char* fn = "tw_detect_language";
+  if (!c) return TW_EINVAL;
+  if (!lang_ids_host || !out_id_host) return fail(c, TW_EINVAL, "%s: null argument", fn);
+  TW_ON_DEVICE(c);
+  if (B < 1 || B > c->Bmax) return fail(c, TW_EINVAL, "%s: B = %d outside 1 .. max_batch = %d", fn, B, c->Bmax);
+  if (sot_id < 0 || sot_id >= c->V) return fail(c, TW_EINVAL, "%s: sot_id %d outside [0, %d)", fn, sot_id, c->V);
+  int r = check_lang_list(c, fn, lang_ids_host, n_lang, c->V);
+  if (r != TW_OK) return r;
+  if (B > c->cross_B) return fail(c, TW_ESTATE, "%s: B=%d but cross K/V holds %d clips", fn, B, c->cross_B);
+  hipStream_t st = pick_stream(c, stream);
+  const size_t Bm = (size_t)c->Bmax, cap = TW_LANG_MAX + Bm + Bm * TW_LANG_MAX + Bm;
+  r = upload_first_use_table(c, c->lang_tab, c->h_lang, cap, true, lang_ids_host, (size_t)n_lang, st);
+  if (r != TW_OK) return r;
+  const size_t o_id = TW_LANG_MAX, o_prob = o_id + Bm, o_sot = o_prob + Bm * TW_LANG_MAX;
+  for (int b = 0; b < B; ++b) c->h_lang[o_sot + b] = sot_id;
+  // the launches of tw_decoder_reset + tw_decode_step
+  r = reset_state(c, 0, st);
+  if (r != TW_OK) return r;
+  c->dec_key_bound = c->P;
+  HIPCHK(c, hipMemcpyAsync(c->cur_ids, c->h_lang + o_sot, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  r = decode_core(c, B, st);
+  if (r != TW_OK) return r;
+  float* prob_dev = reinterpret_cast<float*>(c->lang_tab + o_prob);
+  HIPCHK(c, launch_lang_detect(c->logits, c->V, B, c->lang_tab, n_lang, c->lang_tab + o_id, out_prob_host ? prob_dev : nullptr, st));
+  HIPCHK(c, launch_advance(c->stt, 1, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_lang + o_id, c->lang_tab + o_id, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  if (out_prob_host)
+    HIPCHK(c, hipMemcpyAsync(c->h_lang + o_prob, prob_dev, sizeof(float) * (size_t)B * n_lang, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  memcpy(out_id_host, c->h_lang + o_id, sizeof(int) * B);
+  if (out_prob_host) memcpy(out_prob_host, c->h_lang + o_prob, sizeof(float) * (size_t)B * n_lang);
   return TW_OK;
 }
 

@@ -2380,6 +2380,35 @@ __global__ __launch_bounds__(kRepeatMaxHist) void repeat_logits_kernel(float* lo
 
 __global__ void advance_kernel(DecState* stt, int n) { stt->pos += n; }
 
+// Language detection (tw_language_logits, tw_detect_language; THE RULE is in include/thewhisper.h): one wavefront per row, lane l holds
+// the listed logits j = l and j = l + 64 (n_lang <= kLangMax = 128).  Only the listed logits are read.  The maximum, the lowest token id
+// that attains it and the sum are butterflies over the 64 lanes - the operands and their order depend on n_lang alone, never on the
+// number of rows or on the row's index - and every lane ends with the same m, id and s.  No LDS, no atomics.
+__global__ __launch_bounds__(64) void lang_detect_kernel(const float* logits, int V, const int* ids, int n_lang, int* out_id, float* out_prob) {
+  const int r = blockIdx.x, l = threadIdx.x;
+  const float* row = logits + (long long)r * V;
+  const float ninf = -__builtin_inff();
+  const int j0 = l, j1 = l + 64;
+  const bool on0 = j0 < n_lang, on1 = j1 < n_lang;
+  const int t0 = on0 ? ids[j0] : 0x7fffffff, t1 = on1 ? ids[j1] : 0x7fffffff;
+  float x0 = on0 ? row[t0] : ninf, x1 = on1 ? row[t1] : ninf;
+  if (x0 != x0) x0 = ninf;   // a NaN counts as -inf
+  if (x1 != x1) x1 = ninf;
+  const float m = tw_wave_max(fmaxf(x0, x1));
+  int best = min((on0 && x0 == m) ? t0 : 0x7fffffff, (on1 && x1 == m) ? t1 : 0x7fffffff);   // m == -inf: every listed id qualifies
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+  const bool dead = m == ninf;   // nothing finite in the list: every probability is 0
+  const float e0 = (on0 && !dead) ? expf(x0 - m) : 0.f, e1 = (on1 && !dead) ? expf(x1 - m) : 0.f;
+  const float s = tw_wave_sum(e0 + e1);
+  if (l == 0) out_id[r] = best;
+  if (out_prob) {
+    float* p = out_prob + (long long)r * n_lang;
+    if (on0) p[j0] = dead ? 0.f : e0 / s;
+    if (on1) p[j1] = dead ? 0.f : e1 / s;
+  }
+}
+
 // Beam search (tw_generate_beam, api.hip; THE RULE is in include/thewhisper.h; the tables are BeamArgs', tw_common.h): a step is the
 // ordinary decoder pass over n_clips x K rows, then
 //  * beam_part_kernel: the slicing, the register-resident slice and the vector / scalar paths of sampler_part_kernel.  Per (row, slice):
@@ -3160,6 +3189,12 @@ hipError_t launch_repeat(const RepeatArgs& a, hipStream_t st) {
 hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist, int ld, const int* n_hist, const int* tab, hipStream_t st) {
   if (rows < 1 || rows > 64 || V < 1 || ld < 0 || !logits || !hist || !n_hist || !tab) return hipErrorInvalidValue;
   hipLaunchKernelGGL(repeat_logits_kernel, dim3(rows), dim3(kRepeatMaxHist), 0, st, logits, V, hist, ld, n_hist, tab);
+  return hipGetLastError();
+}
+
+hipError_t launch_lang_detect(const float* logits, int V, int rows, const int* ids, int n_lang, int* out_id, float* out_prob, hipStream_t st) {
+  if (rows < 1 || V < 1 || n_lang < 1 || n_lang > kLangMax || !logits || !ids || !out_id) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lang_detect_kernel, dim3(rows), dim3(64), 0, st, logits, V, ids, n_lang, out_id, out_prob);
   return hipGetLastError();
 }
 

@@ -472,6 +472,11 @@ hipError_t launch_repeat(const RepeatArgs& a, hipStream_t st);
 // The same per-row rule on caller-provided data (tw_repeat_logits): row r reads hist[r * ld .. + n_hist[r]) and tab[r], tab[64 + r].
 hipError_t launch_repeat_logits(float* logits, int V, int rows, const int* hist, int ld, const int* n_hist, const int* tab, hipStream_t st);
 hipError_t launch_advance(DecState* stt, int n, hipStream_t st);     // pos += n only (teacher-forced stepping, prefill)
+// Language detection (tw_language_logits, tw_detect_language; THE RULE is in include/thewhisper.h; k_decode.hip: lang_detect_kernel):
+// one workgroup per row of logits [rows][V] reads the n_lang listed logits (ids: device, distinct, inside [0, V)) and stores
+// out_id[row] and - out_prob non-null - out_prob[row][0 .. n_lang).  A row's results do not depend on rows or on the row's index.
+constexpr int kLangMax = 128;           // TW_LANG_MAX
+hipError_t launch_lang_detect(const float* logits, int V, int rows, const int* ids, int n_lang, int* out_id, float* out_prob, hipStream_t st);
 
 // Beam search (tw_generate_beam; THE RULE is in include/thewhisper.h; k_decode.hip: beam_part_kernel, beam_finish_kernel,
 // beam_reorder_kernel).  Beam k of clip c is row k * n_clips + c of every per-row table (beam-major): `s` carries what sampler_mask()

@@ -494,6 +494,38 @@ class WhisperEngine:
             self._publish()
         return out
 
+    # ---- language detection (include/thewhisper.h: THE RULE) ------------------------------------
+    def detect_language(self, B: int, sot_id: int, lang_ids: Sequence[int]) -> Dict[str, np.ndarray]:
+        """Rows 0 .. B-1 of the cross K/V (``encode`` + ``cross_kv`` first): one decoder step on ``sot_id`` and the language rule on that
+        step's logits (tw_detect_language) - ``ids`` int32 [B], the winning token id per row, and ``probs`` float32 [B, n_lang], the
+        softmax over the listed ids in the order of ``lang_ids``.  Only those come back, not the logits.  It belongs in front of the
+        generate call of a pass: it rewinds the decoder and overwrites the alignment rows of a previous decode."""
+        ids = np.ascontiguousarray(np.asarray(list(lang_ids), dtype=np.int32).reshape(-1))
+        n = int(ids.size)
+        out_id = np.zeros(max(int(B), 1), dtype=np.int32)
+        out_p = np.zeros((max(int(B), 1), max(n, 1)), dtype=np.float32)
+        rc = self.lib.tw_detect_language(self.ctx, int(B), int(sot_id), ids.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                         out_id.ctypes.data_as(C.POINTER(C.c_int32)), out_p.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
+        self._chk(rc, "tw_detect_language")
+        return {"ids": out_id, "probs": out_p}
+
+    def language_logits(self, logits: torch.Tensor, lang_ids: Sequence[int]) -> Dict[str, np.ndarray]:
+        """The language rule on caller-provided logits (tw_language_logits): ``logits`` - a contiguous float32 ``[rows, V]`` tensor on this
+        engine's device, only read.  Returns ``ids`` int32 [rows] and ``probs`` float32 [rows, n_lang]."""
+        if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous() or logits.device != torch.device(self.device):
+            raise ValueError("language_logits: a contiguous float32 [rows, V] tensor on the engine's device")
+        rows, V = int(logits.shape[0]), int(logits.shape[1])
+        ids = np.ascontiguousarray(np.asarray(list(lang_ids), dtype=np.int32).reshape(-1))
+        n = int(ids.size)
+        out_id = np.zeros(max(rows, 1), dtype=np.int32)
+        out_p = np.zeros((max(rows, 1), max(n, 1)), dtype=np.float32)
+        self._adopt(logits)
+        rc = self.lib.tw_language_logits(int(torch.device(self.device).index or 0), C.c_void_p(logits.data_ptr()), V, rows,
+                                         ids.ctypes.data_as(C.POINTER(C.c_int32)), n, out_id.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         out_p.ctypes.data_as(C.POINTER(C.c_float)), self._sp())
+        _cabi.check(self.lib, None, rc, "tw_language_logits")     # (context-free: the message is the library's, not the context's)
+        return {"ids": out_id, "probs": out_p}
+
     # ---- A9/A10 ------------------------------------------------------------------------------
     @staticmethod
     def _greedy_opts(eos_id, pad_id, timestamps, no_timestamps_id, max_initial_timestamp_index, begin_suppress, suppress, min_new_tokens=0,

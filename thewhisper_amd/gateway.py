@@ -280,6 +280,23 @@ class SessionHost:
         with self._engine_lock:
             return self.base_backend.transcribe(audio, 0.0, sr)
 
+    def transcribe_language(self, audio: np.ndarray, sr: int, language: Optional[str] = None):
+        """``transcribe`` on an auto-language backend: ``language`` (a two-letter code) is the request's own, None = detect.  Returns
+        ``(words, [{id, code, prob} per chunk])``."""
+        import queue as _queue
+
+        if self.hub is not None:
+            try:
+                fut = self.hub.submit(audio, 0.0, sr, language=language)
+            except _queue.Full as e:
+                raise HostBusy("request queue full") from e
+            except RuntimeError as e:
+                raise HostBusy(str(e)) from e
+            return fut.result(), (getattr(fut, "language_result", None) or [])
+        with self._engine_lock:
+            words = self.base_backend.transcribe(audio, 0.0, sr, language=language)
+            return words, list(self.base_backend.last_language)
+
     def health(self) -> Dict[str, Any]:
         return {"passes": (self.hub.passes if self.hub is not None else None), "rows": (self.hub.rows if self.hub is not None else None),
                 "last_rows": (list(self.hub.batches)[-24:] if self.hub is not None else None),
@@ -305,7 +322,9 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
     """FastAPI application.  ``backend``: a ``BatchingHub`` (concurrent requests share passes), a bare ``AMDWhisperBackend``, a
     ready ``SessionHost`` or a ``thewhisper_amd.node.NodeRouter`` (one host process per GPU).  ``auth_token``: when set,
     requests must carry ``Authorization: Bearer <token>``.  ``lang_id``: when set, a request's ``X-Lang-Id`` must equal it
-    (the engine is built for one language prompt).  ``vad``: a ``thewhisper_amd.vad.VadService`` - sessions are then gated
+    (the engine is built for one language prompt).  ``lang_id=None`` over an auto-language backend (``AMDWhisperBackend(language=None)``,
+    ``--language auto``): ``X-Lang-Id`` is honoured per request (400 for an unknown code), without the header the language is detected
+    on the device, and the JSON answer carries ``"language": code``.  ``vad``: a ``thewhisper_amd.vad.VadService`` - sessions are then gated
     like the reference's default ``use_vad=True`` (energy rule, not silero - vad.py), all sessions' frames in shared launches.
 
     ``resample`` (off by default; ``--resample``): audio at other rates, as int16 and with several channels is converted on the
@@ -351,6 +370,10 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
                            resample=resample, resample_kernel=resample_kernel)
     app.state.host = host
     sample_rate = host.sample_rate
+    # an auto-language backend behind a gateway that was not pinned to one language: the language is the request's
+    auto_backend = getattr(host, "base_backend", None) if not lang_id else None
+    if not getattr(auto_backend, "auto_language", False) or not hasattr(host, "transcribe_language"):
+        auto_backend = None
 
     def session_format(sample_rate_q, encoding, channels):
         """The three session parameters of a create request -> arguments of ``host.create`` (none for a plain session, so a host
@@ -465,6 +488,16 @@ def create_app(backend, auth_token: str = "", model_name: str = "", lang_id: Opt
             raise HTTPException(status_code=400, detail=str(e)) from e
         if sr != sample_rate and not resample:
             raise HTTPException(status_code=400, detail=f"expected {sample_rate} Hz audio, got {sr} Hz")
+        if auto_backend is not None:
+            if x_lang_id:
+                try:
+                    auto_backend.language_id(x_lang_id)
+                except ValueError as e:
+                    raise HTTPException(status_code=400, detail=str(e)) from e
+            if len(audio) == 0:
+                return {**words_to_response([], model_name), "language": x_lang_id or None}
+            words, langs = await guarded(host.transcribe_language, audio, sr, x_lang_id or None)
+            return {**words_to_response(words, model_name), "language": langs[0]["code"] if langs else (x_lang_id or None)}
         if len(audio) == 0:
             return words_to_response([], model_name)
         words = await guarded(host.transcribe, audio, sr)   # blocks until the (shared) passes have decoded it
@@ -544,7 +577,8 @@ def build_host(argv: Optional[List[str]] = None):
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--auth-token", default="")
-    ap.add_argument("--language", default="en")
+    ap.add_argument("--language", default="en", help="the language every request is decoded in, or 'auto': a request's X-Lang-Id is then "
+                         "honoured and requests without the header are detected on the device")
     ap.add_argument("--dtype", default=None, choices=[None, "bf16", "fp16", "fp32"], help="compute dtype of the engine context (default: fp16 - what the reference's streaming backend asks its platform "
                          "pipelines for, R:thestage_speechkit/streaming/streaming_pipeline.py:369-370; a float16 CONTEXT since round 4, "
                          "rounds 1-3 ran such requests in bf16: pass bf16 for that arithmetic)")
@@ -578,7 +612,7 @@ def main(argv: Optional[List[str]] = None):  # pragma: no cover - serves until i
     import uvicorn
 
     host, args = build_host(argv)
-    app = create_app(host, auth_token=args.auth_token, model_name=args.model, lang_id=args.language,
+    app = create_app(host, auth_token=args.auth_token, model_name=args.model, lang_id=None if args.language == "auto" else args.language,
                      host_threads=max(64, 2 * args.gpus * args.max_batch))
     # add_chunk carries base64 PCM in the QUERY STRING, as the reference's route does (R:examples/server.py:135-144): 0.5 s of audio is
     # 43 KB of URL, above h11's default 16 KB request-line limit

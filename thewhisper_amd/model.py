@@ -442,8 +442,11 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         if (kwargs.get("num_beams") or getattr(gc, "num_beams", 1) or 1) > 1:
             return None           # beam calls always run HF's Whisper control flow around the engine call
         lang = kwargs.get("language", getattr(gc, "language", None))
-        if lang is None and getattr(gc, "is_multilingual", False):
-            return None           # language detection is a forward pass whose result selects the prompt per row
+        if isinstance(lang, (list, tuple)):
+            return None           # one language per row, given by the caller: HF's route
+        auto = lang is None and bool(getattr(gc, "is_multilingual", False))
+        if auto and not (hasattr(self._engine, "detect_language") and getattr(gc, "lang_to_id", None)):
+            return None           # an engine without tw_detect_language: detection stays HF's forward pass
         if kwargs.get("temperature") not in (None, 0, 0.0) or kwargs.get("return_dict_in_generate"):
             return None
         if kwargs.get("return_token_timestamps") and kwargs.get("attention_mask") is None:
@@ -459,6 +462,8 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         kw = tuple(sorted((k, frz(v)) for k, v in kwargs.items() if k not in ("input_features", "attention_mask", "generation_config")))
         gcf = tuple(frz(getattr(gc, f, None)) for f in self._GC_FIELDS)
         ah = getattr(gc, "alignment_heads", None)
+        if auto:                  # the language is detected per row (tw_detect_language): a plan of its own, with a language slot
+            return (kw, gcf, frz(ah), kwargs.get("attention_mask") is None, "auto")
         return (kw, gcf, frz(ah), kwargs.get("attention_mask") is None)
 
     def generate(self, *args, **kwargs):  # type: ignore[override]
@@ -487,6 +492,13 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
             return out
         self.last_plan = plan
         sink = self.score_sink
+        if plan.lang_slot is not None:     # every row's first pass detects its language (shortform.Pass.run)
+            langs: List[Optional[int]] = []
+            kw = {} if sink is None else dict(scores_out=sink["entries"], no_speech_id=sink.get("no_speech_id"))
+            out = shortform.generate_shortform(self._require_engine(), plan, kwargs["input_features"], kwargs.get("attention_mask"),
+                                               languages_out=langs, **kw)
+            self.last_languages = [int(x) for x in langs]
+            return out
         if sink is not None:
             return shortform.generate_shortform(self._require_engine(), plan, kwargs["input_features"], kwargs.get("attention_mask"),
                                                 scores_out=sink["entries"], no_speech_id=sink.get("no_speech_id"))
@@ -500,10 +512,23 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         g0, p0 = recs[0]["greedy"], recs[0]["prompt"][0]
         if any("n_pad" in r["greedy"] for r in recs):
             return None   # padded rows: the plan tiles ONE prompt over the batch
-        for r in recs:   # every inner call of the seek loop must have been the same request, every row the same prompt
-            if r["greedy"] != g0 or r["dict"] != recs[0]["dict"] or r["prompt"].shape[1] != len(p0) or (r["prompt"] != p0[None]).any():
-                return None
         gc = kwargs.get("generation_config") or self.generation_config
+        # a call whose language was detected (_plan_key: "auto"): the rows' prompts may differ at index 1, by language tokens only
+        lang_to_id = getattr(gc, "lang_to_id", None) or {}
+        auto = kwargs.get("language", getattr(gc, "language", None)) is None and bool(getattr(gc, "is_multilingual", False)) and bool(lang_to_id)
+        lang_ids = tuple(sorted(int(v) for v in lang_to_id.values())) if auto else ()
+        for r in recs:   # every inner call of the seek loop must have been the same request, every row the same prompt
+            if r["greedy"] != g0 or r["dict"] != recs[0]["dict"] or r["prompt"].shape[1] != len(p0):
+                return None
+            diff = r["prompt"] != p0[None]
+            if auto and len(p0) > 1:
+                if not np.isin(r["prompt"][:, 1], lang_ids).all():
+                    return None
+                diff[:, 1] = False
+            if diff.any():
+                return None
+        if auto and (len(p0) < 2 or len(lang_ids) > 128):
+            return None
         nts = getattr(gc, "no_timestamps_token_id", None)
         rt = kwargs.get("return_timestamps")
         if rt is None:
@@ -512,7 +537,35 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
             init_tokens=tuple(int(x) for x in p0), greedy=dict(g0), eos=int(g0["eos_id"]), pad=int(g0["pad_id"]),
             timestamp_begin=(int(nts) + 1) if nts is not None else int(self.config.vocab_size) + 1,   # HF:...:1409-1415
             return_timestamps=bool(rt), return_token_timestamps=bool(kwargs.get("return_token_timestamps")),
-            return_segments=bool(kwargs.get("return_segments", False)), result_is_dict=bool(recs[0]["dict"]))
+            return_segments=bool(kwargs.get("return_segments", False)), result_is_dict=bool(recs[0]["dict"]),
+            **(dict(lang_slot=1, lang_ids=lang_ids) if auto else {}))
+
+    # -- language detection on the device ---------------------------------------------------------
+    #: the language token ids of the most recent detection (``detect_language`` or a ``generate(language=None)`` call), one per row
+    last_languages: Optional[List[int]] = None
+
+    def detect_language(self, input_features=None, encoder_outputs=None, generation_config=None, num_segment_frames: int = 3000):  # type: ignore[override]
+        """HF's ``detect_language`` (HF:models/whisper/generation_whisper.py:1610-1683) without the full-vocabulary logits: the first
+        ``num_segment_frames`` frames are encoded, and tw_detect_language runs the step at ``decoder_start_token_id`` and picks the language
+        on the device.  Returns the ``LongTensor`` HF returns.  An engine without the entry answers through ``forward``, as HF does."""
+        eng = self._require_engine()
+        if not hasattr(eng, "detect_language"):
+            return super().detect_language(input_features=input_features, encoder_outputs=encoder_outputs,
+                                           generation_config=generation_config, num_segment_frames=num_segment_frames)
+        if input_features is None and encoder_outputs is None:
+            raise ValueError("You have to specify either `input_features` or `encoder_outputs`")
+        if input_features is not None and encoder_outputs is not None:
+            raise ValueError("Make sure to specify only one of `input_features` or `encoder_outputs` - not both!")
+        if input_features is None:
+            raise NotImplementedError("forward() needs input_features: the MI355X engine keeps the encoder states internally and "
+                                      "does not accept `encoder_outputs`")
+        gc = generation_config or self.generation_config
+        B = int(input_features.shape[0])
+        eng.encode(input_features[:, :, :num_segment_frames])
+        eng.cross_kv(B)
+        res = eng.detect_language(B, int(gc.decoder_start_token_id), sorted(int(v) for v in gc.lang_to_id.values()))
+        self.last_languages = [int(x) for x in res["ids"][:B]]
+        return torch.tensor(self.last_languages, dtype=torch.long, device=input_features.device)
 
     # -- teacher-forced forward (language detection, parity tests) ---------------------------------
     def forward(self, input_features=None, decoder_input_ids=None, encoder_outputs=None, **kwargs):  # type: ignore[override]

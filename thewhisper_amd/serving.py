@@ -33,12 +33,20 @@ from .streaming import AMDWhisperBackend
 class _StreamBackend:
     """What a session's StreamingPipeline sees: a blocking ``transcribe`` with the reference signature."""
 
-    def __init__(self, hub: "BatchingHub", stream_id: int):
+    def __init__(self, hub: "BatchingHub", stream_id: int, language: Optional[str] = None):
         self.hub = hub
         self.stream_id = stream_id
+        self.language = language           # a two-letter code every request of this session carries (a hub over an auto backend)
+        self.last_language: List[Dict[str, Any]] = []
 
     def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
-        return self.hub.submit(audio, buffer_start_time, sample_rate, stream_id=self.stream_id).result()
+        if self.language is None:
+            fut = self.hub.submit(audio, buffer_start_time, sample_rate, stream_id=self.stream_id)
+        else:
+            fut = self.hub.submit(audio, buffer_start_time, sample_rate, stream_id=self.stream_id, language=self.language)
+        words = fut.result()
+        self.last_language = getattr(fut, "language_result", None) or []
+        return words
 
 
 class _Prefetcher:
@@ -211,7 +219,7 @@ class _Prefetcher:
 
         audio, t0, sr, fut = item
         try:
-            job = self.codec.open(audio, t0, sr)
+            job = _open_job(self.codec, audio, t0, sr, fut)
         except Exception as e:  # noqa: BLE001  (a malformed buffer fails its own session only)
             self.hub._answer(fut, exc=e)
             return
@@ -237,6 +245,12 @@ class _Prefetcher:
         self.count += n
         self.new_jobs.append(job)
         self.hub.prefetched += n
+
+
+def _open_job(codec, audio, t0, sr, fut):
+    """``codec.open`` for one queued request: the request's language travels on its future (``BatchingHub.submit``)."""
+    lang = getattr(fut, "language", None)
+    return codec.open(audio, t0, sr) if lang is None else codec.open(audio, t0, sr, language=lang)
 
 
 _NOTHING = object()
@@ -297,15 +311,20 @@ class BatchingHub:
         self._worker.start()
 
     # -- session side --------------------------------------------------------------------------------
-    def stream_backend(self) -> _StreamBackend:
+    def stream_backend(self, language: Optional[str] = None) -> _StreamBackend:
         self._next_id += 1
-        return _StreamBackend(self, self._next_id - 1)
+        return _StreamBackend(self, self._next_id - 1, language)
 
-    def submit(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int, stream_id: Optional[int] = None) -> Future:
-        """Parks one request; raises ``RuntimeError`` after ``close()`` and ``queue.Full`` when ``max_pending`` requests wait."""
+    def submit(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int, stream_id: Optional[int] = None,
+               language: Optional[str] = None) -> Future:
+        """Parks one request; raises ``RuntimeError`` after ``close()`` and ``queue.Full`` when ``max_pending`` requests wait.
+        ``language`` (a two-letter code; a hub over an auto-language backend): the request's own language, handed to ``codec.open`` -
+        requests of different languages then share passes.  None: the backend's language, or detection.  The future's
+        ``language_result`` holds the answer's ``{id, code, prob}`` per chunk once it is done."""
         fut: Future = Future()
         fut.t_submit = time.monotonic()  # type: ignore[attr-defined]
         fut.stream_id = stream_id        # type: ignore[attr-defined]
+        fut.language = language          # type: ignore[attr-defined]
         with self._lock:
             if self._closed:
                 raise RuntimeError("BatchingHub is closed")
@@ -523,7 +542,7 @@ class BatchingHub:
                     break
                 audio, t0, sr, fut = item
                 try:
-                    job = codec.open(audio, t0, sr)
+                    job = _open_job(codec, audio, t0, sr, fut)
                 except Exception as e:  # noqa: BLE001  (a malformed buffer fails its own session only)
                     self._answer(fut, exc=e)
                     continue
@@ -575,7 +594,9 @@ class BatchingHub:
             if job is None:
                 return
             try:
-                self._answer(job.future, result=self._codec.close(job))
+                words = self._codec.close(job)
+                job.future.language_result = getattr(job, "language", None)     # ({id, code, prob} per chunk; read after result())
+                self._answer(job.future, result=words)
             except Exception as e:  # noqa: BLE001
                 self._answer(job.future, exc=e)
 

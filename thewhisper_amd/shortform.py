@@ -17,7 +17,9 @@ What is NOT restated: how a call's options become init tokens and logits process
 lists, timestamp grammar switches - HF:...:1455-1608, :1774-1812).  That is *learned*: the first call with a given
 set of options runs HF's own ``generate``; ``_EngineGreedyMixin.generate`` (model.py) records the decoder prompt and the
 engine options it was handed, and ``ShortFormPlan`` replays exactly those.  Calls that are not eligible (prompt ids,
-temperature fallback, thresholds, language detection, long-form input ...) keep going through HF's code.
+temperature fallback, thresholds, a list of languages, long-form input ...) keep going through HF's code.  A call whose language is
+detected (``language=None``) is eligible: its plan has a language slot and every pass detects the rows that carry no language yet
+(``Pass.run``, tw_detect_language).
 
 Results are identical to HF's control flow by construction of every step (same torch ops in the same order for the
 floating-point bits: time offsets, token-timestamp offsets) and by test: tests/test_shortform.py compares against HF's
@@ -52,6 +54,11 @@ class ShortFormPlan:
     time_precision: float = 0.02
     time_precision_features: float = 0.01
     input_stride: int = 2
+    # a call whose language is detected (learned from ``generate(language=None)``, model.py): ``lang_slot`` = the prompt index that holds
+    # the row's language token (init_tokens has the learning call's first row there), ``lang_ids`` = every language token id, sorted.
+    # None / (): every row's prompt is ``init_tokens`` and a pass is what it has always been
+    lang_slot: Optional[int] = None
+    lang_ids: Tuple[int, ...] = ()
 
     @property
     def n_prompt(self) -> int:
@@ -62,7 +69,7 @@ class ChunkWork:
     """Decoding state of one <= chunk_length_s piece of audio (one row of a ``generate`` batch)."""
 
     __slots__ = ("feats", "num_frames", "max_frames", "seek", "segments", "passes", "tag", "forced", "draft", "draft_result", "first_pass", "scores",
-                 "temperatures", "attempts", "chunk_index", "bias")
+                 "temperatures", "attempts", "chunk_index", "bias", "language", "language_probs")
 
     def __init__(self, feats: torch.Tensor, num_frames: Optional[int], tag: Any = None):
         # SURVEY.md section 8f-3 (opt-in, streaming.py): output tokens of the FIRST seek iteration that are already known - they
@@ -82,6 +89,11 @@ class ChunkWork:
         # optional per-chunk ``sequence_bias`` (HF's list or dict form): a session's own phrase list.  A pass hands the engine one list
         # per row, the plan-level list first (``WhisperEngine.generate_greedy(sequence_bias_rows=...)``); None = the plan's alone
         self.bias: Any = None
+        # plans with a ``lang_slot`` only: the chunk's language TOKEN ID; None = the first pass that runs the chunk detects it
+        # (``WhisperEngine.detect_language`` over the pass's rows), stores it here with the row's probabilities (``language_probs``:
+        # float32 [len(plan.lang_ids)]) and the chunk's later seek iterations reuse it - HF detects once per generate call
+        self.language: Optional[int] = None
+        self.language_probs: Optional[np.ndarray] = None
         self.feats = feats                      # [n_mels, frames] log-mel (device tensor); frames = 2 * T for short-form
         self.num_frames = num_frames            # frames of real audio (attention_mask.sum), None if no mask was given
         self.max_frames = int(feats.shape[-1])  # HF:...:1769 - short-form: the padded feature length, not the audio length
@@ -290,6 +302,21 @@ class Pass:
         self.engine.adopt_cross_kv(side_engine, side_slot0, n_new, len(self.works))
         self.works.extend(works)
 
+    def _language_prompt(self, prompt: np.ndarray) -> np.ndarray:
+        """A plan with a ``lang_slot``: every row's own language token in its prompt.  Rows without one are detected first - one
+        ``detect_language`` call over ALL rows of the pass, behind the encoder stage of every group (adopted rows included), in front of
+        the decode; rows whose language was given ignore the answer."""
+        plan, works = self.plan, self.works
+        slot = int(plan.lang_slot)
+        if any(w.language is None for w in works):
+            res = self.engine.detect_language(len(works), int(plan.init_tokens[slot - 1]), plan.lang_ids)
+            for i, w in enumerate(works):
+                if w.language is None:
+                    w.language = int(res["ids"][i])
+                    w.language_probs = np.asarray(res["probs"][i], dtype=np.float32).copy()
+        prompt[:, slot] = [int(w.language) for w in works]
+        return prompt
+
     def _greedy_kw(self) -> Dict[str, Any]:
         """``plan.greedy`` itself when no chunk of the pass carries a bias (exactly the engine call of a pass without the feature), else
         a copy whose ``sequence_bias_rows`` holds, per row, the plan-level list followed by the chunk's own."""
@@ -312,6 +339,8 @@ class Pass:
             raise ValueError("empty pass")
         n_prompt = plan.n_prompt
         prompt = np.tile(np.asarray(plan.init_tokens, dtype=np.int32), (B, 1))
+        if plan.lang_slot is not None:
+            prompt = self._language_prompt(prompt)
         n_forced = 0
         if any(w.forced is not None and w.seek == 0 for w in works):
             # forced output prefixes (first iteration only): one length for the whole pass (the engine's loop is in lock-step)
@@ -546,11 +575,13 @@ def assemble(plan: ShortFormPlan, works: Sequence[ChunkWork], device) -> Any:
 
 
 def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                       scores_out: Optional[List[Dict[str, Any]]] = None, no_speech_id: Optional[int] = None, fallback=None) -> Any:
+                       scores_out: Optional[List[Dict[str, Any]]] = None, no_speech_id: Optional[int] = None, fallback=None,
+                       languages_out: Optional[List[Optional[int]]] = None) -> Any:
     """Drop-in for ``WhisperGenerationMixin.generate`` on an eligible batch: identical return value, fewer Python layers.
     ``scores_out`` (a list): every pass also scores its tokens (``Pass(score=True)``) and the entries are appended to it, row by row,
     a row's seek iterations in order.  ``fallback`` (a ``fallback.FallbackPolicy``): every pass drives the temperature ladder
-    (``Pass(fallback=...)``); row i of the batch is chunk i of the request."""
+    (``Pass(fallback=...)``); row i of the batch is chunk i of the request.  A plan with a ``lang_slot``: every row's language is detected
+    by its first pass (the works start with ``language=None``); ``languages_out`` (a list) receives the token id per row."""
     B = int(input_features.shape[0])
     nf: List[Optional[int]] = [None] * B
     if plan.return_token_timestamps and attention_mask is not None:
@@ -575,4 +606,6 @@ def generate_shortform(engine, plan: ShortFormPlan, input_features: torch.Tensor
             raise RuntimeError(f"a chunk needed more than {MAX_SEEK_PASSES} seek passes (the decoder keeps seeking to frame 0)")
     if scores_out is not None:
         scores_out.extend(e for w in works for e in w.scores)
+    if languages_out is not None:
+        languages_out.extend(w.language for w in works)
     return assemble(plan, works, input_features.device)

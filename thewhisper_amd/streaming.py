@@ -31,7 +31,7 @@ class AMDWhisperBackend:
         model_size: str = "S",
         chunk_length_s: int = 10,
         torch_dtype: "torch.dtype | None" = None,
-        language: str = "en",
+        language: Optional[str] = "en",
         feature_extractor=None,
         tokenizer=None,
         revision: str = "main",
@@ -47,6 +47,7 @@ class AMDWhisperBackend:
         repetition_penalty: Optional[float] = None,
         no_repeat_ngram_size: Optional[int] = None,
         num_beams: Optional[int] = None,
+        sticky_language: bool = False,
         **pipeline_kwargs,
     ):
         """``reuse_committed_prefix`` (never the default): the reference scheduler hands over, every 0.5 s,
@@ -108,7 +109,15 @@ class AMDWhisperBackend:
         the generate options).  One chunk takes ``num_beams`` engine rows: ``batch_size >= num_beams`` is needed.  The calls run HF's
         control flow around the engine call.  ``draft_previous_tick=None`` resolves to off (a draft does not go with beams), an explicit
         ``True`` raises ``ValueError``; hotwords, the repeat options, ``token_scores``, ``temperature_fallback`` and
-        ``reuse_committed_prefix`` are refused by name."""
+        ``reuse_committed_prefix`` are refused by name.
+
+        ``language=None`` (or ``"auto"``): the language of every chunk is detected on the device (tw_detect_language) by the pass that
+        decodes it - the generate options carry ``language=None`` and the learned short-form plan has a language slot (model.py), so
+        drafts, the temperature fallback, hotwords and token scores keep working.  ``last_language``: for the most recent call, one
+        ``{"id", "code", "prob"}`` per chunk (the language token's id, the inner text of its ``<|xx|>`` token, the winner's probability -
+        None for a chunk whose language was given).  ``sticky_language`` (default False): the first chunk's language of the first call
+        after construction or ``reset()`` is stamped on every later chunk of the stream - a rolling buffer re-detected every 0.5 s can
+        otherwise flip language mid-sentence.  ``language_id(code)`` resolves a two-letter code."""
         from .asr_pipeline import ASRPipeline
 
         self.num_beams: Optional[int] = None
@@ -137,7 +146,12 @@ class AMDWhisperBackend:
         self.chunk_length_s: float = chunk_length_s
         self.sample_rate: int = 16000
         self.device: str = "cuda"  # ROCm exposes MI355X as "cuda", as on the nvidia platform (R:...:365)
-        self.language: str = language
+        self.auto_language = language is None or language == "auto"
+        self.language: Optional[str] = None if self.auto_language else language
+        self.sticky_language = bool(sticky_language)
+        self._sticky_id: Optional[int] = None     # sticky_language: the stream's language once its first chunk has been detected
+        self._auto_route = self.auto_language     # transcribe() goes through the job codec (False while the codec learns, or cannot)
+        self.last_language: List[Dict[str, Any]] = []
         self.asr_pipeline = asr_pipeline or ASRPipeline(
             model,
             model_size=model_size,
@@ -219,6 +233,24 @@ class AMDWhisperBackend:
         self._hotword_bias = sequence_bias_for(tok, phrases, float(boost))
         self.hotwords, self.hotword_boost = phrases, float(boost)
 
+    # -- languages ---------------------------------------------------------------------------------------------------------
+    def language_id(self, code: str) -> int:
+        """The token id of a two-letter language code (``generation_config.lang_to_id["<|xx|>"]``); ``ValueError`` for an unknown one."""
+        table = getattr(getattr(self.asr_pipeline.model, "generation_config", None), "lang_to_id", None) or {}
+        key = code if isinstance(code, str) and code.startswith("<|") else f"<|{code}|>"
+        if key not in table:
+            raise ValueError(f"unknown language code {code!r}")
+        return int(table[key])
+
+    def language_entry(self, token_id: Optional[int], prob: Optional[float] = None) -> Dict[str, Any]:
+        """``{"id", "code", "prob"}`` of a language token: ``code`` is the inner text of the tokenizer's ``<|xx|>`` token."""
+        if token_id is None:
+            return {"id": None, "code": None, "prob": None}
+        tok = getattr(self.asr_pipeline, "tokenizer", None)
+        text = tok.convert_ids_to_tokens(int(token_id)) if tok is not None else None
+        code = text[2:-2] if isinstance(text, str) and text.startswith("<|") and text.endswith("|>") else text
+        return {"id": int(token_id), "code": code, "prob": None if prob is None else float(prob)}
+
     def to_engine_rate(self, audio, sample_rate: int):
         """``(audio, sample_rate)`` as the engine wants it: a buffer at another rate (or int16 / multi-channel) goes through
         ``tw_resample`` first (resample.py; the reference does this with librosa before its backend is called,
@@ -268,12 +300,21 @@ class AMDWhisperBackend:
             model.score_sink = None
             self.last_scores = entries
 
-    def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> List[Dict[str, Any]]:
+    def transcribe(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int, language: Optional[str] = None) -> List[Dict[str, Any]]:
+        """``language`` (a two-letter code; an auto-language backend only): this request's own language - nothing is detected."""
+        if language is not None and not self._auto_route:
+            if language != self.language:
+                raise ValueError(f"this backend serves language '{self.language}' (the engine is built for one language prompt)")
+            language = None
         audio, sample_rate = self.to_engine_rate(audio, sample_rate)
-        if self.reuse_committed_prefix or self.draft_previous_tick or self.temperature_fallback is not None or self._hotword_bias:
-            words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate))
+        if (self.reuse_committed_prefix or self.draft_previous_tick or self.temperature_fallback is not None or self._hotword_bias
+                or self._auto_route):
+            words = self._transcribe_with_reuse(np.asarray(audio), float(buffer_start_time), int(sample_rate), language)
             if words is not None:
                 return words
+            if language is not None:
+                raise ValueError("a per-request language needs the restated short-form loop, and this backend's call is not eligible "
+                                 "for it (job_codec() is None)")
             if self._hotword_bias:
                 raise ValueError("hotwords need the restated short-form loop, and this backend's call is not eligible for it "
                                  "(job_codec() is None)")
@@ -286,6 +327,9 @@ class AMDWhisperBackend:
             generate_kwargs=self._generate_kwargs(),
             chunk_length_s=self.chunk_length_s,
         )
+        if self.auto_language:     # HF's control flow around the engine: what the model object detected last
+            model = getattr(self.asr_pipeline, "model", None)
+            self.last_language = [self.language_entry(i) for i in (getattr(model, "last_languages", None) or [])]
         return self._to_tokens(result, len(audio) / sample_rate, buffer_start_time)
 
     # -- decoder-side reuse between the ticks of one stream (opt-in) -------------------------------
@@ -293,6 +337,7 @@ class AMDWhisperBackend:
         """Forget the previous call (``reuse_committed_prefix``): the next buffer is decoded afresh.  For the owner of the stream to
         call when its scheduler restarts at t = 0 (R:thestage_speechkit/streaming/streaming_pipeline.py:953-976 ``clear``)."""
         self._last = None
+        self._sticky_id = None      # sticky_language: the next call detects again
 
     def _forced_prefix(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> Optional[np.ndarray]:
         """Tokens of the previous call that may be forced in this one, or None.  Eligible: same buffer start, buffer not shorter
@@ -325,7 +370,7 @@ class AMDWhisperBackend:
             return None
         return np.asarray(ids[:keep], dtype=np.int32)
 
-    def _transcribe_with_reuse(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int):
+    def _transcribe_with_reuse(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int, language: Optional[str] = None):
         """The call through the restated short-form loop (shortform.py) with a forced prefix on the first seek iteration; None
         when this backend cannot (no learned plan, a buffer longer than one chunk): the ordinary call then runs."""
         from . import shortform
@@ -334,11 +379,13 @@ class AMDWhisperBackend:
             codec = self.job_codec()
             if codec is None or not codec.learn():        # (the plan is learned from one ORDINARY call of this backend: JobCodec.learn)
                 self.reuse_committed_prefix = self.draft_previous_tick = False
+                self._auto_route = False                  # (an auto backend then detects inside HF's generate, call by call)
                 return None                               # not eligible on this pipeline: stays the plain backend
             self._reuse_codec = codec
         codec = self._reuse_codec
         self.reuse_stats["calls"] += 1
-        job = codec.open(audio, buffer_start_time, sample_rate)      # (the hotword bias travels on the works: JobCodec.open)
+        # (the hotword bias travels on the works: JobCodec.open; so does a request's own language)
+        job = codec.open(audio, buffer_start_time, sample_rate) if language is None else codec.open(audio, buffer_start_time, sample_rate, language=language)
         eng = self.asr_pipeline.model.engine
         if len(job.works) != 1:
             self._last = None
@@ -363,6 +410,11 @@ class AMDWhisperBackend:
         while not job.done:
             for w in [w for w in job.works if not w.done]:
                 shortform.run_pass(eng, codec.plan, [w], score=codec.score, no_speech_id=codec.no_speech_id, fallback=codec.fallback)
+                if self.sticky_language and self._sticky_id is None and job.works[0].language is not None:
+                    self._sticky_id = int(job.works[0].language)      # the stream's first chunk: every later chunk carries it
+                    for later in job.works[1:]:
+                        if later.language is None:
+                            later.language = self._sticky_id
                 if w.passes > shortform.MAX_SEEK_PASSES:
                     raise RuntimeError(f"a chunk needed more than {shortform.MAX_SEEK_PASSES} seek passes")
         if len(job.works) == 1 and job.works[0].first_pass is not None and (self.reuse_committed_prefix or self.draft_previous_tick):
@@ -378,17 +430,20 @@ class AMDWhisperBackend:
         if self.token_scores:
             self.last_scores = job.scores
         self.last_fallback = job.fallback
+        self.last_language = job.language
         return words
 
     def transcribe_many(self, requests, batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """Several streams' rolling buffers in ONE pipeline call: [(audio, buffer_start_time, sample_rate), ...].
         HF collates the chunks of different buffers into batched engine calls; per-stream results are unchanged."""
-        if self.temperature_fallback is not None or self._hotword_bias:      # (HF's batched call knows nothing of the options: one short-form call per request)
-            out, log = [], []
+        if self.temperature_fallback is not None or self._hotword_bias or self._auto_route:      # (HF's batched call knows nothing of the options: one short-form call per request)
+            out, log, langs = [], [], []
             for a, t0, sr in requests:
                 out.append(self.transcribe(a, t0, sr))
                 log.extend(self.last_fallback)
+                langs.extend(self.last_language)
             self.last_fallback = log
+            self.last_language = langs
             return out
         requests = [(self.to_engine_rate(a, sr)[0], t0, self.sample_rate) for a, t0, sr in requests]
         audios = [np.asarray(a) for a, _, _ in requests]
@@ -437,7 +492,7 @@ class _NotEligible(Exception):
 class BufferJob:
     """One ``transcribe`` request on its way through the hub: its chunks' decoding states and what post-processing needs."""
 
-    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit", "scores", "fallback")
+    __slots__ = ("works", "meta", "audio_duration", "buffer_start_time", "future", "t_submit", "scores", "fallback", "language")
 
     def __init__(self, works, meta, audio_duration, buffer_start_time):
         self.works = works                        # [shortform.ChunkWork] - one per <= chunk_length_s piece of the buffer
@@ -448,6 +503,7 @@ class BufferJob:
         self.t_submit = 0.0
         self.scores: List[Dict[str, Any]] = []     # JobCodec.close: the chunks' score entries when the backend asked for them
         self.fallback: List[Dict[str, Any]] = []   # JobCodec.close: {temperature, attempts} per seek iteration (temperature_fallback)
+        self.language: List[Dict[str, Any]] = []   # JobCodec.close: {id, code, prob} per chunk (a plan with a language slot)
 
     @property
     def done(self) -> bool:
@@ -487,6 +543,8 @@ class JobCodec:
         model.last_plan = None
         b = self.backend
         mode = (b.reuse_committed_prefix, b.draft_previous_tick)     # (the ORDINARY call: the reuse / draft paths bypass HF's generate)
+        auto = getattr(b, "_auto_route", False)                      # (... and an auto-language backend's route through this codec)
+        b._auto_route = False
         policy = getattr(b, "temperature_fallback", None)            # (... and so does the temperature fallback)
         bias = getattr(b, "_hotword_bias", None)                     # (... and the hotword bias: a per-chunk list, not part of the plan)
         b.reuse_committed_prefix = b.draft_previous_tick = False
@@ -498,15 +556,27 @@ class JobCodec:
             b.reuse_committed_prefix, b.draft_previous_tick = mode
             b.temperature_fallback = policy
             b._hotword_bias = bias
+            b._auto_route = auto
         plan = model.last_plan
         if plan is None or not plan.return_token_timestamps or not plan.return_segments:
             return False
         self.plan = plan
         return True
 
-    def open(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int) -> BufferJob:
-        """Stage 1 (HF:pipelines/automatic_speech_recognition.py:346-482 via ``pipe.preprocess``)."""
+    def open(self, audio: np.ndarray, buffer_start_time: float, sample_rate: int, language: Optional[str] = None) -> BufferJob:
+        """Stage 1 (HF:pipelines/automatic_speech_recognition.py:346-482 via ``pipe.preprocess``).  ``language`` (a two-letter code; a
+        plan with a language slot only): the request's own language - its chunks are not detected.  None: the backend's sticky language
+        if it has one, else every chunk is detected by the pass that decodes it first."""
         from .shortform import ChunkWork
+
+        lang_id = None
+        if getattr(self.plan, "lang_slot", None) is not None:
+            if language is not None:
+                lang_id = self.backend.language_id(language)
+            elif getattr(self.backend, "sticky_language", False):
+                lang_id = self.backend._sticky_id
+        elif language is not None and language != getattr(self.backend, "language", None):
+            raise ValueError(f"this backend serves language '{getattr(self.backend, 'language', None)}' (the engine is built for one language prompt)")
 
         audio, sample_rate = self.backend.to_engine_rate(audio, sample_rate)
         audio = np.asarray(audio)
@@ -520,6 +590,7 @@ class JobCodec:
             # AMDWhisperBackend(hotwords=...): every chunk carries the backend's list, whoever builds the passes (this backend's own
             # loop or a hub that opens the jobs itself); read per job, so set_hotwords takes effect from the next buffer on
             works[-1].bias = getattr(self.backend, "_hotword_bias", None)
+            works[-1].language = lang_id
             meta.append((item["is_last"], item.get("stride")))
         if not works:
             raise ValueError("empty audio buffer")
@@ -541,5 +612,11 @@ class JobCodec:
         pol = self.fallback
         flt = {"top_k": pol.top_k, "top_p": pol.top_p} if pol is not None and (pol.top_k is not None or pol.top_p is not None) else {}
         job.fallback = [{"temperature": t, "attempts": a, **flt} for w in job.works for t, a in zip(w.temperatures, w.attempts)]
+        if getattr(self.plan, "lang_slot", None) is not None:
+            ids = self.plan.lang_ids
+            job.language = [self.backend.language_entry(w.language, None if w.language_probs is None or w.language not in ids
+                                                        else w.language_probs[ids.index(w.language)]) for w in job.works]
+            if getattr(self.backend, "sticky_language", False) and self.backend._sticky_id is None and job.works[0].language is not None:
+                self.backend._sticky_id = int(job.works[0].language)
         result = self.pipe.postprocess(outs, **self.post)
         return AMDWhisperBackend._to_tokens(result, job.audio_duration, job.buffer_start_time)

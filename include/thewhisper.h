@@ -38,9 +38,21 @@ enum { TW_F32 = 0, TW_BF16 = 1, TW_F16 = 2,
        TW_BF16_MXFP8 = 3, /* context dtype only: bf16 activations / encoder, decoder projection weights as MXFP8 (OCP e4m3 +
                             one power-of-two scale per 32 values) AND the activations quantised the same way in registers, on
                             v_mfma_scale_f32_16x16x128_f8f6f4 ("W8A8"); fp8 cross-attention K / V caches; BASELINE config 5 */
-       TW_BF16_W8A16 = 4  /* context dtype only: the same MXFP8 weights and fp8 cross K / V caches, but the weight fragments are
+       TW_BF16_W8A16 = 4, /* context dtype only: the same MXFP8 weights and fp8 cross K / V caches, but the weight fragments are
                             widened to bf16 in registers and contracted with the UNQUANTISED bf16 activations on the bf16 MFMA
-                            ("W8A16": same bytes from HBM, no activation-quantisation error); up to 64 streams */ };
+                            ("W8A16": same bytes from HBM, no activation-quantisation error); up to 64 streams */
+       TW_F16_W8A16 = 5   /* context dtype only: TW_BF16_W8A16 on a float16 base.  Activations, the encoder, the cross-K/V
+                            projection GEMM and the self-attention caches are those of a TW_F16 context (saturating at 65504); the
+                            decoder projections and the logits projection are MXFP8 with the block structure, scale rule
+                            (sb = max(E - 7, 1)) and fragment layout of TW_BF16_W8A16; the cross K / V^T caches are e4m3 of the
+                            float16-rounded values with one scale byte per (key, head).  Rounding rule of the weights: the
+                            LayerNorm fold is W' = f16(g * W) (one round-to-nearest-even; bf16 contexts round to bf16), W' is
+                            quantised per block of 32 to e4m3(W' / 2^(sb-127)) - magnitudes above 63488 = 248 x 2^8 are clamped to it first,
+                            here and in the cross K / V^T: the image of a larger one, 65536, is outside float16 - and a row sees
+                            RNE_f16(e4m3 x 2^(sb-127)), a pure function of the stored bytes.  That product is exact whenever the
+                            block's largest magnitude is >= 2^-8; in a block of smaller weights an element below the float16
+                            normal range (2^-14) is rounded to the subnormal grid (|error| <= 2^-25) and one below 2^-25 becomes
+                            zero.  Up to 64 streams; d_model and ffn multiples of 128; no beam search */ };
 
 /* error codes */
 enum {
@@ -75,7 +87,7 @@ typedef struct tw_config {
   int32_t dtype;                 /* TW_BF16 (production), TW_F16 (the reference's streaming default dtype,
                                     R:thestage_speechkit/streaming/streaming_pipeline.py:369-370: same MFMA rate, 10 mantissa bits,
                                     activations saturate at 65504 as HF clamps its float16 hidden states), TW_F32 (strict-parity
-                                    mode), TW_BF16_MXFP8 / TW_BF16_W8A16 (fp8 decoder weights) */
+                                    mode), TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 (fp8 decoder weights) */
   int32_t n_align_heads;         /* alignment heads for word timestamps (generation_config.alignment_heads) */
   int32_t align_heads[2 * TW_MAX_ALIGN_HEADS]; /* (layer, head) pairs */
   int32_t device;                /* HIP device ordinal */

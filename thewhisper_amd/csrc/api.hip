@@ -63,8 +63,8 @@ struct ScoreBlock { float *masked, *raw, *no_speech; };  // tw_score_tokens' res
 struct tw_ctx {
   tw_config cfg{};
   int dtype = 1;
-  bool w8 = false;   // decoder projection weights in MXFP8 (TW_BF16_MXFP8 / TW_BF16_W8A16 contexts)
-  int a16 = 0;       // ... contracted as bf16 after widening in registers (TW_BF16_W8A16)
+  bool w8 = false;   // decoder projection weights in MXFP8 (TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 contexts)
+  int a16 = 0;       // ... contracted as bf16 (float16) after widening in registers (TW_BF16_W8A16, TW_F16_W8A16)
   // "cross query ahead" (decode_core): the decoder's cross-attention query projection is folded into the two launches before
   // it, which saves one dependent launch per layer and step.  du = float32 [Bmax][d] pre-activation of that projection.
   bool fuse_cq = false;
@@ -338,11 +338,12 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   *out = nullptr;
   if (cfg->heads <= 0 || cfg->d_model != cfg->heads * 64)
     return fail(nullptr, TW_EINVAL, "head_dim must be 64 (d_model=%d heads=%d)", cfg->d_model, cfg->heads);
-  if (cfg->dtype != TW_BF16 && cfg->dtype != TW_F32 && cfg->dtype != TW_F16 && cfg->dtype != TW_BF16_MXFP8 && cfg->dtype != TW_BF16_W8A16)
-    return fail(nullptr, TW_EINVAL, "dtype must be TW_BF16, TW_F16, TW_F32, TW_BF16_MXFP8 or TW_BF16_W8A16");
-  const bool cfg_w8 = cfg->dtype == TW_BF16_MXFP8 || cfg->dtype == TW_BF16_W8A16;
+  if (cfg->dtype != TW_BF16 && cfg->dtype != TW_F32 && cfg->dtype != TW_F16 && cfg->dtype != TW_BF16_MXFP8 && cfg->dtype != TW_BF16_W8A16 &&
+      cfg->dtype != TW_F16_W8A16)
+    return fail(nullptr, TW_EINVAL, "dtype must be TW_BF16, TW_F16, TW_F32, TW_BF16_MXFP8, TW_BF16_W8A16 or TW_F16_W8A16");
+  const bool cfg_w8 = cfg->dtype == TW_BF16_MXFP8 || cfg->dtype == TW_BF16_W8A16 || cfg->dtype == TW_F16_W8A16;
   if (cfg_w8 && (cfg->d_model % 128 || cfg->ffn % 128))
-    return fail(nullptr, TW_EINVAL, "TW_BF16_MXFP8 / TW_BF16_W8A16 need d_model and ffn to be multiples of 128");
+    return fail(nullptr, TW_EINVAL, "TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 need d_model and ffn to be multiples of 128");
   if (cfg->d_model % 64 || cfg->ffn % 64 || cfg->d_model > 1280)
     return fail(nullptr, TW_EINVAL, "d_model/ffn must be multiples of 64 and d_model <= 1280");
   if (cfg->max_batch < 1 || cfg->max_batch > 64) return fail(nullptr, TW_EINVAL, "max_batch must be in [1,64]");
@@ -363,8 +364,10 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   tw_ctx* c = new tw_ctx();
   c->cfg = *cfg;
   c->w8 = cfg_w8;
-  c->a16 = cfg->dtype == TW_BF16_W8A16;
-  c->dtype = c->w8 ? (int)TW_BF16 : cfg->dtype;
+  c->a16 = cfg->dtype == TW_BF16_W8A16 || cfg->dtype == TW_F16_W8A16;
+  // the 16-bit type everything but the quantised operands is kept and computed in: a TW_F16_W8A16 context issues the launches of
+  // a TW_F16 context for the encoder, the cross-K/V GEMM, the self-attention and the weight fold
+  c->dtype = c->w8 ? (cfg->dtype == TW_F16_W8A16 ? (int)TW_F16 : (int)TW_BF16) : cfg->dtype;
   c->esz = c->dtype == TW_F32 ? 4 : 2;
   c->d = cfg->d_model; c->H = cfg->heads; c->ffn = cfg->ffn; c->V = cfg->vocab;
   c->T = cfg->source_positions; c->Tp = (c->T + 63) / 64 * 64; c->P = cfg->target_positions;
@@ -705,9 +708,9 @@ int tw_finalize_weights(tw_ctx* c, void* stream) {
       const size_t Np = (size_t)(N + 15) / 16 * 16;
       const int tr = tr_out && N <= 2048 && N % 16 == 0 ? 8 : 16;
       if (tr_out) *tr_out = tr;
-      if (c->w8) {  // MXFP8 fragments + block scales replace the bf16 rows in the same buffer (half the bytes + 1/32)
+      if (c->w8) {  // MXFP8 fragments + block scales replace the bf16 (float16) rows in the same buffer (half the bytes + 1/32)
         unsigned char* sc = reinterpret_cast<unsigned char*>(scratch);
-        HIPCHK(c, launch_quant_mx8(w, sc, sc + Np * K, N, K, tr, st));
+        HIPCHK(c, launch_quant_mx8(c->dtype, w, sc, sc + Np * K, N, K, tr, st));
         HIPCHK(c, hipMemcpyAsync(w, scratch, Np * K + Np * K / 32, hipMemcpyDeviceToDevice, st));
         *scales = reinterpret_cast<unsigned char*>(w) + Np * K;
       } else {

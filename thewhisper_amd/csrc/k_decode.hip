@@ -142,7 +142,14 @@ __device__ __forceinline__ unsigned sk_from_xor32(unsigned v) {
 // Scale byte sb = max(E - 7, 1), E = biased exponent of the block's largest magnitude; elements = RNE_e4m3(v / 2^(sb-127))
 // (|.| < 256, never overflows).  One exponent more conservative than the OCP MX convention (E - 8 with saturation)
 // because the gfx950 converts return NaN instead of saturating above 464.  Must be called by all 64 lanes.
+// T = float16 (the weight packer of TW_F16_W8A16 contexts; activations are never quantised there): E is the float32 biased exponent of
+// the block's largest magnitude (for a float16 subnormal maximum: of its normalised value), and the elements go through the float32
+// convert (float16 -> float32 is exact: RNE_e4m3(v / 2^(sb-127)) whatever the float16 exponent of v) after a clamp to +-63488 =
+// 248 x 2^8: a larger float16 value would round to e4m3 256 at sb - 127 = 8, i.e. to 65536, which float16 does not hold (the widening
+// convert returns +-inf there, it does not saturate).  The clamp moves such a value by less than half an e4m3 step (2016 < 2048).
+template <typename T>
 __device__ __forceinline__ v8i_t sk_quant_mx8(const u32x4_t (&xv)[4], int& scale_operand) {
+  constexpr bool F16 = ElemTraits<T>::kCode == 2;
   u16x2_t mx[2] = {{0, 0}, {0, 0}};
 #pragma unroll
   for (int m = 0; m < 4; ++m)
@@ -150,20 +157,36 @@ __device__ __forceinline__ v8i_t sk_quant_mx8(const u32x4_t (&xv)[4], int& scale
     for (int q = 0; q < 4; ++q) mx[m >> 1] = __builtin_elementwise_max(mx[m >> 1], __builtin_bit_cast(u16x2_t, xv[m][q] & 0x7fff7fffu));
   const unsigned own = max((unsigned)mx[0][0], (unsigned)mx[0][1]) | (max((unsigned)mx[1][0], (unsigned)mx[1][1]) << 16);
   const unsigned oth = sk_from_xor16(own);
-  const int sb0 = max((int)(max(own & 0xffffu, oth & 0xffffu) >> 7) - 7, 1);
-  const int sb1 = max((int)(max(own >> 16, oth >> 16) >> 7) - 7, 1);
+  const unsigned m0 = max(own & 0xffffu, oth & 0xffffu), m1 = max(own >> 16, oth >> 16);   // magnitudes order like their bit patterns
+  int e0, e1;
+  if constexpr (F16) {
+    e0 = (int)(__builtin_bit_cast(unsigned, (float)__builtin_bit_cast(f16_t, (unsigned short)m0)) >> 23);
+    e1 = (int)(__builtin_bit_cast(unsigned, (float)__builtin_bit_cast(f16_t, (unsigned short)m1)) >> 23);
+  } else {
+    e0 = (int)(m0 >> 7);
+    e1 = (int)(m1 >> 7);
+  }
+  const int sb0 = max(e0 - 7, 1), sb1 = max(e1 - 7, 1);
   const float X0 = __builtin_bit_cast(float, (unsigned)sb0 << 23), X1 = __builtin_bit_cast(float, (unsigned)sb1 << 23);  // 2^(sb-127)
   v8i_t out;
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     // named pairs of the whole vector, not bit_cast<bf16x2>(xv[m][q]): hipcc (ROCm 7.2) folds the latter to element 0 (NB at the top)
-    const bf16x8_t a = __builtin_bit_cast(bf16x8_t, xv[m]);
+    const typename Pair16<T>::x8 a = __builtin_bit_cast(typename Pair16<T>::x8, xv[m]);
     const float X = m < 2 ? X0 : X1;
     s16x2_t lo = {0, 0}, hi = {0, 0};
-    lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_shufflevector(a, a, 0, 1), X, false);
-    lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_shufflevector(a, a, 2, 3), X, true);
-    hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_shufflevector(a, a, 4, 5), X, false);
-    hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_shufflevector(a, a, 6, 7), X, true);
+    if constexpr (F16) {
+      auto c = [](f16_t v) { return __builtin_amdgcn_fmed3f((float)v, -63488.f, 63488.f); };
+      lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(lo, c(a[0]), c(a[1]), X, false);
+      lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(lo, c(a[2]), c(a[3]), X, true);
+      hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(hi, c(a[4]), c(a[5]), X, false);
+      hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(hi, c(a[6]), c(a[7]), X, true);
+    } else {
+      lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_shufflevector(a, a, 0, 1), X, false);
+      lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_shufflevector(a, a, 2, 3), X, true);
+      hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_shufflevector(a, a, 4, 5), X, false);
+      hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_shufflevector(a, a, 6, 7), X, true);
+    }
     out[2 * m] = __builtin_bit_cast(int, lo);
     out[2 * m + 1] = __builtin_bit_cast(int, hi);
   }
@@ -177,17 +200,28 @@ __device__ __forceinline__ v8i_t sk_quant_mx8(const u32x4_t (&xv)[4], int& scale
   return out;
 }
 
-// 16 e4m3 bytes -> two bf16 MFMA operands (bytes 0..7, 8..15), each value multiplied by X = 2^(scale byte - 127): exact in bf16
-// (3 mantissa bits times a power of two).  v_cvt_scalef32_pk_bf16_fp8 converts one byte pair per instruction.
-__device__ __forceinline__ void sk_widen8(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
-  lo[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[0], X, false));
-  lo[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[0], X, true));
-  lo[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[1], X, false));
-  lo[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[1], X, true));
-  hi[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[2], X, false));
-  hi[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[2], X, true));
-  hi[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[3], X, false));
-  hi[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[3], X, true));
+// 16 e4m3 bytes -> two MFMA operands of T (bytes 0..7, 8..15), each value multiplied by X = 2^(scale byte - 127); one byte pair per
+// v_cvt_scalef32_pk_bf16_fp8 / v_cvt_scalef32_pk_f16_fp8.  bf16: exact (3 mantissa bits times a power of two).
+// float16 (TW_F16_W8A16): the convert returns RNE_f16(value x X) with gradual underflow and +-inf above the float16 range (all 256
+// bytes x 254 scale bytes against the float32 widening followed by a float16 cast: profiles/r24_f16cvt_probe.txt, tools/dbg/
+// f16cvt_probe.hip), so the weight a row sees is the pure function  w(byte, sb) = RNE_f16(e4m3(byte) x 2^(sb-127))  of the stored bytes.
+// With sb = max(E - 7, 1) every element is a multiple of 2^(E-143): the product is EXACT for every block whose largest magnitude is
+// >= 2^-8 (E >= 119) - up to the top of the range, because the packers clamp to 63488 (sk_quant_mx8) and 248 x 2^8 is the largest
+// image.  In a block of smaller weights the elements below 2^-14 land on the float16 subnormal grid (|error| <= 2^-25) and those
+// below 2^-25 vanish.  The float16 MFMA takes subnormal operands as they are (same probe: 2^-24 x 1024 = 2^-14).
+template <typename T, bool HI> __device__ __forceinline__ unsigned sk_cvt8_pair(unsigned src, float X) {
+  if constexpr (ElemTraits<T>::kCode == 2) return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)src, X, HI));
+  else return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)src, X, HI));
+}
+template <typename T> __device__ __forceinline__ void sk_widen8(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
+  lo[0] = sk_cvt8_pair<T, false>(raw[0], X);
+  lo[1] = sk_cvt8_pair<T, true>(raw[0], X);
+  lo[2] = sk_cvt8_pair<T, false>(raw[1], X);
+  lo[3] = sk_cvt8_pair<T, true>(raw[1], X);
+  hi[0] = sk_cvt8_pair<T, false>(raw[2], X);
+  hi[1] = sk_cvt8_pair<T, true>(raw[2], X);
+  hi[2] = sk_cvt8_pair<T, false>(raw[3], X);
+  hi[3] = sk_cvt8_pair<T, true>(raw[3], X);
 }
 
 // (sum, sum of squares) of the 16 bytes of one activation fragment, accumulated per lane
@@ -263,6 +297,15 @@ template <> __device__ __forceinline__ void sk_stats<float>(const u32x4_t& v, fl
 // A weight lane needs the scales of ITS two 32-value blocks (16-byte half h of lane groups 2u, 2u+1, u = kq / 2); the scale array
 // holds block t = 2h + u in lane group t (where the scaled MFMA reads it), so the lane fetches groups u and 2 + u: two byte loads
 // per step instead of one, no exchange.  Several groups of 16 streams (CG > 1) are available in this mode only.
+// A16 with T = float16 (TW_F16_W8A16): the same fragments, scales, request order and reduction order, contracted on
+// v_mfma_f32_16x16x32_f16 against float16 activations.  Unlike bf16, float16 cannot hold every value x 2^k.  Of the two ways out,
+// this kernel takes the per-lane scaled convert (sk_widen8<f16_t>: the lane's own two block scales go into v_cvt_scalef32_pk_f16_fp8)
+// and not the exact unscaled widening with one float32 scale per partial accumulator: a 32-k MFMA contracts lane groups of TWO
+// blocks (u = 0 and 1), so the latter needs twice the matrix instructions with half of each A operand zeroed, four accumulators per
+// group of streams (16 more registers per group in a kernel that runs two workgroups per CU at 64 streams) and the scales of the
+// four OUTPUT rows of a lane instead of its own weight row - all on the critical path of a latency-bound launch, to recover
+// products that are exact anyway for every block whose largest weight is >= 2^-8 and wrong by at most 2^-25 per weight otherwise
+// (the rule is stated at sk_widen8<f16_t>; Whisper's decoder blocks have maxima of 2^-6 .. 2^-2).
 //
 // ONE reduction order for every number of rows (round 6).  A stream's result must not depend on who else is in the launch - the
 // serving hub mixes sessions freely, and the draft-and-verify prefill (api.hip: verify_core) is only exact if a position computed in a
@@ -282,7 +325,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
   // delivers the leading kernel-argument dwords in SGPRs with the wave (kernarg preload, build.py: -amdgpu-kernarg-preload-count),
   // so the activation and weight requests leave without waiting for a scalar load; everything else (epilogue operands, outputs)
   // stays in the GemvArgs block behind them - a struct is never preloaded - and arrives while those requests are in flight.
-  static_assert(!W8 || ElemTraits<T>::kCode == 1, "MXFP8 weights go with bf16 activations");
+  static_assert(!W8 || ElemTraits<T>::kCode == 1 || (A16 && ElemTraits<T>::kCode == 2), "MXFP8 weights go with bf16 activations (W8A16: bf16 or float16)");
   static_assert(TR == 16 || (!MULTI && EPI != SK_KV && EPI != SK_KV_RAG && EPI != SK_F32), "narrow tiles: plain / residual / GELU projections only");
   static_assert(!W8 || TR == 16 || TR == 8, "MXFP8 weights: 16- or 8-row tiles");
   static_assert(!A16 || W8, "A16 is a flavour of the MXFP8-weight kernel");
@@ -539,8 +582,8 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
         if constexpr (A16) {
           // fragments m = 0, 1 live in the first 16 bytes (block h = 0), m = 2, 3 in the second (h = 1)
           u32x4_t wf[4];
-          sk_widen8(on ? wq[2 * i] : zero, __builtin_bit_cast(float, (unsigned)(wsc[i] & 0xff) << 23), wf[0], wf[1]);
-          sk_widen8(on ? wq[2 * i + 1] : zero, __builtin_bit_cast(float, (unsigned)(wsc2[i] & 0xff) << 23), wf[2], wf[3]);
+          sk_widen8<T>(on ? wq[2 * i] : zero, __builtin_bit_cast(float, (unsigned)(wsc[i] & 0xff) << 23), wf[0], wf[1]);
+          sk_widen8<T>(on ? wq[2 * i + 1] : zero, __builtin_bit_cast(float, (unsigned)(wsc2[i] & 0xff) << 23), wf[2], wf[3]);
           if (SPLIT2 && second) {   // (a branch around matrix instructions only: no load inside)
 #pragma unroll
             for (int g = 0; g < (SPLIT2 ? CG : 1); ++g)
@@ -568,7 +611,7 @@ void skinny_mfma_kernel(const void* x_arg, const void* w_arg, int k_arg, int b_a
               if (LN && (!MULTI || grp == 0)) sk_stats<T>(xv[m], ps[g], pss[g]);
             }
             int xs;
-            const v8i_t xb = sk_quant_mx8(xv, xs);
+            const v8i_t xb = sk_quant_mx8<bf16_t>(xv, xs);
             acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wb, xb, acc[g], 0, 0, 0, wsc[i], 0, xs);
           }
         } else {
@@ -768,7 +811,9 @@ __global__ __launch_bounds__(256) void tile_weights_kernel(const T* __restrict__
 // W[row][(4s + m)*32 + kq*8 + e]: the same k set the activation lane (stream, kq) holds) followed, in a separate array, by
 // one scale byte per lane (already placed in the lane the MFMA reads it from).  Quantisation = sk_quant_mx8, i.e. identical
 // to what the projection kernel does to the activations.
-__global__ __launch_bounds__(256) void quant_mx8_kernel(const bf16_t* __restrict__ src, unsigned char* __restrict__ dst,
+// T = float16: the packer of TW_F16_W8A16 contexts, same storage.
+template <typename T>
+__global__ __launch_bounds__(256) void quant_mx8_kernel(const T* __restrict__ src, unsigned char* __restrict__ dst,
                                                         unsigned char* __restrict__ scales, int N, int K, int TR) {
   const int S = K / 128;
   const long long v = (long long)blockIdx.x * 256 + threadIdx.x;  // (16-row tile, step, lane): quantisation always works on
@@ -786,7 +831,7 @@ __global__ __launch_bounds__(256) void quant_mx8_kernel(const bf16_t* __restrict
     if (n < N) xv[m] = *reinterpret_cast<const u32x4_t*>(src + (long long)n * K + (4 * s + m) * 32 + kq * 8);
   }
   int sb;  // (whole wavefronts reach this point: `total` is a multiple of 64)
-  const v8i_t q = sk_quant_mx8(xv, sb);
+  const v8i_t q = sk_quant_mx8<T>(xv, sb);
   // storage: tiles of TR rows (16, or 8 for the narrow projections): [tile][step][half][kq * TR + row % TR][16 B]
   const int fr = l & 15;
   const long long tile = t * (16 / TR) + fr / TR;
@@ -1038,29 +1083,29 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
 // that instruction, lane = key; the V scale multiplies the probability of its key before the P.V operand is packed), so q and
 // the probabilities are NOT quantised.  A 16-B fp8 vector holds 16 dims (K) / 16 keys (V^T), i.e. two bf16 MFMA operands:
 // the contraction index of an MFMA is order-free, so the q / probability operands are simply gathered in the same order.
-__device__ __forceinline__ void kv8_widen(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
-  lo[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[0], X, false));
-  lo[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[0], X, true));
-  lo[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[1], X, false));
-  lo[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[1], X, true));
-  hi[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[2], X, false));
-  hi[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[2], X, true));
-  hi[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[3], X, false));
-  hi[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)raw[3], X, true));
+//
+// T = float16 (TW_F16_W8A16 contexts): float16 queries, MFMAs and outputs, the fragments widened by v_cvt_scalef32_pk_f16_fp8
+// (sk_widen8<f16_t>: RNE to float16 with gradual underflow; exact for every key whose largest |K| is >= 2^-8 - the epilogue clamps to 63488, so no image
+// exceeds the float16 range - and always exact for V^T, which is widened unscaled).  The P.V operand differs: probability x V scale can be far below the float16 normal range
+// (p = 1e-3 against values around 1 is 2^-17), so it is carried times 2^7 - sb - 127 <= 8 for float16 data, hence the operand
+// stays <= 2^15 - and the result takes the 2^-7 back in float32 (kPvUp below).  With values around 1 the operand is then the
+// plain probability, the operand of the TW_F16 kernel.
+template <typename T> __device__ __forceinline__ void kv8_widen(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
+  sk_widen8<T>(raw, X, lo, hi);
 }
 
 // G = 64-key groups per wavefront (1, 2 or 3: up to 512 / 1024 / 1536 keys with 8 wavefronts, i.e. every chunk length up to
 // 30 s).  At 32 registers per group and operand the whole head fits the register file, so - unlike the bf16 kernel, which
 // falls back to two dependent passes above 512 keys - EVERY fragment of the head is requested before anything is waited for:
 // one memory round trip per head whatever the chunk length.
-template <int NW, int G, bool FQ = false>
-__device__ __forceinline__ float attn_mfma_block_kv8(const bf16_t* __restrict__ q, const unsigned char* __restrict__ kf8,
+template <typename T, int NW, int G, bool FQ = false>
+__device__ __forceinline__ float attn_mfma_block_kv8(const T* __restrict__ q, const unsigned char* __restrict__ kf8,
                                                      const unsigned char* __restrict__ vtf8, const unsigned char* __restrict__ ksc,
                                                      const unsigned char* __restrict__ vsc, int n_keys, int n_bound, float* sc,
-                                                     float* scv, float* red, bf16_t* __restrict__ out_base, int out_j, int out_k0,
+                                                     float* scv, float* red, T* __restrict__ out_base, int out_j, int out_k0,
                                                      const FusedQ& fq = FusedQ{}, int fq_b = 0, int fq_h = 0,
-                                                     bf16_t* qst = nullptr) {
-  typedef bf16_t T;
+                                                     T* qst = nullptr) {
+  constexpr bool kPvUp = ElemTraits<T>::kCode == 2;   // float16: the P.V operand is carried times 2^7 (header)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, kq = lane >> 4;
@@ -1108,7 +1153,7 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const bf16_t* __restrict__ 
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       u32x4_t k0, k1;
-      kv8_widen(kraw[g][a], __builtin_bit_cast(float, ((ks4[g] >> (8 * a)) & 0xffu) << 23), k0, k1);
+      kv8_widen<T>(kraw[g][a], __builtin_bit_cast(float, ((ks4[g] >> (8 * a)) & 0xffu) << 23), k0, k1);
       f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
       acc = sk_mfma<T>(k0, qf[0], acc);
       acc = sk_mfma<T>(k1, qf[1], acc);
@@ -1140,12 +1185,12 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const bf16_t* __restrict__ 
     if (t0 < n_bound) {
       pr = (t0 < n_keys) ? expf(sc[t0] - M) : 0.f;
       sc[t0] = pr;                                                  // plain probability: alignment rows, normaliser
-      scv[t0] = pr * __builtin_bit_cast(float, vsb[g] << 23);       // probability x the key's V scale: the P.V operand
+      scv[t0] = pr * __builtin_bit_cast(float, (vsb[g] + (kPvUp ? 7u : 0u)) << 23);   // probability x the key's V scale: the P.V operand
     }
     ls += pr;
     u32x4_t v0[4], v1[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) kv8_widen(vraw[g][dt], 1.0f, v0[dt], v1[dt]);
+    for (int dt = 0; dt < 4; ++dt) kv8_widen<T>(vraw[g][dt], 1.0f, v0[dt], v1[dt]);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {   // operand j of lane (kq, .): keys kq*16 + j*8 .. +7 of this 64-key group
       float pv[8];
@@ -1178,7 +1223,8 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const bf16_t* __restrict__ 
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += wo[w * 64 + tid];
-    out_base[tw_xt_index<T>(out_j, out_k0 + tid)] = (T)(v * inv);
+    if constexpr (kPvUp) out_base[tw_xt_index<T>(out_j, out_k0 + tid)] = tw_cast<T>(v * inv * 0.0078125f);
+    else out_base[tw_xt_index<T>(out_j, out_k0 + tid)] = (T)(v * inv);
   }
   return inv;
 }
@@ -1420,23 +1466,23 @@ __global__ __launch_bounds__(512) void dec_cross_attn_rows_kernel(const T* __res
   }
 }
 
-template <int G, bool FQ>
+template <typename T, int G, bool FQ>
 __global__ __launch_bounds__(512) void dec_cross_attn_kv8_kernel(const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                   const unsigned char* __restrict__ ksc,
                                                                   const unsigned char* __restrict__ vsc, int H, int Tp, int Tlen,
-                                                                  int rows_streams, const bf16_t* __restrict__ q, bf16_t* __restrict__ out,
+                                                                  int rows_streams, const T* __restrict__ q, T* __restrict__ out,
                                                                   const int* __restrict__ align_slot, float* __restrict__ align,
                                                                   int Ha, int P, const DecState* __restrict__ stt, FusedQ fq) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* sc = reinterpret_cast<float*>(smem);  // [Tp] scores -> unnormalised probabilities
   float* scv = sc + Tp;                        // [Tp] probabilities x V scale
   __shared__ float red[2 * 8 + 8 * 64];
-  __shared__ __attribute__((aligned(16))) bf16_t qst[FQ ? 8 * 64 : 8];
+  __shared__ __attribute__((aligned(16))) T qst[FQ ? 8 * 64 : 8];
   asm volatile("" ::"s"(ck), "s"(cv), "s"(ksc), "s"(vsc), "s"(H), "s"(Tp), "s"(Tlen), "s"(rows_streams));
   const int h = blockIdx.x, b = blockIdx.y;
   const int srow = rows_streams > 0 ? b % rows_streams : b;   // rows mode (prefill), as in dec_cross_attn_kernel
   const long long hb = ((long long)srow * H + h) * Tp;
-  const float inv = attn_mfma_block_kv8<8, G, FQ>(q + ((long long)b * H + h) * 64, ck + hb * 64, cv + hb * 64, ksc + hb, vsc + hb,
+  const float inv = attn_mfma_block_kv8<T, 8, G, FQ>(q + ((long long)b * H + h) * 64, ck + hb * 64, cv + hb * 64, ksc + hb, vsc + hb,
                                                   Tlen, Tp, sc, scv, red, out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64,
                                                   fq, b, h, qst);
   const int slot = align_slot ? align_slot[h] : -1;
@@ -2915,13 +2961,24 @@ static hipError_t skinny_launch_nw(const GemvArgs& a0, hipStream_t st, bool spli
   }
 }
 
+// one group of streams: W8A8 (bf16 only) or W8A16
+template <typename T, int NW, int S, bool MU, int TR>
+static hipError_t sk_w8_one(const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  if constexpr (ElemTraits<T>::kCode == 1) {
+    if (!a.a16) return sk_go<T, NW, S, MU, true, 1, TR>(a, grid, lds, st);
+  }
+  return sk_go<T, NW, S, MU, true, 1, TR, true>(a, grid, lds, st);
+}
+
 // MXFP8 weights: 128-k steps; 2 steps per wavefront cover K = 1280 with 8 wavefronts, 3 cover K = 5120 with 16.  a.a16: W8A16
 // (weights widened in registers, bf16 activations) - the only flavour with several groups of 16 streams (2 steps = 8 activation
 // fragments per group in flight, further rounds for longer K)
-template <int NW, int TR>
+// T = float16: W8A16 only (TW_F16_W8A16); the launch geometry does not depend on T.
+template <typename T, int NW, int TR>
 static hipError_t skinny_launch_w8(const GemvArgs& a0, hipStream_t st, bool split2 = false) {
   GemvArgs a = a0;
   if (a.K % 128 != 0 || a.B > 64) return hipErrorInvalidValue;
+  if (ElemTraits<T>::kCode != 1 && !a.a16) return hipErrorInvalidValue;
   const size_t lds = (size_t)NW * kRedTile * 4;
   const int tiles = (a.N + TR - 1) / TR;
   const int steps_per_wave = (a.K / 128 + NW - 1) / NW;
@@ -2942,8 +2999,8 @@ static hipError_t skinny_launch_w8(const GemvArgs& a0, hipStream_t st, bool spli
       return hipErrorInvalidValue;
     } else {
       if (!groups || a.rg != 1) return hipErrorInvalidValue;
-      return a.B <= 32 ? sk_go<bf16_t, NW, 2, false, true, 2, TR, true, 0, true>(a, grid, lds, st)
-                       : sk_go<bf16_t, NW, 2, false, true, 4, TR, true, 0, true>(a, grid, lds, st);
+      return a.B <= 32 ? sk_go<T, NW, 2, false, true, 2, TR, true, 0, true>(a, grid, lds, st)
+                       : sk_go<T, NW, 2, false, true, 4, TR, true, 0, true>(a, grid, lds, st);
     }
   }
   if (groups) {
@@ -2951,12 +3008,12 @@ static hipError_t skinny_launch_w8(const GemvArgs& a0, hipStream_t st, bool spli
       return hipErrorInvalidValue;
     } else {
       if constexpr (TR == 16) {
-        if (a.rg > 1) return a.B <= 32 ? sk_go<bf16_t, NW, 2, true, true, 2, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, 2, true, true, 4, TR, true>(a, grid, lds, st);
+        if (a.rg > 1) return a.B <= 32 ? sk_go<T, NW, 2, true, true, 2, TR, true>(a, grid, lds, st) : sk_go<T, NW, 2, true, true, 4, TR, true>(a, grid, lds, st);
       }
-      return a.B <= 32 ? sk_go<bf16_t, NW, 2, false, true, 2, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, 2, false, true, 4, TR, true>(a, grid, lds, st);
+      return a.B <= 32 ? sk_go<T, NW, 2, false, true, 2, TR, true>(a, grid, lds, st) : sk_go<T, NW, 2, false, true, 4, TR, true>(a, grid, lds, st);
     }
   }
-#define SK_W8(S, MU) (a.a16 ? sk_go<bf16_t, NW, S, MU, true, 1, TR, true>(a, grid, lds, st) : sk_go<bf16_t, NW, S, MU, true, 1, TR>(a, grid, lds, st))
+#define SK_W8(S, MU) sk_w8_one<T, NW, S, MU, TR>(a, grid, lds, st)
   if constexpr (TR == 16) {
     if (a.rg > 1) return steps_per_wave <= 2 ? SK_W8(2, true) : SK_W8(3, true);
   }
@@ -2973,9 +3030,12 @@ static hipError_t skinny_launch(const GemvArgs& a, hipStream_t st) {
   if (a.tr != 0 && a.tr != 8 && a.tr != 16) return hipErrorInvalidValue;
   if (a.tr != 8 && longk) return hipErrorInvalidValue;
   if (a.wscale) {
-    if (ElemTraits<T>::kCode != 1) return hipErrorInvalidValue;
-    if (a.tr == 8) return big ? skinny_launch_w8<16, 8>(a, st) : skinny_launch_w8<8, 8>(a, st, split2);
-    return skinny_launch_w8<8, 16>(a, st);
+    if constexpr (ElemTraits<T>::kCode == 0) {
+      return hipErrorInvalidValue;
+    } else {
+      if (a.tr == 8) return big ? skinny_launch_w8<T, 16, 8>(a, st) : skinny_launch_w8<T, 8, 8>(a, st, split2);
+      return skinny_launch_w8<T, 8, 16>(a, st);
+    }
   }
   if (a.tr == 8) return big ? skinny_launch_nw<T, 16, 8>(a, st) : skinny_launch_nw<T, 8, 8>(a, st, split2);
   return skinny_launch_nw<T, 8, 16>(a, st);
@@ -3046,15 +3106,16 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
   } else if (!q) {
     return hipErrorInvalidValue;
   }
-  if (ksc || vsc) {  // fp8 K / V^T caches with per-key scales (TW_BF16_MXFP8 contexts)
-    if (!ksc || !vsc || dtype != 1) return hipErrorInvalidValue;
+  if (ksc || vsc) {  // fp8 K / V^T caches with per-key scales (MXFP8 contexts: bf16 or - TW_F16_W8A16 - float16 activations)
+    if (!ksc || !vsc || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
     const size_t lds8 = (size_t)Tp * sizeof(float) * 2;
-#define CA8_GO(GV, FV) hipLaunchKernelGGL((dec_cross_attn_kv8_kernel<GV, FV>), dim3(H, B), dim3(512), lds8, st,                        \
-                                          (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, (const bf16_t*)q,  \
-                                          (bf16_t*)out, align_slot_for_head, align, Ha, P, stt, fq)
-#define CA8_PICK(FV) do { if (Tp <= 512) CA8_GO(1, FV); else if (Tp <= 1024) CA8_GO(2, FV); else if (Tp <= 1536) CA8_GO(3, FV);      \
-                          else return hipErrorInvalidValue; } while (0)
-    if (f) CA8_PICK(true); else CA8_PICK(false);
+#define CA8_GO(TT, GV, FV) hipLaunchKernelGGL((dec_cross_attn_kv8_kernel<TT, GV, FV>), dim3(H, B), dim3(512), lds8, st,                \
+                                          (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, (const TT*)q,  \
+                                          (TT*)out, align_slot_for_head, align, Ha, P, stt, fq)
+#define CA8_PICK(TT, FV) do { if (Tp <= 512) CA8_GO(TT, 1, FV); else if (Tp <= 1024) CA8_GO(TT, 2, FV); else if (Tp <= 1536) CA8_GO(TT, 3, FV); \
+                              else return hipErrorInvalidValue; } while (0)
+    if (dtype == 1) { if (f) CA8_PICK(bf16_t, true); else CA8_PICK(bf16_t, false); }
+    else { if (f) CA8_PICK(f16_t, true); else CA8_PICK(f16_t, false); }
 #undef CA8_PICK
 #undef CA8_GO
     return hipGetLastError();
@@ -3264,11 +3325,14 @@ hipError_t launch_tile_weights(int dtype, const void* src, void* dst, int N, int
   return hipGetLastError();
 }
 
-hipError_t launch_quant_mx8(const void* src_bf16, void* dst_fp8, void* dst_scales, int N, int K, int tr, hipStream_t st) {
-  if (K % 128 != 0 || (tr != 16 && tr != 8) || (tr == 8 && N % 16 != 0)) return hipErrorInvalidValue;
+hipError_t launch_quant_mx8(int dtype, const void* src, void* dst_fp8, void* dst_scales, int N, int K, int tr, hipStream_t st) {
+  if ((dtype != 1 && dtype != 2) || K % 128 != 0 || (tr != 16 && tr != 8) || (tr == 8 && N % 16 != 0)) return hipErrorInvalidValue;
   const long long total = (long long)((N + 15) / 16) * (K / 128) * 64;
-  hipLaunchKernelGGL(quant_mx8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)src_bf16,
-                     (unsigned char*)dst_fp8, (unsigned char*)dst_scales, N, K, tr);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (dtype == 1)
+    hipLaunchKernelGGL(quant_mx8_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)src, (unsigned char*)dst_fp8, (unsigned char*)dst_scales, N, K, tr);
+  else
+    hipLaunchKernelGGL(quant_mx8_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)src, (unsigned char*)dst_fp8, (unsigned char*)dst_scales, N, K, tr);
   return hipGetLastError();
 }
 

@@ -492,12 +492,18 @@ __device__ __forceinline__ void gemm_epilogue_staged_vt(const f32x4_t (&acc)[NT]
 // V, so the per-key maximum over the head is 16 in-lane values and two lane swaps; every key gets one power-of-two scale
 // byte (sb = max(E - 7, 1), E = biased exponent of the maximum: the rule of sk_quant_mx8 in k_decode.hip) and its 64 values
 // are stored as e4m3(bf16(v) / 2^(sb-127)) in the fp8 fragment layouts of tw_common.h.
+// float16 contexts (TW_F16_W8A16): the accumulator is rounded to float16 first (saturating at 65504, as every float16 store), E is
+// the float32 exponent of the largest float16 magnitude, and the elements go through the float32 convert (float16 -> float32 is
+// exact) after a clamp to +-63488 = 248 x 2^8, the largest magnitude whose e4m3 image float16 holds (k_decode.hip: sk_quant_mx8):
+// e4m3(clamp(f16(v)) / 2^(sb-127)).  Same layouts, same scale bytes.
 typedef short tw_s16x2 __attribute__((ext_vector_type(2)));
 template <typename T, int NT, int MT>
 __device__ __forceinline__ void gemm_epilogue_kv8(const f32x4_t (&acc)[NT][MT], int m_base, int n_base, int M, int N,
                                                   const GemmEpilogue& ep, int fr, int fq) {
   static_assert(NT == 4, "one 64-column head per wavefront");
-  if constexpr (ElemTraits<T>::kCode == 1) {   // fp8 cross K / V caches exist in bf16 contexts only
+  if constexpr (ElemTraits<T>::kCode != 0) {   // fp8 cross K / V caches exist in 16-bit contexts only
+    constexpr bool F16 = ElemTraits<T>::kCode == 2;
+    typedef typename Pair16<T>::x2 x2_t;
     const T* bias = reinterpret_cast<const T*>(ep.bias);
     const int dmodel = ep.H * 64;
     if (n_base >= N) return;
@@ -516,12 +522,12 @@ __device__ __forceinline__ void gemm_epilogue_kv8(const f32x4_t (&acc)[NT][MT], 
       const int m = m_base + b * 16 + fr;
       const int mc = min(m, M - 1);
       const int bidx = mc / ep.T, t = mc % ep.T;
-      bf16x2_t pk[NT][2];
+      x2_t pk[NT][2];
       unsigned amax = 0;
 #pragma unroll
       for (int a = 0; a < NT; ++a) {
-        pk[a][0] = bf16x2_t{(bf16_t)(acc[a][b][0] + bv[a][0]), (bf16_t)(acc[a][b][1] + bv[a][1])};
-        pk[a][1] = bf16x2_t{(bf16_t)(acc[a][b][2] + bv[a][2]), (bf16_t)(acc[a][b][3] + bv[a][3])};
+        pk[a][0] = x2_t{tw_cast<T>(acc[a][b][0] + bv[a][0]), tw_cast<T>(acc[a][b][1] + bv[a][1])};
+        pk[a][1] = x2_t{tw_cast<T>(acc[a][b][2] + bv[a][2]), tw_cast<T>(acc[a][b][3] + bv[a][3])};
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const unsigned u = __builtin_bit_cast(unsigned, pk[a][j]) & 0x7fff7fffu;
@@ -529,10 +535,11 @@ __device__ __forceinline__ void gemm_epilogue_kv8(const f32x4_t (&acc)[NT][MT], 
         }
       }
       // the 64 columns of row m live in the 4 lanes fr, fr+16, fr+32, fr+48
-      float am = __builtin_bit_cast(float, amax << 16);   // the bf16 pattern as the float32 it denotes (a normal number)
+      float am;
+      if constexpr (F16) am = (float)__builtin_bit_cast(f16_t, (unsigned short)amax);   // magnitudes order like their bit patterns
+      else am = __builtin_bit_cast(float, amax << 16);   // the bf16 pattern as the float32 it denotes (a normal number)
       am = tw_xor32_max(tw_xor16_max(am));
-      amax = __builtin_bit_cast(unsigned, am) >> 16;
-      const int sb = max((int)(amax >> 7) - 7, 1);
+      const int sb = max((int)(__builtin_bit_cast(unsigned, am) >> 23) - 7, 1);
       const float X = __builtin_bit_cast(float, (unsigned)sb << 23);
       if (m < M) {
         const long long hb = (long long)(bidx * ep.H + h) * ep.Tp;       // (stream, head) slab: Tp*64 bytes, Tp scale bytes
@@ -540,8 +547,14 @@ __device__ __forceinline__ void gemm_epilogue_kv8(const f32x4_t (&acc)[NT][MT], 
 #pragma unroll
         for (int a = 0; a < NT; ++a) {
           tw_s16x2 q = {0, 0};
-          q = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(q, pk[a][0], X, false);
-          q = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(q, pk[a][1], X, true);
+          if constexpr (F16) {
+            auto c = [](f16_t v) { return __builtin_amdgcn_fmed3f((float)v, -63488.f, 63488.f); };
+            q = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(q, c(pk[a][0][0]), c(pk[a][0][1]), X, false);
+            q = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(q, c(pk[a][1][0]), c(pk[a][1][1]), X, true);
+          } else {
+            q = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(q, pk[a][0], X, false);
+            q = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(q, pk[a][1], X, true);
+          }
           const unsigned w = __builtin_bit_cast(unsigned, q);
           const int c = a * 16 + fq * 4;
           if (seg == 0) {
@@ -922,7 +935,7 @@ static hipError_t gemm_dispatch(const void* A, RowMap amap, const void* W, int M
   // Tile choice:
   //   kernel 2: BM x 256 (BM = 80 ... 128), 4 wavefronts side by side, weights straight to registers, 3-stage activation ring - large M
   //   kernel 1: 128 x 64 (3 stages) or 64 x 64 (4 stages), both operands through an LDS ring - small M (one to three streams)
-  if (ep.mode == EPI_KV_CROSS8 && (ElemTraits<T>::kCode != 1 || N % 64 != 0)) return hipErrorInvalidValue;   // bf16 contexts only
+  if (ep.mode == EPI_KV_CROSS8 && (ElemTraits<T>::kCode == 0 || N % 64 != 0)) return hipErrorInvalidValue;   // 16-bit contexts only
   const GemmPlan plan = gemm_plan(ep.mode, M, N);
   if (plan.kernel == 2) {
     switch (plan.bm) {

@@ -312,7 +312,7 @@ hipError_t launch_gemv(int dtype, const GemvArgs& a, hipStream_t st);
 // row-major [N][K] -> the fragment-major layout launch_gemv reads (k_decode.hip); dst holds ceil(N/16)*16 rows
 hipError_t launch_tile_weights(int dtype, const void* src, void* dst, int N, int K, int tr, hipStream_t st);
 // row-major bf16 [N][K] -> MXFP8 fragments (ceil(N/16)*16*K bytes) + block scales (ceil(N/16)*16*K/32 bytes); K % 128 == 0
-hipError_t launch_quant_mx8(const void* src_bf16, void* dst_fp8, void* dst_scales, int N, int K, int tr, hipStream_t st);   // tr: 16 or 8 rows per tile
+hipError_t launch_quant_mx8(int dtype, const void* src, void* dst_fp8, void* dst_scales, int N, int K, int tr, hipStream_t st);   // src: bf16 (1) or float16 (2); tr: 16 or 8 rows per tile
 // weight preparation for the folded pre-LayerNorm: W <- Wsrc * g (may alias), gw, cb as above
 hipError_t launch_fold_ln(int dtype, void* W, const void* Wsrc, const void* g, const void* beta, const void* bias, float* gw,
                           float* cb, int N, int K, hipStream_t st);  // once per process: dynamic-LDS caps of the gemv instantiations
@@ -326,7 +326,7 @@ hipError_t launch_dec_self_attn_ragged(int dtype, const void* q, const void* kc,
                                        int key_bound, const DecState* stt, const int* n_pad, hipStream_t st);
 // cross attention over cached encoder K/V: ck/cv per (stream, head) Tp keys fragment-major; out fragment-major; align rows:
 // for head h with align_slot[h] >= 0 write the softmax row to align[((b*Ha + slot)*P + pos)*T + t]
-// ksc / vsc non-null: ck / cv are the fp8 caches above (bf16 contexts only), these their per-key scale bytes [B][H][Tp]
+// ksc / vsc non-null: ck / cv are the fp8 caches above (bf16 and float16 contexts), these their per-key scale bytes [B][H][Tp]
 // Query operand: either q [B,d] row-major (T), or - fq.u non-null - the un-normalised pre-activation u of the folded
 // LayerNorm'd query projection: q = rstd (u - mean gw) + cb with the statistics of x's row taken inside the launch.
 struct FusedQ {

@@ -263,10 +263,11 @@ class WhisperEngine:
             dtype = FP8_DEFAULT
         self.dtype_name = dtype
         # "f16" = float16 context (round 4): the reference's streaming default dtype; same kernels instantiated for _Float16
+        # "fp8f16" = "fp8a16" on a float16 base (TW_F16_W8A16): float16 activations, encoder and caches, the same fp8 bytes
         self.tw_dtype = {"bf16": _cabi.TW_BF16, "f16": _cabi.TW_F16, "f32": _cabi.TW_F32, "fp8a8": _cabi.TW_BF16_MXFP8,
-                         "fp8a16": _cabi.TW_BF16_W8A16}[dtype]
+                         "fp8a16": _cabi.TW_BF16_W8A16, "fp8f16": _cabi.TW_F16_W8A16}[dtype]
         self.torch_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "fp8a8": torch.bfloat16,
-                            "fp8a16": torch.bfloat16}[dtype]
+                            "fp8a16": torch.bfloat16, "fp8f16": torch.float16}[dtype]
         self.alignment_heads = [tuple(map(int, x)) for x in (alignment_heads or [])]
         cfg = _cabi.tw_config()
         cfg.d_model = dims["d_model"]

@@ -358,7 +358,9 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
         if decoder_weights == "fp8":
             if eng_dtype == "f32":
                 raise ValueError("decoder_weights='fp8' needs a bf16 (or fp16) torch_dtype")
-            eng_dtype = "fp8"
+            # a float16 request keeps its float16 activations, encoder and caches (TW_F16_W8A16); bf16 - and float16 under
+            # THEWHISPER_FP16_AS_BF16=1 - the bf16-based flavour
+            eng_dtype = "fp8f16" if eng_dtype == "f16" else "fp8"
         heads = getattr(self.generation_config, "alignment_heads", None) or []
         factory = engine_factory or type(self)._engine_factory
         dev_index = p0.device.index if p0.device.type == "cuda" and p0.device.index is not None else 0

@@ -574,6 +574,14 @@ int tw_last_draft(tw_ctx* ctx, int32_t* offered, int32_t* accepted, int32_t* lau
  * the rows launches of a draft are tw_last_draft's.  Any pointer may be NULL. */
 int tw_last_prompt_rows(tw_ctx* ctx, int32_t* launches, int32_t* positions);
 
+/* The x, y, z workgroup counts of the context's most recent decoder cross-attention launch (the last layer's; recorded on the host, nothing
+ * is read from the device; all 0 before the first launch).  A one-position step - a replayed step graph included - and a rows launch
+ * with one position per stream read (heads, rows, 1): one workgroup per head and row.  A rows launch with several positions per stream
+ * (batched prefill, prompt as rows, a verify launch, tw_score_tokens) reads (heads, streams, ceil(positions / 16)) in every dtype, the
+ * fp8 contexts included: one pass over a stream's K / V^T serves up to 16 of its positions.  A generate call ends with one-position
+ * steps, so the rows form is read behind a call that ends with a rows launch, such as tw_score_tokens. */
+int tw_last_cross_grid(tw_ctx* ctx, int32_t* grid3);
+
 /* Token log-probabilities and the no-speech probability of FINISHED sequences, by a teacher-forced re-scoring pass.  Replaces: the
  * `scores` HF's generate keeps per step and WhisperGenerationMixin._retrieve_avg_logprobs reduces
  * (HF:models/whisper/generation_whisper.py:1957-1974: log_softmax of the PROCESSED scores, gathered at the chosen tokens, summed and divided

@@ -145,6 +145,7 @@ struct tw_ctx {
   // such call with want_alignment
   int* beam_anc = nullptr;
   int last_draft[4] = {0, 0, 0, 0};   // of the last greedy call: tokens offered, accepted, verify launches, verify rounds
+  int last_cross_grid[3] = {0, 0, 0};   // workgroup counts of the most recent decoder cross-attention launch (decode_core; a graph replay: what its capture recorded)
   int last_prompt_rows[2] = {0, 0};   // of the last call of the generate family: rows launches its prompt took, positions they consumed
   size_t row_ids_cap = 0;
   // tw_score_tokens: its own token table, processor tables, slice partials and results, so that nothing a later tw_generate_greedy
@@ -172,6 +173,7 @@ struct tw_ctx {
   // one captured step per 64-key bucket of the self-attention length (the step at position s only has to read keys
   // [0, roundup(s + 1, 64)), and the host knows s): fewer bytes per step than one graph sized for the longest sequence
   std::map<std::string, hipGraphExec_t> step_graphs;
+  int step_graph_grid[3] = {0, 0, 0};   // last_cross_grid as decode_core recorded it while a step graph of the current key was captured
   std::string step_graph_key;
 
   // timing
@@ -1104,7 +1106,7 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, const DecodeOpts& o = DecodeOp
                                     c->datt, B, H, T, c->Tp, (c->Ha > 0 && o.record_alignment) ? c->align_slot + (size_t)l * H : nullptr, c->align,
                                     o.record_alignment ? c->Ha : 0,
                                     P, c->stt, c->w8 ? c->cross_ksc + (size_t)c->Bmax * H * c->Tp * l : nullptr,
-                                    c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, st));
+                                    c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, st, c->last_cross_grid));
     {
       GemvArgs a{};
       a.x = c->datt; a.ldx = d; a.W = L.wo_c; a.wscale = L.s_oc; a.a16 = c->a16; a.tr = L.tr_oc; a.bias = L.bo_c; a.N = d; a.K = d; a.B = B; a.res = xmid; a.ldres = d;
@@ -1653,6 +1655,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
     (void)hipGraphDestroy(g);
     if (ei != hipSuccess) return fail(c, TW_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ei));
     c->step_graphs[k] = ex;
+    std::copy(c->last_cross_grid, c->last_cross_grid + 3, c->step_graph_grid);   // every graph of one key holds the same step launches
     *out = ex;
     return TW_OK;
   };
@@ -1707,6 +1710,7 @@ static int generate_loop(tw_ctx* c, int32_t B, const int32_t* prompt, int32_t n_
       int r = graph_for(kb, n, &ex);
       if (r != TW_OK) return r;
       HIPCHK(c, hipGraphLaunch(ex, st));
+      std::copy(c->step_graph_grid, c->step_graph_grid + 3, c->last_cross_grid);   // what the launcher handed back at capture time
     } else {
       c->dec_key_bound = kb;
       int r = decode_core(c, B, st, step);
@@ -2134,6 +2138,12 @@ int tw_last_prompt_rows(tw_ctx* c, int32_t* launches, int32_t* positions) {
   if (!c) return TW_EINVAL;
   if (launches) *launches = c->last_prompt_rows[0];
   if (positions) *positions = c->last_prompt_rows[1];
+  return TW_OK;
+}
+
+int tw_last_cross_grid(tw_ctx* c, int32_t* grid3) {
+  if (!c || !grid3) return TW_EINVAL;
+  for (int i = 0; i < 3; ++i) grid3[i] = c->last_cross_grid[i];
   return TW_OK;
 }
 

@@ -14,6 +14,7 @@
 //  * sampler: Whisper's logits processors + first-index argmax on the fp32 logits, one workgroup
 //    per stream (HF:generation/logits_process.py:1816-2047, HF:generation/utils.py:2925).
 #include "tw_common.h"
+#include "k_decode_attn.h"   // pack16, sk_mfma, sk_widen8, QRaw / fq_request / fq_finish
 
 namespace {
 
@@ -46,23 +47,6 @@ __device__ __forceinline__ float gelu_exact(float x) {
 // inside an unrolled loop to element 0 for every i (seen in the ISA: identical instructions), so pairs are always taken
 // with named __builtin_shufflevector selections of the whole bf16x8 vector.
 
-template <typename T> __device__ __forceinline__ u32x4_t pack16(const float* in);
-template <> __device__ __forceinline__ u32x4_t pack16<float>(const float* in) {
-  return __builtin_bit_cast(u32x4_t, f32x4_t{in[0], in[1], in[2], in[3]});
-}
-template <> __device__ __forceinline__ u32x4_t pack16<bf16_t>(const float* in) {
-  bf16x8_t f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = (bf16_t)in[i];
-  return __builtin_bit_cast(u32x4_t, f);
-}
-template <> __device__ __forceinline__ u32x4_t pack16<f16_t>(const float* in) {   // probabilities: in range, no saturation needed
-  f16x8_t f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = (f16_t)in[i];
-  return __builtin_bit_cast(u32x4_t, f);
-}
-
 // Folded pre-LayerNorm.  For y = LN(x) . W^T + bias with LN(x) = (x - mean) * rstd * g + beta:
 //     y[n] = rstd * ( x . W'[n]  -  mean * gW[n] )  +  cb[n],
 //     W'[n,k] = g[k] W[n,k],   gW[n] = sum_k g[k] W[n,k],   cb[n] = sum_k beta[k] W[n,k] + bias[n]
@@ -85,26 +69,6 @@ template <> __device__ __forceinline__ u32x4_t pack16<f16_t>(const float* in) { 
 // accumulators at the one barrier the partial-tile reduction needs anyway.
 // Deterministic: fixed summation order, no atomics.
 // ---------------------------------------------------------------------------------------------
-
-template <typename T>
-__device__ __forceinline__ f32x4_t sk_mfma(const u32x4_t& w, const u32x4_t& x, f32x4_t acc);
-template <>
-__device__ __forceinline__ f32x4_t sk_mfma<bf16_t>(const u32x4_t& w, const u32x4_t& x, f32x4_t acc) {
-  return tw_mfma32<bf16_t>(w, x, acc);
-}
-template <>
-__device__ __forceinline__ f32x4_t sk_mfma<f16_t>(const u32x4_t& w, const u32x4_t& x, f32x4_t acc) {
-  return tw_mfma32<f16_t>(w, x, acc);
-}
-template <>
-__device__ __forceinline__ f32x4_t sk_mfma<float>(const u32x4_t& w, const u32x4_t& x, f32x4_t acc) {
-  const f32x4_t a = __builtin_bit_cast(f32x4_t, w), b = __builtin_bit_cast(f32x4_t, x);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], acc, 0, 0, 0);
-  return acc;
-}
 
 // Epilogue flavours (compile-time: a runtime-uniform branch around a load makes hipcc wait for EVERY outstanding load at
 // the join, which serialises the whole prologue - see the ordering note below).
@@ -198,30 +162,6 @@ __device__ __forceinline__ v8i_t sk_quant_mx8(const u32x4_t (&xv)[4], int& scale
   const unsigned pick = (kq == 0) ? (mine & 0xffu) : (kq == 3) ? (mine >> 8) : (kq == 1) ? (far & 0xffu) : (far >> 8);
   scale_operand = (int)(pick & 0xffu);
   return out;
-}
-
-// 16 e4m3 bytes -> two MFMA operands of T (bytes 0..7, 8..15), each value multiplied by X = 2^(scale byte - 127); one byte pair per
-// v_cvt_scalef32_pk_bf16_fp8 / v_cvt_scalef32_pk_f16_fp8.  bf16: exact (3 mantissa bits times a power of two).
-// float16 (TW_F16_W8A16): the convert returns RNE_f16(value x X) with gradual underflow and +-inf above the float16 range (all 256
-// bytes x 254 scale bytes against the float32 widening followed by a float16 cast: profiles/r24_f16cvt_probe.txt, tools/dbg/
-// f16cvt_probe.hip), so the weight a row sees is the pure function  w(byte, sb) = RNE_f16(e4m3(byte) x 2^(sb-127))  of the stored bytes.
-// With sb = max(E - 7, 1) every element is a multiple of 2^(E-143): the product is EXACT for every block whose largest magnitude is
-// >= 2^-8 (E >= 119) - up to the top of the range, because the packers clamp to 63488 (sk_quant_mx8) and 248 x 2^8 is the largest
-// image.  In a block of smaller weights the elements below 2^-14 land on the float16 subnormal grid (|error| <= 2^-25) and those
-// below 2^-25 vanish.  The float16 MFMA takes subnormal operands as they are (same probe: 2^-24 x 1024 = 2^-14).
-template <typename T, bool HI> __device__ __forceinline__ unsigned sk_cvt8_pair(unsigned src, float X) {
-  if constexpr (ElemTraits<T>::kCode == 2) return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)src, X, HI));
-  else return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)src, X, HI));
-}
-template <typename T> __device__ __forceinline__ void sk_widen8(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
-  lo[0] = sk_cvt8_pair<T, false>(raw[0], X);
-  lo[1] = sk_cvt8_pair<T, true>(raw[0], X);
-  lo[2] = sk_cvt8_pair<T, false>(raw[1], X);
-  lo[3] = sk_cvt8_pair<T, true>(raw[1], X);
-  hi[0] = sk_cvt8_pair<T, false>(raw[2], X);
-  hi[1] = sk_cvt8_pair<T, true>(raw[2], X);
-  hi[2] = sk_cvt8_pair<T, false>(raw[3], X);
-  hi[3] = sk_cvt8_pair<T, true>(raw[3], X);
 }
 
 // (sum, sum of squares) of the 16 bytes of one activation fragment, accumulated per lane
@@ -907,46 +847,6 @@ __global__ __launch_bounds__(256) void compose_kernel(const T* __restrict__ A, c
 // type for the P.V product as the reference does (HF casts attn_weights to the value dtype).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) { return tw_wave_max(v); }
-
-// Fused query operand (FusedQ, tw_common.h): the query of the cross attention is the LayerNorm'd projection of the residual
-// stream, q = rstd (u - mean gw) + cb, with u = x . W'^T accumulated by the two projections that ran before (api.hip:
-// decode_core).  Every wavefront folds the partial row statistics the residual launch left behind (one coalesced 8-byte
-// request per lane and 64 partials; reading the fragment-major row itself costs 64 cache lines per request and made the
-// launch 3 us slower) and lane l forms element l of the head's query; the MFMA operand order is then read back from a 64-element LDS
-// row PRIVATE to the wavefront (LDS operations of one wavefront stay in order: no barrier).  All requests are issued before
-// the K / V^T requests of the caller and consumed after them, i.e. this arithmetic runs while the K fragments are in flight.
-template <typename T>
-struct QRaw {
-  static constexpr int MAXP = 3;   // partial statistics per lane: n_part <= 192 (d = 1280 in 8-row tiles: 160)
-  float u, gw, cb;
-  f32x2_t st[MAXP];
-};
-template <typename T>
-__device__ __forceinline__ void fq_request(QRaw<T>& r, const FusedQ& fq, int b, int h, int lane) {
-  r.u = fq.u[(long long)b * fq.d + h * 64 + lane];
-  r.gw = fq.gw[h * 64 + lane];
-  r.cb = fq.cb[h * 64 + lane];
-  const f32x2_t* sp = reinterpret_cast<const f32x2_t*>(fq.stats) + (long long)b * fq.n_part;
-#pragma unroll
-  for (int m = 0; m < QRaw<T>::MAXP; ++m) r.st[m] = sp[min(lane + 64 * m, fq.n_part - 1)];
-}
-// qrow: this wavefront's 64-element LDS row.  Returns with the element `lane` of the query stored there (type T).
-template <typename T>
-__device__ __forceinline__ void fq_finish(const QRaw<T>& r, const FusedQ& fq, int lane, T* qrow) {
-  float s = 0.f, ss = 0.f;
-#pragma unroll
-  for (int m = 0; m < QRaw<T>::MAXP; ++m) {
-    const bool on = lane + 64 * m < fq.n_part;
-    s += on ? r.st[m][0] : 0.f;
-    ss += on ? r.st[m][1] : 0.f;
-  }
-  s = tw_wave_sum(s);
-  ss = tw_wave_sum(ss);
-  const float inv_k = __builtin_amdgcn_rcpf((float)fq.d);
-  float mean, rstd;
-  tw_ln_scalars(s, ss, inv_k, mean, rstd);
-  qrow[lane] = tw_cast<T>(tw_ln_apply(r.u, mean, rstd, r.gw, r.cb));
-}
 
 // SINGLE: n_bound <= NW*64, so every K and V^T fragment of the head is requested before anything is waited for
 // (one memory round trip per head); otherwise two passes over chunks of NW*64 keys.
@@ -3097,8 +2997,9 @@ hipError_t launch_dec_self_attn_ragged(int dtype, const void* q, const void* kc,
 hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
-                                 hipStream_t st) {
+                                 hipStream_t st, int* grid3) {
   if (Tp % 64 != 0 || Tp < T) return hipErrorInvalidValue;
+  if (grid3) { grid3[0] = H; grid3[1] = B; grid3[2] = 1; }   // one workgroup per (head, row) unless a rows flavour is picked below
   const bool single = Tp <= 512;
   const bool f = fq.u != nullptr;
   if (f) {   // the partial statistics must fit the per-lane request budget of fq_request
@@ -3108,6 +3009,9 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
   }
   if (ksc || vsc) {  // fp8 K / V^T caches with per-key scales (MXFP8 contexts: bf16 or - TW_F16_W8A16 - float16 activations)
     if (!ksc || !vsc || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
+    if (rows_streams > 0 && B > rows_streams)   // several positions per stream: one e4m3 K / V^T pass per (stream, head, 16 positions)
+      return launch_dec_cross_attn_kv8_rows(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, ksc, vsc, rows_streams,
+                                            st, grid3);
     const size_t lds8 = (size_t)Tp * sizeof(float) * 2;
 #define CA8_GO(TT, GV, FV) hipLaunchKernelGGL((dec_cross_attn_kv8_kernel<TT, GV, FV>), dim3(H, B), dim3(512), lds8, st,                \
                                           (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, (const TT*)q,  \
@@ -3124,6 +3028,7 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
     if (B % rows_streams != 0 || Tp > 1536) return hipErrorInvalidValue;
     const int n_pos = B / rows_streams;
     const dim3 grid(H, rows_streams, (n_pos + 15) / 16);
+    if (grid3) { grid3[1] = rows_streams; grid3[2] = (n_pos + 15) / 16; }
     const size_t esz = dtype == 0 ? 4 : 2;
     const size_t ldsr = ((size_t)16 * (Tp + 4) + 8 * 16 * 68 + 2 * 8 * 16) * sizeof(float) + 16 * 64 * esz;
     constexpr int lds_cap = 16 * (1536 + 4) * 4 + 8 * 16 * 68 * 4 + 2 * 8 * 16 * 4 + 16 * 64 * 4;

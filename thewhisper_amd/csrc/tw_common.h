@@ -335,10 +335,16 @@ struct FusedQ {
   const float* gw; const float* cb;   // folded-LayerNorm companions of the query projection (float32 [d])
   int d;
 };
+// grid3 non-null: receives the x, y, z workgroup counts of the launch - (H, B, 1), or (H, rows_streams, ceil(positions / 16)) where a rows
+// flavour serves it (rows_streams > 0 and B > rows_streams: dec_cross_attn_rows_kernel, dec_cross_attn_kv8_rows_kernel)
 hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
-                                 hipStream_t st);
+                                 hipStream_t st, int* grid3 = nullptr);
+// its rows flavour for the fp8 caches (k_decode_kv8_rows.hip): reached through launch_dec_cross_attn only, which has checked the arguments
+hipError_t launch_dec_cross_attn_kv8_rows(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
+                                          int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
+                                          const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st, int* grid3);
 // load-time composition for "cross query ahead": out[n][k] = sum_j A[n][j] Bm[j][k] (row-major, T), c0[n] = sum_j A[n][j] bvec[j]
 hipError_t launch_compose(int dtype, const void* A, const void* Bm, const void* bvec, void* out, float* c0, int N, int J, int K,
                           hipStream_t st);

@@ -861,6 +861,13 @@ class WhisperEngine:
         self._chk(self.lib.tw_last_prompt_rows(self.ctx, *[C.byref(x) for x in v]), "tw_last_prompt_rows")
         return {"launches": int(v[0].value), "positions": int(v[1].value)}
 
+    def last_cross_grid(self) -> tuple:
+        """Workgroup counts (x, y, z) of the most recent decoder cross-attention launch (tw_last_cross_grid): ``(heads, rows, 1)`` for a
+        one-position step, ``(heads, streams, ceil(positions / 16))`` for a rows launch with several positions per stream."""
+        g = (C.c_int32 * 3)()
+        self._chk(self.lib.tw_last_cross_grid(self.ctx, g), "tw_last_cross_grid")
+        return (int(g[0]), int(g[1]), int(g[2]))
+
     def last_timings(self) -> Dict[str, float]:
         ms = (C.c_float * 5)()
         steps = C.c_int32(0)

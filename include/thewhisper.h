@@ -503,10 +503,12 @@ int tw_generate_sample_filtered(tw_ctx* ctx, int32_t B, const int32_t* prompt_ho
  * <= -1e9 is a placeholder.  Deviation: where float32 rounding maps two different logits of one beam onto the same accumulated score,
  * the larger logit is listed first (the rule says the lower id); real ties between equal logits follow the rule.
  *
- * Rows: beam k of clip c is row (slot) k * n_clips + c.  The call copies every clip's cross K / V to the slots of its beams >= 1 and
- * never writes slots 0 .. n_clips-1: afterwards the context holds the n_clips clips as tw_cross_kv left them (tw_score_tokens and
- * further tw_generate_* calls for them need no re-encoding); whatever slots n_clips .. n_clips * K - 1 held is gone.  A step is the
- * ordinary decoder pass over n_clips * K rows plus four short launches (slice partials, one workgroup per clip for steps 3-6 / 8 / 9,
+ * Rows: beam k of clip c is launch row k * n_clips + c and reads the cross K / V^T of slot c - one pass over a clip's K / V^T per
+ * (layer, head, step) serves all of its beams.  No cross-K/V slot is written, and slots n_clips .. keep what tw_cross_kv(_at) /
+ * tw_adopt_cross_kv put there: afterwards the context holds every slot as it was (tw_score_tokens and further tw_generate_* calls
+ * need no re-encoding, for the clips and for whatever the slots behind them hold).  The self-attention caches, the sequence state
+ * and the alignment rows of rows 0 .. n_clips * K - 1 are overwritten, as by any decode over that many rows.  A step is the
+ * decoder pass over n_clips * K rows plus four short launches (slice partials, one workgroup per clip for steps 3-6 / 8 / 9,
  * the in-place cache reorder, the position); steps are not captured, so use_graph contexts run the same launches.  A clip's result
  * does not depend on its slot or on its batch-mates.  tw_last_timings[3] and the step count are filled; the state tables live in
  * context-owned device memory, allocated by the first beam call of a context (a sibling owns its own) and freed by tw_destroy.
@@ -579,7 +581,8 @@ int tw_last_prompt_rows(tw_ctx* ctx, int32_t* launches, int32_t* positions);
  * with one position per stream read (heads, rows, 1): one workgroup per head and row.  A rows launch with several positions per stream
  * (batched prefill, prompt as rows, a verify launch, tw_score_tokens) reads (heads, streams, ceil(positions / 16)) in every dtype, the
  * fp8 contexts included: one pass over a stream's K / V^T serves up to 16 of its positions.  A generate call ends with one-position
- * steps, so the rows form is read behind a call that ends with a rows launch, such as tw_score_tokens. */
+ * steps, so the rows form is read behind a call that ends with a rows launch, such as tw_score_tokens.  A step of tw_generate_beam(_aligned),
+ * the prompt steps included, reads (heads, n_clips, 1): one workgroup per head and CLIP serves the clip's num_beams rows. */
 int tw_last_cross_grid(tw_ctx* ctx, int32_t* grid3);
 
 /* Token log-probabilities and the no-speech probability of FINISHED sequences, by a teacher-forced re-scoring pass.  Replaces: the

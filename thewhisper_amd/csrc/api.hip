@@ -1052,6 +1052,9 @@ struct DecodeOpts {
   // `embed` says), the K / V^T scatter of the QKV launch and the self attention are the ragged instantiations (tw_common.h:
   // tw_row_pos); every other launch is the plain step's
   const int* n_pad = nullptr;
+  // > 0: a step of the beam loop (ordinary step only) - the B rows are beam_clips clips x B / beam_clips beams, beam k of clip c = row
+  // k * beam_clips + c, and the cross attention of every row of clip c reads the K / V^T of slot c (launch_dec_cross_attn)
+  int beam_clips = 0;
 };
 
 // one token for every stream: embed -> Ld layers -> final LN + tied logits (fp32)
@@ -1060,6 +1063,7 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, const DecodeOpts& o = DecodeOp
   const size_t e = c->esz;
   const int rs = o.rows_streams; const int* n_pad = o.n_pad;
   if (n_pad && rs != 0) return fail(c, TW_EINVAL, "decode_core: a ragged step is an ordinary step with its own embedding");
+  if (o.beam_clips != 0 && (rs != 0 || n_pad)) return fail(c, TW_EINVAL, "decode_core: a beam step is an ordinary step");
   if (n_pad) HIPCHK(c, launch_embed_ragged(dt, c->cur_ids, c->stt, n_pad, c->tok_emb, c->dec_pos, c->dx0, B, d, st));
   else if (o.embed) HIPCHK(c, launch_embed(dt, rs > 0 ? o.ids : c->cur_ids, c->stt, c->tok_emb, c->dec_pos, c->dx0, B, d, rs, st));
   void* xin = c->dx0;
@@ -1106,7 +1110,7 @@ int decode_core(tw_ctx* c, int B, hipStream_t st, const DecodeOpts& o = DecodeOp
                                     c->datt, B, H, T, c->Tp, (c->Ha > 0 && o.record_alignment) ? c->align_slot + (size_t)l * H : nullptr, c->align,
                                     o.record_alignment ? c->Ha : 0,
                                     P, c->stt, c->w8 ? c->cross_ksc + (size_t)c->Bmax * H * c->Tp * l : nullptr,
-                                    c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, st, c->last_cross_grid));
+                                    c->w8 ? c->cross_vsc + (size_t)c->Bmax * H * c->Tp * l : nullptr, rs, o.beam_clips, st, c->last_cross_grid));
     {
       GemvArgs a{};
       a.x = c->datt; a.ldx = d; a.W = L.wo_c; a.wscale = L.s_oc; a.a16 = c->a16; a.tr = L.tr_oc; a.bias = L.bo_c; a.N = d; a.K = d; a.B = B; a.res = xmid; a.ldres = d;
@@ -1896,11 +1900,6 @@ static int generate_beam_checked(const char* fn, bool aligned_entry, tw_ctx* c, 
   if (r != TW_OK) return r;
   hs.state = DecState{0, n_prompt, max_len - 1, rows};
   HIPCHK(c, hipMemcpyAsync(c->stt, &hs.state, sizeof(DecState), hipMemcpyHostToDevice, st));
-  // every clip's cross K / V for its beams 1 .. K-1: slots n .. n K - 1 (the clips' own slots are only read)
-  const size_t ckv_e = c->esz;
-  HIPCHK(c, launch_beam_cross_copy(c->cross_k, c->cross_v, (long long)((size_t)c->Bmax * c->Tp * c->d * ckv_e),
-                                   (long long)((size_t)c->Tp * c->d * ckv_e), c->Ld, n, K, st));
-  c->cross_B = n;   // the slots behind the clips now hold their copies
 
   BeamArgs ba{};
   SamplerArgs& sa = ba.s;
@@ -1923,7 +1922,9 @@ static int generate_beam_checked(const char* fn, bool aligned_entry, tw_ctx* c, 
   const int Pp = (P + 63) / 64 * 64;
   // embeds from cur_ids; without want_alignment the alignment rows of an earlier call stay as they are, with it every beam's rows
   // are recorded where the beam sits (prompt steps included) and gathered along the ancestry once the loop is over
-  DecodeOpts step; step.record_alignment = rec;
+  // every beam of clip b reads the cross K / V^T of slot b (one pass per clip and head): no cross-K/V slot is written, and the slots
+  // behind the clips keep what they held
+  DecodeOpts step; step.record_alignment = rec; step.beam_clips = n;
   tic(c, 3, st);
   constexpr int LAG = 2;
   int steps = 0;

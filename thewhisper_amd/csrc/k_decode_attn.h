@@ -106,4 +106,195 @@ __device__ __forceinline__ void fq_finish(const QRaw<T>& r, const FusedQ& fq, in
   qrow[lane] = tw_cast<T>(tw_ln_apply(r.u, mean, rstd, r.gw, r.cb));
 }
 
+// Score rows (= columns that are computed to the end) of the beams mode below: a clip has at most kBeamMax = 8 beams
+constexpr int kBeamCols = 8;
+
+// Rows flavour of dec_cross_attn_kernel (rows mode with more than one position per stream: prefill_core, verify_round,
+// tw_score_tokens).  One workgroup per (stream, head, group of up to 16 of the stream's positions): column j of the MFMA B operands
+// is position g * 16 + j of the stream, i.e. row srow + (g * 16 + j) * rows_streams of the launch, so ONE pass over the head's K / V^T
+// serves 16 queries with the matrix instructions the single-query kernel spends on one (there every column carries the same query).
+// Every column is computed by that kernel's expression tree - a column of an MFMA depends on its own B column only; column max
+// over the kq lane groups, then over the wavefronts in index order; expf(sc - M), one key per lane; tw_wave_sum, then the wavefronts
+// in index order; probabilities rounded by pack16 before P.V; partial context vectors added over the wavefronts in index order,
+// then x 1/L - so a row's bits are the one-position step's.  Columns behind the group's last position repeat that position and are
+// not written.
+// LDS (dynamic): scores float[16][Tp + 4] | partial context vectors float[8][16][68] | column max float[8][16] | normaliser
+// float[8][16] | query rows T[16][64]: 71 KiB at Tp = 512 (two workgroups per CU), 135 KiB at Tp = 1536 (one).
+//
+// BEAMS (a step of tw_generate_beam; grid (heads, n_clips, 1), rows_streams = n_clips, n_pos = K <= kBeamCols): the columns of a
+// workgroup are not consecutive positions of a stream but the K beams of clip `srow` at the SAME position.  Beam j is launch row
+// srow + j * n_clips - the row map above with p0 = 0 - and every one of them reads the K / V^T of slot srow, so a clip's cross K / V
+// is streamed once per (layer, head, step) whatever K is, and the slots behind the clips are neither read nor written.  What differs:
+//  * the alignment side output of column j is the softmax row of SLOT r_j = srow + j * n_clips at position stt->pos (the beam's row,
+//    where tw_generate_beam_aligned's gather expects it), not (srow, pos + j);
+//  * NC = kBeamCols columns instead of 16 are carried behind the score MFMAs: score rows, exponentials, normalisers, partial context
+//    vectors and query rows exist for columns 0 .. 7 only, and the P.V operand of column fr >= 8 is column fr - 8's (an MFMA column
+//    nobody reads).  LDS: 36.7 KiB at Tp = 512, 69 KiB at Tp = 1536 in float32, and half the expf of the 16-column layout.
+// Columns K .. 7 repeat beam K - 1 and are not written.  Every column that is written runs the expression tree above, operation for
+// operation, so a beam's context vector and alignment row keep the bits of the one-row kernel.
+template <typename T, bool SINGLE, bool FQ, bool BEAMS = false>
+__global__ __launch_bounds__(512) void dec_cross_attn_rows_kernel(const T* __restrict__ ck, const T* __restrict__ cv, int H, int Tp,
+                                                                   int Tlen, int rows_streams, int n_pos, const T* __restrict__ q,
+                                                                   T* __restrict__ out, const int* __restrict__ align_slot,
+                                                                   float* __restrict__ align, int Ha, int P,
+                                                                   const DecState* __restrict__ stt, FusedQ fq) {
+  constexpr int NW = 8, WS = 68;
+  constexpr int NC = BEAMS ? kBeamCols : 16;    // columns with score rows, normalisers and partial context vectors
+  constexpr int E = ElemTraits<T>::kPer16B;
+  constexpr int DS = 64 / (4 * E);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int S = Tp + 4;
+  float* sc = reinterpret_cast<float*>(smem);   // [NC][S] scores -> unnormalised probabilities
+  float* wo = sc + NC * S;                      // [NW][NC][WS]
+  float* redm = wo + NW * NC * WS;              // [NW][16]
+  float* wl = redm + NW * 16;                   // [NW][NC]
+  T* qst = reinterpret_cast<T*>(wl + NW * NC);  // [NC][64]
+  const int h = blockIdx.x, srow = blockIdx.y, p0 = BEAMS ? 0 : blockIdx.z * 16;
+  const int nc = min(NC, n_pos - p0);           // columns in use
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, kq = lane >> 4;
+  const int fc = fr & (NC - 1);                 // the column whose LDS rows lane (fr, .) reads: fr itself in the rows flavour
+  const bool own = NC == 16 || fr < NC;         // lane's MFMA column is one of the NC
+  const long long base = ((long long)srow * H + h) * Tp * 64;
+  const T* kf = ck + base;
+  const T* vtf = cv + base;
+  const int n_keys = Tlen, n_bound = Tp;
+  const int n_chunks = SINGLE ? 1 : (n_bound + NW * 64 - 1) / (NW * 64);
+  const int last64 = n_bound / 64 - 1;
+  u32x4_t qf[DS], kfr[4 * DS], vfr[4 * DS];
+  auto load_k = [&](int g64) {
+    const T* p = kf + ((long long)min(g64, last64) * (4 * DS) * 64 + lane) * E;
+#pragma unroll
+    for (int i = 0; i < 4 * DS; ++i) kfr[i] = *reinterpret_cast<const u32x4_t*>(p + (long long)i * 64 * E);
+  };
+  auto load_v = [&](int g64) {
+    const T* p = vtf + ((long long)min(g64, last64) * (4 * DS) * 64 + lane) * E;
+#pragma unroll
+    for (int i = 0; i < 4 * DS; ++i) vfr[i] = *reinterpret_cast<const u32x4_t*>(p + (long long)i * 64 * E);
+  };
+  auto row_of = [&](int j) { return srow + (p0 + min(j, nc - 1)) * rows_streams; };   // launch row of column j
+  load_k(wave);
+  if constexpr (FQ) {
+    // the group's query rows, once per workgroup: wavefront w builds the rows of columns w and (rows flavour) w + 8
+    QRaw<T> qr[NC / 8];
+#pragma unroll
+    for (int i = 0; i < NC / 8; ++i) fq_request<T>(qr[i], fq, row_of(wave + 8 * i), h, lane);
+    if (SINGLE) load_v(wave);
+#pragma unroll
+    for (int i = 0; i < NC / 8; ++i) fq_finish<T>(qr[i], fq, lane, qst + (wave + 8 * i) * 64);
+    __syncthreads();
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const u32x4_t*>(qst + fc * 64 + ds * 4 * E + kq * E);
+  } else {
+    const T* qrow = q + ((long long)row_of(fr) * H + h) * 64;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const u32x4_t*>(qrow + ds * 4 * E + kq * E);
+    if (SINGLE) load_v(wave);
+  }
+
+  // ---- scores: lane (fr, kq) holds keys kq * 4 + r of the tile for column fr ----
+  float m = -1.0e30f;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int g64 = c * NW + wave;
+    if (c > 0) load_k(g64);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ds = 0; ds < DS; ++ds) acc = sk_mfma<T>(kfr[a * DS + ds], qf[ds], acc);
+      f32x4_t sv4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = g64 * 64 + a * 16 + kq * 4 + r;
+        const float sv = (t < n_keys) ? acc[r] : -1.0e30f;
+        m = fmaxf(m, sv);
+        sv4[r] = sv;
+      }
+      if (own && g64 * 64 < n_bound) *reinterpret_cast<f32x4_t*>(sc + fr * S + g64 * 64 + a * 16 + kq * 4) = sv4;
+    }
+  }
+  m = tw_xor32_max(tw_xor16_max(m));
+  if (kq == 0) redm[wave * 16 + fr] = m;
+  __syncthreads();
+  float Mc = redm[fr];   // lane's column
+#pragma unroll
+  for (int w = 1; w < NW; ++w) Mc = fmaxf(Mc, redm[w * 16 + fr]);
+
+  // ---- probabilities of this wavefront's own keys, every column, and P.V ----
+  f32x4_t o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float ls[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) ls[j] = 0.f;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int g64 = c * NW + wave;
+    if (!SINGLE) load_v(g64);
+    const int t0 = g64 * 64 + lane;  // one key per lane
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const float M = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Mc), j));
+      float pr = 0.f;
+      if (t0 < n_bound) {
+        pr = (t0 < n_keys) ? expf(sc[j * S + t0] - M) : 0.f;
+        sc[j * S + t0] = pr;
+      }
+      ls[j] += pr;
+    }
+#pragma unroll
+    for (int ks = 0; ks < DS; ++ks) {
+      float pv[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int t = g64 * 64 + ks * 4 * E + kq * E + e;
+        pv[e] = (t < n_bound) ? sc[fc * S + t] : 0.f;  // same wavefront wrote these: LDS operations of a wavefront stay in order
+      }
+      const u32x4_t pf = pack16<T>(pv);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = sk_mfma<T>(vfr[ks * 4 + dt], pf, o[dt]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    // lane 0's sum, as in the single-query kernel: tw_wave_sum adds the four quads of a row in another order in odd quads
+    // than in even ones, so the lanes of a wavefront do not all hold the same bits
+    const float l = tw_wave_sum(ls[j]);
+    if (lane == 0) wl[wave * NC + j] = l;
+  }
+  if (own) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4_t*>(wo + (wave * NC + fr) * WS + dt * 16 + kq * 4) = o[dt];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NC / 8; ++i) {   // NC columns x 64 dims over 512 threads
+    const int j = (tid >> 6) + 8 * i, k = tid & 63;
+    float L = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) L += wl[w * NC + j];
+    const float inv = 1.0f / L;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += wo[(w * NC + j) * WS + k];
+    if (j < nc) {
+      const int b = srow + (p0 + j) * rows_streams;
+      out[(long long)(b >> 4) * 16 * H * 64 + tw_xt_index<T>(b & 15, h * 64 + k)] = (T)(v * inv);
+    }
+  }
+  const int slot = align_slot ? align_slot[h] : -1;
+  if (slot >= 0) {  // A11 side output: every column writes the softmax row of its own (stream, position) - BEAMS: (beam's row, pos)
+    const int pos = stt->pos;
+    for (int j = 0; j < nc; ++j) {
+      float L = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) L += wl[w * NC + j];
+      const float inv = 1.0f / L;
+      float* row = BEAMS ? align + (((long long)(srow + j * rows_streams) * Ha + slot) * P + pos) * Tlen
+                         : align + (((long long)srow * Ha + slot) * P + pos + p0 + j) * Tlen;
+      for (int t = tid; t < Tlen; t += 512) row[t] = sc[j * S + t] * inv;
+    }
+  }
+}
+
 }  // namespace

@@ -337,10 +337,18 @@ struct FusedQ {
 };
 // grid3 non-null: receives the x, y, z workgroup counts of the launch - (H, B, 1), or (H, rows_streams, ceil(positions / 16)) where a rows
 // flavour serves it (rows_streams > 0 and B > rows_streams: dec_cross_attn_rows_kernel, dec_cross_attn_kv8_rows_kernel)
+// beam_clips > 0 (with rows_streams == 0, B > beam_clips, no fp8 caches): a step of tw_generate_beam - the B rows are beam_clips clips
+// x B / beam_clips <= kBeamMax beams, beam k of clip c = row k * beam_clips + c, and every row of clip c attends to the K / V^T of
+// SLOT c, read once per (head, clip) by the beams mode of dec_cross_attn_rows_kernel; its alignment row goes to (row, pos); grid3
+// reads (H, beam_clips, 1).  0: not a beam step
 hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
-                                 hipStream_t st, int* grid3 = nullptr);
+                                 int beam_clips, hipStream_t st, int* grid3 = nullptr);
+// its beams mode (k_decode_beam_cross.hip): reached through launch_dec_cross_attn only, which has checked the arguments
+hipError_t launch_dec_cross_attn_beams(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
+                                       int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
+                                       int n_clips, hipStream_t st, int* grid3);
 // its rows flavour for the fp8 caches (k_decode_kv8_rows.hip): reached through launch_dec_cross_attn only, which has checked the arguments
 hipError_t launch_dec_cross_attn_kv8_rows(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                           int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
@@ -522,9 +530,6 @@ hipError_t launch_beam_step(const BeamArgs& a, bool in_prompt, hipStream_t st);
 // one run of 4096 elements): row k * n_clips + c <- row beam_idx[..] * n_clips + c for the keys [0, pos], in place
 hipError_t launch_beam_reorder(int dtype, void* kc, void* vc, long long layer_stride, long long bstride, long long hstride, int Ld, int H,
                                int key_bound, const BeamArgs& a, hipStream_t st);
-// cross K / V of clip c (slot c) -> slots k * n_clips + c, k = 1 .. K-1, every layer, one launch of 16-byte copies; the source slots
-// are only read
-hipError_t launch_beam_cross_copy(void* ck, void* cv, long long layer_bytes, long long slot_bytes, int Ld, int n_clips, int K, hipStream_t st);
 // alignment rows follow the finished hypotheses (beam_align_gather_kernel), one launch, in place: afterwards slot k * n_clips + c of
 // align [slots][Ha][P][T] holds rows 0 .. fin_len - 2 of finished hypothesis k of clip c (placeholders are left alone).  n_pos: the
 // positions the loop consumed at most (max_len - 1)

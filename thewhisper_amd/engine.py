@@ -687,7 +687,10 @@ class WhisperEngine:
                       begin_suppress: Iterable[int] = (220, 50257), suppress: Iterable[int] = (),
                       want_alignment: bool = False) -> Dict[str, np.ndarray]:
         """Beam search with ``num_beams`` (2..8) beams per row of ``prompt`` (tw_generate_beam, where the rule - HF's
-        ``GenerationMixin._beam_search`` - is stated).  Needs ``max_batch >= rows x num_beams``.  ``sequences`` int64 [n, L]: the best
+        ``GenerationMixin._beam_search`` - is stated).  Needs ``max_batch >= rows x num_beams``: beam k of clip c is launch row
+        ``k * n + c`` and reads the cross K/V of slot ``c``.  No cross-K/V slot is written - the slots behind the ``n`` clips keep what
+        ``cross_kv`` / ``adopt_cross_kv`` put there - while the self-attention caches, the sequence state and the alignment rows of rows
+        ``0 .. n * num_beams - 1`` are overwritten.  ``sequences`` int64 [n, L]: the best
         hypotheses; ``scores`` float32 [n]; ``nbest_sequences`` int64 [n, K, Ln] and ``nbest_scores`` float32 [n, K]: every hypothesis in
         descending score (a score <= -1e9 marks a placeholder).  Everything behind a hypothesis's end is ``pad_id``.  The other
         keywords are ``generate_greedy``'s processors.  ``lengths`` int32 [n] and ``nbest_lengths`` int32 [n, K]: the tokens of every
@@ -863,7 +866,8 @@ class WhisperEngine:
 
     def last_cross_grid(self) -> tuple:
         """Workgroup counts (x, y, z) of the most recent decoder cross-attention launch (tw_last_cross_grid): ``(heads, rows, 1)`` for a
-        one-position step, ``(heads, streams, ceil(positions / 16))`` for a rows launch with several positions per stream."""
+        one-position step, ``(heads, streams, ceil(positions / 16))`` for a rows launch with several positions per stream,
+        ``(heads, clips, 1)`` for a step of ``generate_beam``."""
         g = (C.c_int32 * 3)()
         self._chk(self.lib.tw_last_cross_grid(self.ctx, g), "tw_last_cross_grid")
         return (int(g[0]), int(g[1]), int(g[2]))

@@ -119,22 +119,69 @@ def test_cross_grid_of_a_beam_step_is_heads_by_clips(engines):
 
 
 # ---- 4. bits do not depend on the other slots ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dtype", ["f16", "bf16"])
-@pytest.mark.parametrize("shape", [(3, 8), (5, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
-def test_bits_do_not_depend_on_the_other_slots(engines, shape, dtype):
+def bits_case(get, shape, dtype, T=em.T):
     n, K = shape
-    name, sel = SHAPES[shape][0], SHAPES[shape][1][em.T]
+    name, sel = SHAPES[shape][0], SHAPES[shape][1][T]
     kw = dataclasses.replace(bj.case(name), K=K).engine_kw()
-    eng = engines(dtype)
+    eng = get(dtype, T)
     got = []
     for slots in (_foreign(sel, n * K), [sel[c] for _ in range(K) for c in range(n)]):   # foreign clips | slot k n + c holds clip c
-        _fill(eng, slots)
+        _fill(eng, slots, T)
         res = eng.generate_beam(em.prompt(sel), **kw, want_alignment=True)
         got.append((res, eng.get_alignment(n * K, res["nbest_sequences"].shape[2] - 1)))
     (a, rows_a), (b, rows_b) = got
     for key in ("nbest_sequences", "nbest_scores", "nbest_lengths"):      # (tobytes: the scores bit for bit)
-        assert a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (shape, dtype, key)
+        assert a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (shape, dtype, T, key)
     live = [(c, k, int(a["nbest_lengths"][c, k])) for c in range(n) for k in range(K) if a["nbest_scores"][c, k] > -1e9]
     assert len(live) >= n
     for c, k, L in live:
-        assert np.array_equal(rows_a[k * n + c, :, : L - 1].view(np.int32), rows_b[k * n + c, :, : L - 1].view(np.int32)), (shape, dtype, c, k)
+        assert np.array_equal(rows_a[k * n + c, :, : L - 1].view(np.int32), rows_b[k * n + c, :, : L - 1].view(np.int32)), (shape, dtype, T, c, k)
+    print(f"beams bits {dtype} T={T} {n}x{K}: independent of the other slots")
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+@pytest.mark.parametrize("shape", [(3, 8), (5, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_bits_do_not_depend_on_the_other_slots(engines, shape, dtype):
+    bits_case(engines, shape, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_bits_do_not_depend_on_the_other_slots_two_pass(engines, dtype):
+    """T = 600 -> Tp = 640: the two-pass (SINGLE = false) instantiations of the beams mode in the 16-bit types (f32: test 1)."""
+    bits_case(engines, (3, 8), dtype, 600)
+
+
+# ---- 5. the plain launch sequence (FQ = false: the query is loaded, not formed in LDS) ------------------------------------------------
+PLAIN = [(t, T) for t in ("f32", "f16", "bf16") for T in (em.T, 600)]     # SINGLE and two-pass
+
+
+def plain_child():
+    """In the child: TW_FUSE_CQ=0 is read once per process."""
+    import os
+    assert os.environ.get("TW_FUSE_CQ") == "0"
+    made = {}
+
+    def get(dtype, T):
+        if (dtype, T) not in made:
+            dims, w = em.model(2.5)
+            made[(dtype, T)] = make_engine(dims, w, T=T, max_batch=64, dtype=dtype, heads=em.HEADS)
+        return made[(dtype, T)]
+
+    try:
+        for dtype, T in PLAIN:
+            bits_case(get, (3, 8), dtype, T)
+    finally:
+        for e in made.values():
+            e.close()
+
+
+def test_bits_do_not_depend_on_the_other_slots_on_the_plain_launch_sequence():
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, "-c", "from tests.test_gpu_beam_shared import plain_child; plain_child()"],
+                         env=dict(os.environ, TW_FUSE_CQ="0"), cwd=root, timeout=600, capture_output=True, text=True)
+    print(run.stdout)
+    assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
+    assert run.stdout.count("independent of the other slots") == len(PLAIN)

@@ -62,6 +62,9 @@ CASES = {50: ("f32", "bf16", "fp8a16"), 500: ("f32", "bf16", "f16", "fp8a16", "f
 FORCED = {(T, t) for T in (500, 1500) for t in ("bf16", "f32", "fp8a16")}
 ALONE = {(750, "bf16"), (1500, "fp8a16")}
 PLAIN = [(500, "f32"), (750, "bf16"), (1500, "f16"), (1000, "fp8a16")]
+# the FQ = false instantiations PLAIN leaves out: dec_cross_attn_kernel<f32, two-pass>, <bf16, SINGLE>, <f16, SINGLE>,
+# dec_cross_attn_kv8_kernel<bf16, G = 1> and <bf16, G = 3> (float16 fp8 contexts: tests/test_gpu_cross_rows_fp8.py)
+PLAIN_MORE = [(750, "f32"), (50, "bf16"), (500, "f16"), (50, "fp8a16"), (1450, "fp8a16")]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -213,10 +216,10 @@ def test_cross_pointer_every_frame_step_rows_and_alignment(T, dtype):
     pointer_case(T, dtype)
 
 
-def plain_child():
+def plain_child(cases=PLAIN):
     """(d), in the child: TW_FUSE_CQ=0 is read once per process."""
     assert os.environ.get("TW_FUSE_CQ") == "0"
-    for T, dtype in PLAIN:
+    for T, dtype in cases:
         pointer_case(T, dtype, fused=False)
 
 
@@ -229,3 +232,13 @@ def test_cross_pointer_on_the_plain_launch_sequence():
     print(run.stdout)
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     assert run.stdout.count("plain sequence: step mode") == len(PLAIN)
+
+
+def test_cross_pointer_on_the_plain_launch_sequence_other_instantiations():
+    """The `FQ = false` instantiations the test above does not launch (PLAIN_MORE), same assertions, one child process."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, "-c", "from tests.test_gpu_cross import plain_child; plain_child(PLAIN_MORE)".replace("PLAIN_MORE", repr(PLAIN_MORE))],
+                         env=dict(os.environ, TW_FUSE_CQ="0"), cwd=root, timeout=600, capture_output=True, text=True)
+    print(run.stdout)
+    assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
+    assert run.stdout.count("plain sequence: step mode") == len(PLAIN_MORE)

@@ -39,6 +39,8 @@ N_REF = 65                  # stepped positions
 STREAMS = (1, 2, 3, 16)
 ROWS_TOL = 1e-4             # tests/test_gpu_score.py: TOL
 PLAIN = [(100, "f32"), (750, "bf16")]
+# the FQ = false instantiations of dec_cross_attn_rows_kernel PLAIN leaves out: T = 100 -> Tp = 128, SINGLE; T = 600 -> Tp = 640, two-pass
+PLAIN_MORE = [(600, "f32"), (100, "bf16"), (100, "f16"), (600, "f16")]
 OFF = dict(begin_suppress=(), suppress=(), timestamps=False)
 
 
@@ -144,10 +146,10 @@ def test_cross_rows_near_uniform_attention_rows_equal_the_steps(dtype):
         eng.close()
 
 
-def plain_child():
+def plain_child(cases=PLAIN):
     """(d), in the child: TW_FUSE_CQ=0 is read once per process."""
     assert os.environ.get("TW_FUSE_CQ") == "0"
-    for T, dtype in PLAIN:
+    for T, dtype in cases:
         rows_case(T, dtype, f"cross rows T={T} {dtype} plain sequence")
 
 
@@ -158,3 +160,13 @@ def test_cross_rows_on_the_plain_launch_sequence():
     print(run.stdout)
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     assert run.stdout.count("plain sequence:") == len(PLAIN)
+
+
+def test_cross_rows_on_the_plain_launch_sequence_other_instantiations():
+    """The `FQ = false` instantiations of the rows kernel the test above does not launch (PLAIN_MORE): (a) - (c) in one child process."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, "-c", "from tests.test_gpu_cross_rows import plain_child; plain_child(PLAIN_MORE)".replace("PLAIN_MORE", repr(PLAIN_MORE))],
+                         env=dict(os.environ, TW_FUSE_CQ="0"), cwd=root, timeout=600, capture_output=True, text=True)
+    print(run.stdout)
+    assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
+    assert run.stdout.count("plain sequence:") == len(PLAIN_MORE)

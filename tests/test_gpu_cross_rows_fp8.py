@@ -143,10 +143,16 @@ def test_fp8_cross_rows_near_uniform_attention_rows_equal_the_steps(dtype):
         eng.close()
 
 
-def plain_child():
+# the FQ = false instantiations of dec_cross_attn_kv8_rows_kernel - and, through the steps they are compared with, of
+# dec_cross_attn_kv8_kernel - that (1000, "fp8a16") leaves out: G = 1 (T = 100), 2 (600), 3 (1100) in bf16 and float16
+PLAIN_MORE = [(100, "fp8a16"), (1100, "fp8a16"), (100, "fp8f16"), (600, "fp8f16"), (1100, "fp8f16")]
+
+
+def plain_child(cases=((1000, "fp8a16"),)):
     """(d), in the child: TW_FUSE_CQ=0 is read once per process."""
     assert os.environ.get("TW_FUSE_CQ") == "0"
-    rows_case(1000, "fp8a16", "fp8 cross rows T=1000 fp8a16 plain sequence")
+    for T, dtype in cases:
+        rows_case(T, dtype, f"fp8 cross rows T={T} {dtype} plain sequence")
 
 
 def test_fp8_cross_rows_on_the_plain_launch_sequence():
@@ -156,3 +162,13 @@ def test_fp8_cross_rows_on_the_plain_launch_sequence():
     print(run.stdout)
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     assert run.stdout.count("plain sequence:") == 1
+
+
+def test_fp8_cross_rows_on_the_plain_launch_sequence_other_instantiations():
+    """The `FQ = false` instantiations the test above does not launch (PLAIN_MORE), same assertions, one child process."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, "-c", "from tests.test_gpu_cross_rows_fp8 import plain_child; plain_child(PLAIN_MORE)".replace("PLAIN_MORE", repr(PLAIN_MORE))],
+                         env=dict(os.environ, TW_FUSE_CQ="0"), cwd=root, timeout=600, capture_output=True, text=True)
+    print(run.stdout)
+    assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
+    assert run.stdout.count("plain sequence:") == len(PLAIN_MORE)

@@ -102,6 +102,25 @@ def test_a_padded_row_is_the_row_alone_bit_for_bit(dtype, weights, pcm):
         eng.close()
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16"])
+def test_a_padded_row_past_256_positions_is_the_row_alone(dtype, weights, pcm):
+    """The ragged self attention's two-pass instantiation (key bound above 256: 4 wavefronts, SINGLE = false), which the 136 positions
+    above do not reach: the padded call runs to absolute position 266, the heavily padded row alone stays in the first two buckets."""
+    n_pad, n_prompt = [0, 200], 250
+    prompt = padded_batch(n_pad, n_prompt, seed=3)
+    kw = dict(max_new_tokens=16, min_new_tokens=16, timestamps=True, want_alignment=True)
+    eng = make_engine(DIMS, weights, T=T, max_batch=2, dtype=dtype, heads=HEADS, use_graph=False)
+    try:
+        mel = eng.logmel(torch.from_numpy(pcm[:2]).cuda())
+        fill(eng, mel, range(2))
+        got = results(eng, 2, n_prompt, eng.generate_greedy(prompt, n_pad=n_pad, **kw))
+        assert got[0].shape == (2, n_prompt + 16)
+        for b in range(2):
+            assert_row_is_the_row_alone(eng, mel, b, prompt[b], n_pad[b], n_prompt, got, b, kw, f"{dtype} row {b} (n_pad {n_pad[b]})")
+    finally:
+        eng.close()
+
+
 def test_a_padded_row_in_the_second_group_of_sixteen(weights, pcm):
     B, n_prompt = 17, 8
     n_pad = [0] * 16 + [5]

@@ -25,7 +25,6 @@ namespace {
 constexpr int kRedStride = 17;
 constexpr int kRedTile = 16 * kRedStride;   // floats per partial tile in LDS
 
-__device__ __forceinline__ float wave_sum(float v) { return tw_wave_sum(v); }
 // erf-GELU (activation_function = "gelu").  Strict-f32 contexts use the library erff; bf16 contexts, whose outputs are
 // rounded to 8 mantissa bits anyway, use the Abramowitz-Stegun 7.1.26 rational form (|error| < 2e-7 on erf + one fast
 // exp: ~12 instead of ~45 VALU instructions per element, which is a third of the fc1 GEMM's epilogue-bound run time).
@@ -799,8 +798,8 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(T* __restrict__ W, const T
     sb += (float)beta[k] * w;
     W[(long long)n * K + k] = wr;
   }
-  sg = wave_sum(sg);
-  sb = wave_sum(sb);
+  sg = tw_wave_sum(sg);
+  sb = tw_wave_sum(sb);
   if (lane == 0) {
     gw[n] = sg;
     cb[n] = sb + (bias ? (float)bias[n] : 0.f);
@@ -846,7 +845,6 @@ __global__ __launch_bounds__(256) void compose_kernel(const T* __restrict__ A, c
 // Softmax in fp32 (scores -> LDS, block max, exp, sum); probabilities are rounded to the storage
 // type for the P.V product as the reference does (HF casts attn_weights to the value dtype).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_max(float v) { return tw_wave_max(v); }
 
 // SINGLE: n_bound <= NW*64, so every K and V^T fragment of the head is requested before anything is waited for
 // (one memory round trip per head); otherwise two passes over chunks of NW*64 keys.
@@ -990,9 +988,6 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
 // (p = 1e-3 against values around 1 is 2^-17), so it is carried times 2^7 - sb - 127 <= 8 for float16 data, hence the operand
 // stays <= 2^15 - and the result takes the 2^-7 back in float32 (kPvUp below).  With values around 1 the operand is then the
 // plain probability, the operand of the TW_F16 kernel.
-template <typename T> __device__ __forceinline__ void kv8_widen(const u32x4_t& raw, float X, u32x4_t& lo, u32x4_t& hi) {
-  sk_widen8<T>(raw, X, lo, hi);
-}
 
 // G = 64-key groups per wavefront (1, 2 or 3: up to 512 / 1024 / 1536 keys with 8 wavefronts, i.e. every chunk length up to
 // 30 s).  At 32 registers per group and operand the whole head fits the register file, so - unlike the bf16 kernel, which
@@ -1053,7 +1048,7 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const T* __restrict__ q, co
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       u32x4_t k0, k1;
-      kv8_widen<T>(kraw[g][a], __builtin_bit_cast(float, ((ks4[g] >> (8 * a)) & 0xffu) << 23), k0, k1);
+      sk_widen8<T>(kraw[g][a], __builtin_bit_cast(float, ((ks4[g] >> (8 * a)) & 0xffu) << 23), k0, k1);
       f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
       acc = sk_mfma<T>(k0, qf[0], acc);
       acc = sk_mfma<T>(k1, qf[1], acc);
@@ -1090,7 +1085,7 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const T* __restrict__ q, co
     ls += pr;
     u32x4_t v0[4], v1[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) kv8_widen<T>(vraw[g][dt], 1.0f, v0[dt], v1[dt]);
+    for (int dt = 0; dt < 4; ++dt) sk_widen8<T>(vraw[g][dt], 1.0f, v0[dt], v1[dt]);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {   // operand j of lane (kq, .): keys kq*16 + j*8 .. +7 of this 64-key group
       float pv[8];
@@ -1132,42 +1127,24 @@ __device__ __forceinline__ float attn_mfma_block_kv8(const T* __restrict__ q, co
 // q [B, H*64] row-major; kc / vc per (stream, head): `rows` (multiple of 64) keys of K fragment-major / V^T fragment-major
 // NW wavefronts of 64 keys each: 1 / 2 wavefronts while the sequence is shorter than 64 / 128 positions (the host picks the
 // 64-key bucket per step): no idle wavefronts to launch and to meet at the barriers of the cross-wavefront reductions
-template <typename T, bool SINGLE, int NW>
+// MAP: the row map (k_decode_attn.h: attn_row_map) - AttnRowsMap, trailing argument int rows_streams (plain steps and rows mode), or
+// AttnRaggedMap, trailing argument const int* n_pad (ragged steps; the table pointer stands behind the leading arguments).
+template <typename T, bool SINGLE, int NW, typename MAP = AttnRowsMap>
 __global__ __launch_bounds__(NW * 64) void dec_self_attn_kernel(const T* __restrict__ q, const T* __restrict__ kc,
                                                                  const T* __restrict__ vc, int rows, int H, int key_bound,
-                                                                 T* __restrict__ out, const DecState* __restrict__ stt, int rows_streams) {
+                                                                 T* __restrict__ out, const DecState* __restrict__ stt,
+                                                                 typename MAP::Arg map_arg) {
   // argument order: what the K / V^T / q request addresses need comes first (kernarg preload, see skinny_mfma_kernel)
   __shared__ float sc[512];
   __shared__ float red[2 * 4 + 4 * 64];
   asm volatile("" ::"s"(q), "s"(kc), "s"(vc), "s"(rows), "s"(H), "s"(key_bound));
   const int h = blockIdx.x, b = blockIdx.y;
-  // rows mode (prefill): row b is a position of stream b % rs - its K / V^T live in that stream's cache (the addresses depend on
-  // kernel arguments only, as before) and it sees the keys up to ITS position (causal inside the launch)
-  const int srow = rows_streams > 0 ? b % rows_streams : b;
-  const int n_keys = stt->pos + (rows_streams > 0 ? b / rows_streams : 0) + 1;
+  const int srow = MAP::stream(b, map_arg);
+  const int n_keys = MAP::pos(stt->pos, b, map_arg) + 1;
   const long long base = ((long long)srow * H + h) * rows * 64;
   // the host guarantees pos < key_bound (a multiple of 64, <= rows): the requests do not wait for `pos`
   attn_mfma_block<T, NW, SINGLE>(q + ((long long)b * H + h) * 64, kc + base, vc + base, n_keys, key_bound, sc, red,
                                 out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64);  // fragment-major, groups of 16 streams
-}
-
-// The same for a ragged step (tw_common.h: tw_row_pos): stream b sees the keys [0, q] of its ROW position q <= pos < key_bound, so the
-// requests cover them; the keys between q and the bucket's end are masked like the ones behind pos in the kernel above, and the
-// result does not depend on the bucket (attn_mfma_block: masked keys contribute exact zeros).  The table pointer stands behind the
-// leading arguments, which are the plain kernel's.
-template <typename T, bool SINGLE, int NW>
-__global__ __launch_bounds__(NW * 64) void dec_self_attn_ragged_kernel(const T* __restrict__ q, const T* __restrict__ kc,
-                                                                        const T* __restrict__ vc, int rows, int H, int key_bound,
-                                                                        T* __restrict__ out, const DecState* __restrict__ stt,
-                                                                        const int* __restrict__ n_pad) {
-  __shared__ float sc[512];
-  __shared__ float red[2 * 4 + 4 * 64];
-  asm volatile("" ::"s"(q), "s"(kc), "s"(vc), "s"(rows), "s"(H), "s"(key_bound));
-  const int h = blockIdx.x, b = blockIdx.y;
-  const int n_keys = tw_row_pos(stt->pos, n_pad[b]) + 1;
-  const long long base = ((long long)b * H + h) * rows * 64;
-  attn_mfma_block<T, NW, SINGLE>(q + ((long long)b * H + h) * 64, kc + base, vc + base, n_keys, key_bound, sc, red,
-                                out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64);
 }
 
 template <typename T, bool SINGLE, bool FQ>
@@ -1183,7 +1160,7 @@ __global__ __launch_bounds__(512) void dec_cross_attn_kernel(const T* __restrict
   __shared__ __attribute__((aligned(16))) T qst[FQ ? 8 * 64 : 8];
   asm volatile("" ::"s"(ck), "s"(cv), "s"(H), "s"(Tp), "s"(Tlen), "s"(rows_streams));
   const int h = blockIdx.x, b = blockIdx.y;
-  const int srow = rows_streams > 0 ? b % rows_streams : b;   // rows mode (prefill): the stream whose encoder K / V this row attends to
+  const int srow = AttnRowsMap::stream(b, rows_streams);   // rows mode (prefill): the stream whose encoder K / V this row attends to
   const long long base = ((long long)srow * H + h) * Tp * 64;
   const float inv = attn_mfma_block<T, 8, SINGLE, FQ>(q + ((long long)b * H + h) * 64, ck + base, cv + base, Tlen, Tp, sc, red,
                                                       out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64, fq, b, h, qst);
@@ -1213,7 +1190,7 @@ __global__ __launch_bounds__(512) void dec_cross_attn_kv8_kernel(const unsigned 
   __shared__ __attribute__((aligned(16))) T qst[FQ ? 8 * 64 : 8];
   asm volatile("" ::"s"(ck), "s"(cv), "s"(ksc), "s"(vsc), "s"(H), "s"(Tp), "s"(Tlen), "s"(rows_streams));
   const int h = blockIdx.x, b = blockIdx.y;
-  const int srow = rows_streams > 0 ? b % rows_streams : b;   // rows mode (prefill), as in dec_cross_attn_kernel
+  const int srow = AttnRowsMap::stream(b, rows_streams);
   const long long hb = ((long long)srow * H + h) * Tp;
   const float inv = attn_mfma_block_kv8<T, 8, G, FQ>(q + ((long long)b * H + h) * 64, ck + hb * 64, cv + hb * 64, ksc + hb, vsc + hb,
                                                   Tlen, Tp, sc, scv, red, out + (long long)(b >> 4) * 16 * H * 64, b & 15, h * 64,
@@ -1358,7 +1335,7 @@ __device__ __forceinline__ void slice_load(const SamplerArgs& a, const float* lg
 
 // the block's sum of one value per thread (256 threads): wavefront reduction, then the four wavefronts in index order through LDS
 __device__ __forceinline__ float block4_sum(float x, float* red, int lane, int wave) {
-  x = wave_sum(x);
+  x = tw_wave_sum(x);
   if (lane == 0) red[wave] = x;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
@@ -1473,7 +1450,7 @@ __device__ __forceinline__ SliceMerge merge_slices(const SamplerArgs& a, const P
   m.bt = wave_best(m.bt);
   m.bs = wave_best(m.bs);
   const float part_sum = (on && my_m > -INFINITY) ? p.sum * expf(my_m - m.bs.v) : 0.f;
-  const float tot = wave_sum(part_sum);
+  const float tot = tw_wave_sum(part_sum);
   if (a.timestamps && m.bs.v > -INFINITY) m.force_ts = (m.bs.v + logf(tot)) > m.bt.v;
   return m;
 }
@@ -1723,7 +1700,7 @@ template <bool MAX>
 __device__ __forceinline__ void score_block3(float (&v)[3], float (*red)[4], int lane, int wave) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const float w = MAX ? wave_max(v[j]) : wave_sum(v[j]);
+    const float w = MAX ? tw_wave_max(v[j]) : tw_wave_sum(v[j]);
     if (lane == 0) red[j][wave] = w;
   }
   __syncthreads();
@@ -1954,7 +1931,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(FilterArgs fa) {
         n += key[i] >= t ? 1 : 0;
         if ((i & 15) == 15) __builtin_amdgcn_sched_barrier(0);
       }
-      n = filter_block_sum<int>((int)wave_sum((float)n), red_n[round & 1], lane, wave);   // (counts up to 65536: exact in float32)
+      n = filter_block_sum<int>((int)tw_wave_sum((float)n), red_n[round & 1], lane, wave);   // (counts up to 65536: exact in float32)
       ++round;
       if (n >= top_k) tau = t;
     }
@@ -2231,7 +2208,7 @@ __global__ __launch_bounds__(256) void beam_part_kernel(BeamArgs ba) {
   } else {
     for (int v = v0 + tid; v < v1; v += 256) rm = fmaxf(rm, lg[v]);
   }
-  rm = wave_max(rm);
+  rm = tw_wave_max(rm);
   if (lane == 0) red_raw[0][wave] = rm;
   __syncthreads();
   rm = fmaxf(fmaxf(red_raw[0][0], red_raw[0][1]), fmaxf(red_raw[0][2], red_raw[0][3]));
@@ -2243,7 +2220,7 @@ __global__ __launch_bounds__(256) void beam_part_kernel(BeamArgs ba) {
   } else {
     for (int v = v0 + tid; v < v1; v += 256) rs += expf(lg[v] - rm);
   }
-  rs = wave_sum(rs);
+  rs = tw_wave_sum(rs);
   if (lane == 0) red_raw[1][wave] = rs;
   __syncthreads();
   rs = ((red_raw[1][0] + red_raw[1][1]) + red_raw[1][2]) + red_raw[1][3];
@@ -2339,8 +2316,8 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(BeamArgs ba) {
     const BeamPartial* pp = ba.parts + r * SAMPLER_NS_MAX + (lane & 31);
     const bool on = lane < 32;
     const float pm = on ? pp->raw_m : -INFINITY;
-    const float M = wave_max(pm);
-    const float S = wave_sum(pm > -INFINITY ? pp->raw_s * expf(pm - M) : 0.f);
+    const float M = tw_wave_max(pm);
+    const float S = tw_wave_sum(pm > -INFINITY ? pp->raw_s * expf(pm - M) : 0.f);
     const float logZ = logf(S);
     const float acc = ba.run_score[r];
     const bool is_ts = lane >= 32;
@@ -2782,104 +2759,87 @@ hipError_t launch_gemv(int dtype, const GemvArgs& a, hipStream_t st) {
   return dtype == 1 ? gemv_b<bf16_t>(a, st) : (dtype == 2 ? gemv_b<f16_t>(a, st) : gemv_b<float>(a, st));
 }
 
+// key_bound: an upper bound of pos+1 for this call known on the host (prompt + max new tokens); ragged: of the ABSOLUTE position, a
+// row position is never behind it, so the bucket is the plain launch's
+template <typename MAP>
+static hipError_t dec_self_attn_go(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H, int key_bound,
+                                   const DecState* stt, typename MAP::Arg map_arg, hipStream_t st) {
+  const int kb = (key_bound + 63) / 64 * 64;
+  if (rows % 64 != 0 || rows > 512 || kb > rows) return hipErrorInvalidValue;
+  TW_DISPATCH3(dtype, TT, return tw_with_int<1, 2, 4>(kb <= 64 ? 1 : (kb <= 128 ? 2 : 4), [&](auto nw) {
+    // 1 / 2 wavefronts are single-round-trip kernels; 4 wavefronts: single up to 256 keys
+    return tw_with_bool(nw() < 4 || kb <= 256, [&](auto single) {
+      if constexpr (nw() == 4 || single()) {
+        hipLaunchKernelGGL((dec_self_attn_kernel<TT, single(), nw(), MAP>), dim3(H, B), dim3(nw() * 64), 0, st, (const TT*)q,
+                           (const TT*)kc, (const TT*)vc, rows, H, kb, (TT*)out, stt, map_arg);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;   // not reached
+      }
+    });
+  }));
+}
+
 hipError_t launch_dec_self_attn(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H,
                                 int key_bound, const DecState* stt, int rows_streams, hipStream_t st) {
-  // key_bound: an upper bound of pos+1 for this call known on the host (prompt + max new tokens)
-  int kb = (key_bound + 63) / 64 * 64;
-  if (rows % 64 != 0 || rows > 512 || kb > rows) return hipErrorInvalidValue;
-  const bool single = kb <= 256;
-  const int nw = kb <= 64 ? 1 : (kb <= 128 ? 2 : 4);
-#define SA_GO(TT, SV, NWV) hipLaunchKernelGGL((dec_self_attn_kernel<TT, SV, NWV>), dim3(H, B), dim3(NWV * 64), 0, st, (const TT*)q, \
-                                              (const TT*)kc, (const TT*)vc, rows, H, kb, (TT*)out, stt, rows_streams)
-#define SA_PICK(TT) do { if (nw == 1) SA_GO(TT, true, 1); else if (nw == 2) SA_GO(TT, true, 2); else if (single) SA_GO(TT, true, 4); \
-                         else SA_GO(TT, false, 4); } while (0)
-  if (dtype == 1) SA_PICK(bf16_t); else if (dtype == 2) SA_PICK(f16_t); else SA_PICK(float);
-#undef SA_PICK
-#undef SA_GO
-  return hipGetLastError();
+  return dec_self_attn_go<AttnRowsMap>(dtype, q, kc, vc, rows, out, B, H, key_bound, stt, rows_streams, st);
 }
 
 hipError_t launch_dec_self_attn_ragged(int dtype, const void* q, const void* kc, const void* vc, int rows, void* out, int B, int H,
                                        int key_bound, const DecState* stt, const int* n_pad, hipStream_t st) {
-  // the bucket is the plain launch's, picked from the ABSOLUTE position: a row position is never behind it
-  int kb = (key_bound + 63) / 64 * 64;
-  if (rows % 64 != 0 || rows > 512 || kb > rows || !n_pad || B < 1 || B > 64) return hipErrorInvalidValue;
-  const bool single = kb <= 256;
-  const int nw = kb <= 64 ? 1 : (kb <= 128 ? 2 : 4);
-#define SA_GO(TT, SV, NWV) hipLaunchKernelGGL((dec_self_attn_ragged_kernel<TT, SV, NWV>), dim3(H, B), dim3(NWV * 64), 0, st, (const TT*)q, \
-                                              (const TT*)kc, (const TT*)vc, rows, H, kb, (TT*)out, stt, n_pad)
-#define SA_PICK(TT) do { if (nw == 1) SA_GO(TT, true, 1); else if (nw == 2) SA_GO(TT, true, 2); else if (single) SA_GO(TT, true, 4); \
-                         else SA_GO(TT, false, 4); } while (0)
-  if (dtype == 1) SA_PICK(bf16_t); else if (dtype == 2) SA_PICK(f16_t); else SA_PICK(float);
-#undef SA_PICK
-#undef SA_GO
-  return hipGetLastError();
+  if (!n_pad || B < 1 || B > 64) return hipErrorInvalidValue;
+  return dec_self_attn_go<AttnRaggedMap>(dtype, q, kc, vc, rows, out, B, H, key_bound, stt, n_pad, st);
 }
 
+// Every check on a cross-attention launch is made here; the sub-launchers of the other translation units assume them.
 hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
                                  int beam_clips, hipStream_t st, int* grid3) {
   if (Tp % 64 != 0 || Tp < T || beam_clips < 0) return hipErrorInvalidValue;
-  if (grid3) { grid3[0] = H; grid3[1] = B; grid3[2] = 1; }   // one workgroup per (head, row) unless a rows flavour is picked below
-  const bool single = Tp <= 512;
+  if (grid3) { grid3[0] = H; grid3[1] = B; grid3[2] = 1; }   // one workgroup per (head, row) unless a rows flavour or the beams mode is picked below
   const bool f = fq.u != nullptr;
   if (f) {   // the partial statistics must fit the per-lane request budget of fq_request
     if (!fq.stats || !fq.gw || !fq.cb || fq.d != H * 64 || fq.n_part < 1 || fq.n_part > 192) return hipErrorInvalidValue;
   } else if (!q) {
     return hipErrorInvalidValue;
   }
-  if (ksc || vsc) {  // fp8 K / V^T caches with per-key scales (MXFP8 contexts: bf16 or - TW_F16_W8A16 - float16 activations)
-    if (!ksc || !vsc || (dtype != 1 && dtype != 2) || beam_clips > 0) return hipErrorInvalidValue;   // (no beams mode for fp8 caches)
-    if (rows_streams > 0 && B > rows_streams)   // several positions per stream: one e4m3 K / V^T pass per (stream, head, 16 positions)
-      return launch_dec_cross_attn_kv8_rows(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, ksc, vsc, rows_streams,
-                                            st, grid3);
-    const size_t lds8 = (size_t)Tp * sizeof(float) * 2;
-#define CA8_GO(TT, GV, FV) hipLaunchKernelGGL((dec_cross_attn_kv8_kernel<TT, GV, FV>), dim3(H, B), dim3(512), lds8, st,                \
-                                          (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, (const TT*)q,  \
-                                          (TT*)out, align_slot_for_head, align, Ha, P, stt, fq)
-#define CA8_PICK(TT, FV) do { if (Tp <= 512) CA8_GO(TT, 1, FV); else if (Tp <= 1024) CA8_GO(TT, 2, FV); else if (Tp <= 1536) CA8_GO(TT, 3, FV); \
-                              else return hipErrorInvalidValue; } while (0)
-    if (dtype == 1) { if (f) CA8_PICK(bf16_t, true); else CA8_PICK(bf16_t, false); }
-    else { if (f) CA8_PICK(f16_t, true); else CA8_PICK(f16_t, false); }
-#undef CA8_PICK
-#undef CA8_GO
-    return hipGetLastError();
-  }
-  if (beam_clips > 0 && rows_streams == 0 && B > beam_clips)   // a beam step: one K / V^T pass per (clip, head) for the clip's beams
-    return launch_dec_cross_attn_beams(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, beam_clips, st, grid3);
-  if (rows_streams > 0 && B > rows_streams) {   // several positions per stream: one K / V^T pass per (stream, head, 16 positions)
-    if (B % rows_streams != 0 || Tp > 1536) return hipErrorInvalidValue;
-    const int n_pos = B / rows_streams;
-    const dim3 grid(H, rows_streams, (n_pos + 15) / 16);
-    if (grid3) { grid3[1] = rows_streams; grid3[2] = (n_pos + 15) / 16; }
-    const size_t esz = dtype == 0 ? 4 : 2;
-    const size_t ldsr = ((size_t)16 * (Tp + 4) + 8 * 16 * 68 + 2 * 8 * 16) * sizeof(float) + 16 * 64 * esz;
-    constexpr int lds_cap = 16 * (1536 + 4) * 4 + 8 * 16 * 68 * 4 + 2 * 8 * 16 * 4 + 16 * 64 * 4;
-    static_assert(lds_cap <= 160 * 1024, "LDS of a compute unit");
-#define CAR_GO(TT, SV, FV) do {                                                                                                        \
-      static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_cross_attn_rows_kernel<TT, SV, FV>),       \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);                        \
-      if (attr != hipSuccess) return attr;                                                                                             \
-      hipLaunchKernelGGL((dec_cross_attn_rows_kernel<TT, SV, FV>), grid, dim3(512), ldsr, st, (const TT*)ck, (const TT*)cv, H, Tp, T,  \
-                         rows_streams, n_pos, (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq);                     \
-    } while (0)
-#define CAR_PICK(TT) do { if (single) { if (f) CAR_GO(TT, true, true); else CAR_GO(TT, true, false); }                               \
-                          else { if (f) CAR_GO(TT, false, true); else CAR_GO(TT, false, false); } } while (0)
-    if (dtype == 1) CAR_PICK(bf16_t); else if (dtype == 2) CAR_PICK(f16_t); else CAR_PICK(float);
-#undef CAR_PICK
-#undef CAR_GO
-    return hipGetLastError();
-  }
-  const size_t lds = (size_t)Tp * sizeof(float);
-#define CA_GO(TT, SV, FV) hipLaunchKernelGGL((dec_cross_attn_kernel<TT, SV, FV>), dim3(H, B), dim3(512), lds, st, (const TT*)ck,      \
-                                             (const TT*)cv, H, Tp, T, rows_streams, (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq)
-#define CA_PICK(TT) do { if (single) { if (f) CA_GO(TT, true, true); else CA_GO(TT, true, false); }                                  \
-                         else { if (f) CA_GO(TT, false, true); else CA_GO(TT, false, false); } } while (0)
-  if (dtype == 1) CA_PICK(bf16_t); else if (dtype == 2) CA_PICK(f16_t); else CA_PICK(float);
-#undef CA_PICK
-#undef CA_GO
-  return hipGetLastError();
+  const bool fp8 = ksc || vsc;   // fp8 K / V^T caches with per-key scales (MXFP8 contexts: bf16 or - TW_F16_W8A16 - float16 activations)
+  if (fp8 && (!ksc || !vsc || (dtype != 1 && dtype != 2) || beam_clips > 0 || Tp > 1536)) return hipErrorInvalidValue;   // (no beams mode for fp8 caches)
+  const bool beams = !fp8 && beam_clips > 0 && rows_streams == 0 && B > beam_clips;   // a beam step: one K / V^T pass per (clip, head)
+  const bool rows = !beams && rows_streams > 0 && B > rows_streams;   // several positions per stream: one pass per (stream, head, 16 positions)
+  if (beams && (B % beam_clips != 0 || B / beam_clips > kBeamMax || B / beam_clips < 2 || Tp > 1536 || dtype < 0 || dtype > 2))
+    return hipErrorInvalidValue;
+  if (rows && (B % rows_streams != 0 || Tp > 1536)) return hipErrorInvalidValue;
+  const int n_pos = rows ? B / rows_streams : 0;
+  const dim3 grid = beams ? dim3(H, beam_clips, 1) : (rows ? dim3(H, rows_streams, (n_pos + 15) / 16) : dim3(H, B, 1));
+  if (grid3 && (beams || rows)) { grid3[1] = grid.y; grid3[2] = grid.z; }
+  if (beams) return launch_dec_cross_attn_beams(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, beam_clips, st);
+  if (fp8 && rows)
+    return launch_dec_cross_attn_kv8_rows(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, ksc, vsc, rows_streams, st);
+  if (fp8)
+    return tw_with_bool(dtype == 1, [&](auto is_bf16) {
+      using TT = std::conditional_t<is_bf16(), bf16_t, f16_t>;
+      return tw_with_int<1, 2, 3>(Tp <= 512 ? 1 : (Tp <= 1024 ? 2 : 3), [&](auto g) {
+        return tw_with_bool(f, [&](auto fv) {
+          hipLaunchKernelGGL((dec_cross_attn_kv8_kernel<TT, g(), fv()>), grid, dim3(512), (size_t)Tp * sizeof(float) * 2, st,
+                             (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, (const TT*)q, (TT*)out,
+                             align_slot_for_head, align, Ha, P, stt, fq);
+          return hipGetLastError();
+        });
+      });
+    });
+  TW_DISPATCH3(dtype, TT, return tw_with_bool(Tp <= 512, [&](auto single) {
+    return tw_with_bool(f, [&](auto fv) {
+      if (rows)   // one cap for the three element types
+        return tw_launch_big_lds<&dec_cross_attn_rows_kernel<TT, single(), fv()>, RowsLds<16, 4>::cap>(
+            grid, dim3(512), RowsLds<16, (int)sizeof(TT)>::bytes(Tp), st, (const TT*)ck, (const TT*)cv, H, Tp, T, rows_streams, n_pos,
+            (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq);
+      hipLaunchKernelGGL((dec_cross_attn_kernel<TT, single(), fv()>), grid, dim3(512), (size_t)Tp * sizeof(float), st, (const TT*)ck,
+                         (const TT*)cv, H, Tp, T, rows_streams, (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq);
+      return hipGetLastError();
+    });
+  }));
 }
 
 hipError_t launch_sampler(const SamplerArgs& a0, hipStream_t st) {

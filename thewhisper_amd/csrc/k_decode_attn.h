@@ -1,6 +1,9 @@
-// Device helpers shared by the decode kernels of k_decode.hip and k_decode_kv8_rows.hip: operand packing, the MFMA wrapper, the e4m3
-// widening and the fused cross-attention query.  Each translation unit gets its own copies (anonymous namespace, all forceinline).
+// Device helpers shared by the decode kernels of k_decode.hip, k_decode_kv8_rows.hip and k_decode_beam_cross.hip: operand packing, the
+// MFMA wrapper, the e4m3 widening, the fused cross-attention query, the shared pieces of the attention kernels (row map, LDS layout
+// of the rows flavours) and the launchers' dispatch helpers.  Each translation unit gets its own
+// copies (anonymous namespace, device code all forceinline).
 #pragma once
+#include <type_traits>
 #include "tw_common.h"
 
 namespace {
@@ -106,8 +109,60 @@ __device__ __forceinline__ void fq_finish(const QRaw<T>& r, const FusedQ& fq, in
   qrow[lane] = tw_cast<T>(tw_ln_apply(r.u, mean, rstd, r.gw, r.cb));
 }
 
+// ---- pieces shared by the attention kernels (dec_self_attn, dec_cross_attn and their kv8 / rows / beams flavours) ----
+
+// attn_row_map: launch row b -> the stream whose cache it attends to and the number of keys it sees.  Two policies; the trailing
+// kernel argument is the policy's Arg.
+//  * AttnRowsMap (int rows_streams): 0 = plain, row b is stream b at stt->pos; > 0 = rows mode (prefill), row b is position
+//    pos + b / rows_streams of stream b % rows_streams (causal inside the launch).  The addresses depend on kernel arguments only.
+//  * AttnRaggedMap (const int* n_pad; tw_common.h: tw_row_pos): stream b sees the keys [0, q] of its ROW position q <= pos < key_bound;
+//    the keys between q and the bucket's end are masked like the ones behind pos, and masked keys contribute exact zeros.
+struct AttnRowsMap {
+  using Arg = int;
+  static __device__ __forceinline__ int stream(int b, int rs) { return rs > 0 ? b % rs : b; }
+  static __device__ __forceinline__ int pos(int p, int b, int rs) { return p + (rs > 0 ? b / rs : 0); }
+};
+struct AttnRaggedMap {
+  using Arg = const int* __restrict__;
+  static __device__ __forceinline__ int stream(int b, const int*) { return b; }
+  static __device__ __forceinline__ int pos(int p, int b, const int* n_pad) { return tw_row_pos(p, n_pad[b]); }
+};
+
 // Score rows (= columns that are computed to the end) of the beams mode below: a clip has at most kBeamMax = 8 beams
 constexpr int kBeamCols = 8;
+
+// LDS (dynamic) of the rows and beams flavours, 8 wavefronts, NC columns, query elements of ESZ bytes:
+//   scores float[NC][Tp + 4] | partial context vectors float[8][NC][68] | column max float[8][16] | normaliser float[8][NC] |
+//   query rows [NC][64] x ESZ.  Offsets in floats from the start: the launchers size the launch and the cap from it, the kernels carve
+//   their pointers as one chain in this order.
+template <int NC, int ESZ>
+struct RowsLds {
+  static constexpr int NW = 8, WS = 68;
+  static constexpr __host__ __device__ int wo(int Tp) { return NC * (Tp + 4); }
+  static constexpr __host__ __device__ int redm(int Tp) { return wo(Tp) + NW * NC * WS; }
+  static constexpr __host__ __device__ int wl(int Tp) { return redm(Tp) + NW * 16; }
+  static constexpr __host__ __device__ int qst(int Tp) { return wl(Tp) + NW * NC; }
+  static constexpr __host__ __device__ size_t bytes(int Tp) { return (size_t)qst(Tp) * sizeof(float) + NC * 64 * ESZ; }
+  static constexpr int cap = (int)bytes(1536);   // Tp <= 1536: launch_dec_cross_attn
+  static_assert(cap <= 160 * 1024, "LDS of a compute unit");
+};
+
+// ---- launcher side ----
+// a run-time bool / small int as a compile-time constant: f(std::bool_constant) / f(std::integral_constant), which returns hipError_t
+template <typename F> hipError_t tw_with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Vs, typename F> hipError_t tw_with_int(int v, F&& f) {
+  hipError_t e = hipErrorInvalidValue;   // v is none of Vs
+  (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return e;
+}
+// launch a kernel whose dynamic LDS exceeds the 64-KiB default: the attribute is set once per instantiation
+template <auto Kernel, int Cap, typename... A>
+hipError_t tw_launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Cap);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
 
 // Rows flavour of dec_cross_attn_kernel (rows mode with more than one position per stream: prefill_core, verify_round,
 // tw_score_tokens).  One workgroup per (stream, head, group of up to 16 of the stream's positions): column j of the MFMA B operands
@@ -118,8 +173,7 @@ constexpr int kBeamCols = 8;
 // in index order; probabilities rounded by pack16 before P.V; partial context vectors added over the wavefronts in index order,
 // then x 1/L - so a row's bits are the one-position step's.  Columns behind the group's last position repeat that position and are
 // not written.
-// LDS (dynamic): scores float[16][Tp + 4] | partial context vectors float[8][16][68] | column max float[8][16] | normaliser
-// float[8][16] | query rows T[16][64]: 71 KiB at Tp = 512 (two workgroups per CU), 135 KiB at Tp = 1536 (one).
+// LDS (dynamic): RowsLds<16, sizeof(T)> - 71 KiB at Tp = 512 (two workgroups per CU), 135 KiB at Tp = 1536 (one).
 //
 // BEAMS (a step of tw_generate_beam; grid (heads, n_clips, 1), rows_streams = n_clips, n_pos = K <= kBeamCols): the columns of a
 // workgroup are not consecutive positions of a stream but the K beams of clip `srow` at the SAME position.  Beam j is launch row
@@ -143,7 +197,7 @@ __global__ __launch_bounds__(512) void dec_cross_attn_rows_kernel(const T* __res
   constexpr int E = ElemTraits<T>::kPer16B;
   constexpr int DS = 64 / (4 * E);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int S = Tp + 4;
+  const int S = Tp + 4;                         // carved in the order of RowsLds<NC, sizeof(T)>
   float* sc = reinterpret_cast<float*>(smem);   // [NC][S] scores -> unnormalised probabilities
   float* wo = sc + NC * S;                      // [NW][NC][WS]
   float* redm = wo + NW * NC * WS;              // [NW][16]

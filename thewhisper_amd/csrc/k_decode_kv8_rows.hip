@@ -21,8 +21,7 @@ namespace {
 // keys kq * 16 .. + 15 of each of its groups in registers (one 16-byte request per group, the same for the 16 columns).
 // Columns behind the group's last position repeat that position's query, stop behind the scores (no exponentials, no normaliser:
 // a column of an MFMA depends on its own B column only) and are not written.
-// LDS (dynamic): scores float[16][Tp + 4] | partial context vectors float[8][16][68] | column max float[8][16] | normaliser
-// float[8][16] | query rows T[16][64]: 69.3 KiB at Tp = 512 (two workgroups per CU), 133.3 KiB at Tp = 1536 (one).
+// LDS (dynamic): RowsLds<16, 2> (k_decode_attn.h) - 69.3 KiB at Tp = 512 (two workgroups per CU), 133.3 KiB at Tp = 1536 (one).
 template <typename T, int G, bool FQ>
 __global__ __launch_bounds__(512) void dec_cross_attn_kv8_rows_kernel(const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                        const unsigned char* __restrict__ ksc,
@@ -35,7 +34,7 @@ __global__ __launch_bounds__(512) void dec_cross_attn_kv8_rows_kernel(const unsi
   constexpr bool kPvUp = ElemTraits<T>::kCode == 2;   // float16: the P.V operand is carried times 2^7 (attn_mfma_block_kv8)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   asm volatile("" ::"s"(ck), "s"(cv), "s"(ksc), "s"(vsc), "s"(H), "s"(Tp), "s"(Tlen), "s"(rows_streams), "s"(n_pos));
-  const int S = Tp + 4;
+  const int S = Tp + 4;                         // carved in the order of RowsLds<16, 2>
   float* sc = reinterpret_cast<float*>(smem);   // [16][S] scores -> unnormalised probabilities
   float* wo = sc + 16 * S;                      // [NW][16][WS]
   float* redm = wo + NW * 16 * WS;              // [NW][16]
@@ -208,30 +207,22 @@ __global__ __launch_bounds__(512) void dec_cross_attn_kv8_rows_kernel(const unsi
 
 }  // namespace
 
-// The checks on Tp, the FusedQ block and the scale pointers are launch_dec_cross_attn's, which is the only caller.
+// Reached through launch_dec_cross_attn only, which has made every check (dtype 1 or 2, B a multiple of rows_streams, Tp <= 1536)
+// and reports the grid.
 hipError_t launch_dec_cross_attn_kv8_rows(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                           int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
-                                          const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st, int* grid3) {
-  if (rows_streams < 1 || B % rows_streams != 0 || Tp > 1536 || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
-  const bool f = fq.u != nullptr;
+                                          const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st) {
   const int n_pos = B / rows_streams;
   const dim3 grid(H, rows_streams, (n_pos + 15) / 16);
-  const size_t ldsr = ((size_t)16 * (Tp + 4) + 8 * 16 * 68 + 2 * 8 * 16) * sizeof(float) + 16 * 64 * 2;
-  constexpr int lds_cap = 16 * (1536 + 4) * 4 + 8 * 16 * 68 * 4 + 2 * 8 * 16 * 4 + 16 * 64 * 2;
-  static_assert(lds_cap <= 160 * 1024, "LDS of a compute unit");
-#define CA8R_GO(TT, GV, FV) do {                                                                                                       \
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_cross_attn_kv8_rows_kernel<TT, GV, FV>),     \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);                          \
-    if (attr != hipSuccess) return attr;                                                                                               \
-    hipLaunchKernelGGL((dec_cross_attn_kv8_rows_kernel<TT, GV, FV>), grid, dim3(512), ldsr, st, (const unsigned char*)ck,              \
-                       (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, n_pos, (const TT*)q, (TT*)out,                      \
-                       align_slot_for_head, align, Ha, P, stt, fq);                                                                    \
-  } while (0)
-#define CA8R_PICK(TT, FV) do { if (Tp <= 512) CA8R_GO(TT, 1, FV); else if (Tp <= 1024) CA8R_GO(TT, 2, FV); else CA8R_GO(TT, 3, FV); } while (0)
-  if (dtype == 1) { if (f) CA8R_PICK(bf16_t, true); else CA8R_PICK(bf16_t, false); }
-  else { if (f) CA8R_PICK(f16_t, true); else CA8R_PICK(f16_t, false); }
-#undef CA8R_PICK
-#undef CA8R_GO
-  if (grid3) { grid3[0] = H; grid3[1] = rows_streams; grid3[2] = (n_pos + 15) / 16; }
-  return hipGetLastError();
+  using Lds = RowsLds<16, 2>;
+  return tw_with_bool(dtype == 1, [&](auto is_bf16) {   // fp8 caches: bf16 or float16 activations
+    using TT = std::conditional_t<is_bf16(), bf16_t, f16_t>;
+    return tw_with_int<1, 2, 3>(Tp <= 512 ? 1 : (Tp <= 1024 ? 2 : 3), [&](auto g) {
+      return tw_with_bool(fq.u != nullptr, [&](auto f) {
+        return tw_launch_big_lds<&dec_cross_attn_kv8_rows_kernel<TT, g(), f()>, Lds::cap>(
+            grid, dim3(512), Lds::bytes(Tp), st, (const unsigned char*)ck, (const unsigned char*)cv, ksc, vsc, H, Tp, T, rows_streams, n_pos,
+            (const TT*)q, (TT*)out, align_slot_for_head, align, Ha, P, stt, fq);
+      });
+    });
+  });
 }

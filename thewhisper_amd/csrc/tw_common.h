@@ -272,7 +272,7 @@ hipError_t launch_embed(int dtype, const int* ids, const DecState* stt, const vo
 // padding, and the stream at absolute position p is at ROW position q = p - n_pad[b] - its positional row, its self-attention cache slot
 // and its key range [0, q] - or idles at row position 0 while p < n_pad[b].  n_pad: int32 [64] in context-owned device memory.  Only
 // the three kernels that read a stream's own position take the table, each as an instantiation of its own (embed_ragged_kernel, the
-// RAG flavours of skinny_mfma_kernel's SK_KV epilogue and of dec_self_attn_kernel): the launches of every other call are as before.
+// RAG flavour of skinny_mfma_kernel's SK_KV epilogue and dec_self_attn_kernel's AttnRaggedMap): the launches of every other call are as before.
 __device__ __forceinline__ int tw_row_pos(int p, int n_pad) { return p > n_pad ? p - n_pad : 0; }
 // x[b] = tok_emb[ids[b]] + pos_emb[tw_row_pos(pos, n_pad[b])]   (ordinary step only)
 hipError_t launch_embed_ragged(int dtype, const int* ids, const DecState* stt, const int* n_pad, const void* tok, const void* pos,
@@ -345,14 +345,14 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
                                  int beam_clips, hipStream_t st, int* grid3 = nullptr);
-// its beams mode (k_decode_beam_cross.hip): reached through launch_dec_cross_attn only, which has checked the arguments
+// its beams mode (k_decode_beam_cross.hip): reached through launch_dec_cross_attn only, which makes every check and reports the grid
 hipError_t launch_dec_cross_attn_beams(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                        int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
-                                       int n_clips, hipStream_t st, int* grid3);
-// its rows flavour for the fp8 caches (k_decode_kv8_rows.hip): reached through launch_dec_cross_attn only, which has checked the arguments
+                                       int n_clips, hipStream_t st);
+// its rows flavour for the fp8 caches (k_decode_kv8_rows.hip): likewise
 hipError_t launch_dec_cross_attn_kv8_rows(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                           int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
-                                          const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st, int* grid3);
+                                          const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st);
 // load-time composition for "cross query ahead": out[n][k] = sum_j A[n][j] Bm[j][k] (row-major, T), c0[n] = sum_j A[n][j] bvec[j]
 hipError_t launch_compose(int dtype, const void* A, const void* Bm, const void* bvec, void* out, float* c0, int N, int J, int K,
                           hipStream_t st);

@@ -52,7 +52,8 @@ enum { TW_F32 = 0, TW_BF16 = 1, TW_F16 = 2,
                             RNE_f16(e4m3 x 2^(sb-127)), a pure function of the stored bytes.  That product is exact whenever the
                             block's largest magnitude is >= 2^-8; in a block of smaller weights an element below the float16
                             normal range (2^-14) is rounded to the subnormal grid (|error| <= 2^-25) and one below 2^-25 becomes
-                            zero.  Up to 64 streams; d_model and ffn multiples of 128; no beam search */ };
+                            zero.  Up to 64 streams; d_model and ffn multiples of 128.  The one fp8 context with beam search
+                            (tw_generate_beam) */ };
 
 /* error codes */
 enum {
@@ -504,7 +505,8 @@ int tw_generate_sample_filtered(tw_ctx* ctx, int32_t B, const int32_t* prompt_ho
  * the larger logit is listed first (the rule says the lower id); real ties between equal logits follow the rule.
  *
  * Rows: beam k of clip c is launch row k * n_clips + c and reads the cross K / V^T of slot c - one pass over a clip's K / V^T per
- * (layer, head, step) serves all of its beams.  No cross-K/V slot is written, and slots n_clips .. keep what tw_cross_kv(_at) /
+ * (layer, head, step) serves all of its beams (a TW_F16_W8A16 context: over the clip's e4m3 K / V^T and their scale bytes, half the
+ * bytes of the float16 caches plus one byte per key).  No cross-K/V slot is written, and slots n_clips .. keep what tw_cross_kv(_at) /
  * tw_adopt_cross_kv put there: afterwards the context holds every slot as it was (tw_score_tokens and further tw_generate_* calls
  * need no re-encoding, for the clips and for whatever the slots behind them hold).  The self-attention caches, the sequence state
  * and the alignment rows of rows 0 .. n_clips * K - 1 are overwritten, as by any decode over that many rows.  A step is the
@@ -520,7 +522,8 @@ int tw_generate_sample_filtered(tw_ctx* ctx, int32_t B, const int32_t* prompt_ho
  * is pad_id.
  * TW_ESTATE: tw_encode + tw_cross_kv did not fill n_clips slots.  TW_EINVAL, before any work is enqueued (the context stays usable):
  * num_beams outside 2 .. 8, n_clips * num_beams above max_batch or above 64, a NaN or infinite length_penalty, early_stopping outside
- * {0, 1}, want_alignment / n_forced / n_draft set, a TW_BF16_MXFP8 / TW_BF16_W8A16 context, a context whose target_positions exceed
+ * {0, 1}, want_alignment / n_forced / n_draft set, a TW_BF16_MXFP8 / TW_BF16_W8A16 context (the bf16-based fp8 contexts have no beams
+ * mode of their cross attention; TW_F16_W8A16 is served), a context whose target_positions exceed
  * 512 (the histories a workgroup holds), tw_generate_greedy's own refusals. */
 typedef struct tw_beam_opts { int32_t num_beams; float length_penalty; int32_t early_stopping; } tw_beam_opts;   /* 2..8, finite, 0 | 1 */
 int tw_generate_beam(tw_ctx* ctx, int32_t n_clips, const int32_t* prompt_host /*[n_clips, n_prompt]*/, int32_t n_prompt,
@@ -582,7 +585,8 @@ int tw_last_prompt_rows(tw_ctx* ctx, int32_t* launches, int32_t* positions);
  * (batched prefill, prompt as rows, a verify launch, tw_score_tokens) reads (heads, streams, ceil(positions / 16)) in every dtype, the
  * fp8 contexts included: one pass over a stream's K / V^T serves up to 16 of its positions.  A generate call ends with one-position
  * steps, so the rows form is read behind a call that ends with a rows launch, such as tw_score_tokens.  A step of tw_generate_beam(_aligned),
- * the prompt steps included, reads (heads, n_clips, 1): one workgroup per head and CLIP serves the clip's num_beams rows. */
+ * the prompt steps included, reads (heads, n_clips, 1): one workgroup per head and CLIP serves the clip's num_beams rows, in a
+ * TW_F16_W8A16 context too. */
 int tw_last_cross_grid(tw_ctx* ctx, int32_t* grid3);
 
 /* Token log-probabilities and the no-speech probability of FINISHED sequences, by a teacher-forced re-scoring pass.  Replaces: the

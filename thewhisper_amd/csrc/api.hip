@@ -1850,7 +1850,8 @@ static int generate_beam_checked(const char* fn, bool aligned_entry, tw_ctx* c, 
   if (o->want_alignment != 0 && o->want_alignment != 1) return fail(c, TW_EINVAL, "%s: want_alignment %d outside {0, 1}", fn, o->want_alignment);
   const bool rec = o->want_alignment != 0;   // record the alignment rows and the ancestry; gather behind the loop
   if (rec && c->Ha == 0) return fail(c, TW_EINVAL, "%s: want_alignment but the context has no alignment heads", fn);
-  if (c->w8) return fail(c, TW_EINVAL, "%s: fp8 contexts are not supported", fn);
+  // fp8 contexts: the float16 base (TW_F16_W8A16) has a beams mode of its cross attention, the bf16-based two have none
+  if (c->w8 && c->dtype != TW_F16) return fail(c, TW_EINVAL, "%s: fp8 contexts are not supported", fn);
   if (c->P > kBeamSeqMax) return fail(c, TW_EINVAL, "%s: target_positions %d above %d", fn, c->P, kBeamSeqMax);
   if (n > c->cross_B) return fail(c, TW_ESTATE, "%s: %d clips but cross K/V holds %d", fn, n, c->cross_B);
   if (n_prompt < 1 || n_prompt >= c->P) return fail(c, TW_EINVAL, "bad n_prompt %d", n_prompt);

@@ -2805,8 +2805,10 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
     return hipErrorInvalidValue;
   }
   const bool fp8 = ksc || vsc;   // fp8 K / V^T caches with per-key scales (MXFP8 contexts: bf16 or - TW_F16_W8A16 - float16 activations)
-  if (fp8 && (!ksc || !vsc || (dtype != 1 && dtype != 2) || beam_clips > 0 || Tp > 1536)) return hipErrorInvalidValue;   // (no beams mode for fp8 caches)
-  const bool beams = !fp8 && beam_clips > 0 && rows_streams == 0 && B > beam_clips;   // a beam step: one K / V^T pass per (clip, head)
+  if (fp8 && (!ksc || !vsc || (dtype != 1 && dtype != 2) || Tp > 1536)) return hipErrorInvalidValue;
+  // (fp8 caches have a beams mode for float16 activations only, and no other way to serve a beam step)
+  if (fp8 && beam_clips > 0 && (dtype != 2 || rows_streams != 0 || B <= beam_clips)) return hipErrorInvalidValue;
+  const bool beams = beam_clips > 0 && rows_streams == 0 && B > beam_clips;   // a beam step: one K / V^T pass per (clip, head)
   const bool rows = !beams && rows_streams > 0 && B > rows_streams;   // several positions per stream: one pass per (stream, head, 16 positions)
   if (beams && (B % beam_clips != 0 || B / beam_clips > kBeamMax || B / beam_clips < 2 || Tp > 1536 || dtype < 0 || dtype > 2))
     return hipErrorInvalidValue;
@@ -2814,6 +2816,8 @@ hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, con
   const int n_pos = rows ? B / rows_streams : 0;
   const dim3 grid = beams ? dim3(H, beam_clips, 1) : (rows ? dim3(H, rows_streams, (n_pos + 15) / 16) : dim3(H, B, 1));
   if (grid3 && (beams || rows)) { grid3[1] = grid.y; grid3[2] = grid.z; }
+  if (fp8 && beams)
+    return launch_dec_cross_attn_kv8_beams(q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, ksc, vsc, beam_clips, st);
   if (beams) return launch_dec_cross_attn_beams(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, beam_clips, st);
   if (fp8 && rows)
     return launch_dec_cross_attn_kv8_rows(dtype, q, fq, ck, cv, out, B, H, T, Tp, align_slot_for_head, align, Ha, P, stt, ksc, vsc, rows_streams, st);

@@ -1,4 +1,4 @@
-// Device helpers shared by the decode kernels of k_decode.hip, k_decode_kv8_rows.hip and k_decode_beam_cross.hip: operand packing, the
+// Device helpers shared by the decode kernels of k_decode.hip, k_decode_kv8_rows.hip, k_decode_kv8_beams.hip and k_decode_beam_cross.hip: operand packing, the
 // MFMA wrapper, the e4m3 widening, the fused cross-attention query, the shared pieces of the attention kernels (row map, LDS layout
 // of the rows flavours) and the launchers' dispatch helpers.  Each translation unit gets its own
 // copies (anonymous namespace, device code all forceinline).

@@ -8,8 +8,8 @@
 static_assert(kBeamMax <= kBeamCols, "a clip's beams are the columns of one workgroup");
 
 // Reached through launch_dec_cross_attn only, which has made every check (2 <= B / n_clips <= kBeamMax, Tp <= 1536) and reports the
-// grid.  B = n_clips * K rows, beam k of clip c = row k * n_clips + c; fp8 caches have no beams mode (tw_generate_beam refuses fp8
-// contexts).  One cap for the three element types.
+// grid.  B = n_clips * K rows, beam k of clip c = row k * n_clips + c; the fp8 caches' beams kernel is k_decode_kv8_beams.hip's.
+// One cap for the three element types.
 hipError_t launch_dec_cross_attn_beams(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                        int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
                                        int n_clips, hipStream_t st) {

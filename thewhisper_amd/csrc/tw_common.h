@@ -337,10 +337,10 @@ struct FusedQ {
 };
 // grid3 non-null: receives the x, y, z workgroup counts of the launch - (H, B, 1), or (H, rows_streams, ceil(positions / 16)) where a rows
 // flavour serves it (rows_streams > 0 and B > rows_streams: dec_cross_attn_rows_kernel, dec_cross_attn_kv8_rows_kernel)
-// beam_clips > 0 (with rows_streams == 0, B > beam_clips, no fp8 caches): a step of tw_generate_beam - the B rows are beam_clips clips
-// x B / beam_clips <= kBeamMax beams, beam k of clip c = row k * beam_clips + c, and every row of clip c attends to the K / V^T of
-// SLOT c, read once per (head, clip) by the beams mode of dec_cross_attn_rows_kernel; its alignment row goes to (row, pos); grid3
-// reads (H, beam_clips, 1).  0: not a beam step
+// beam_clips > 0 (with rows_streams == 0, B > beam_clips; fp8 caches: float16 activations only): a step of tw_generate_beam - the B
+// rows are beam_clips clips x B / beam_clips <= kBeamMax beams, beam k of clip c = row k * beam_clips + c, and every row of clip c
+// attends to the K / V^T of SLOT c, read once per (head, clip) by the beams mode of dec_cross_attn_rows_kernel (fp8 caches:
+// dec_cross_attn_kv8_beams_kernel); its alignment row goes to (row, pos); grid3 reads (H, beam_clips, 1).  0: not a beam step
 hipError_t launch_dec_cross_attn(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                  int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P,
                                  const DecState* stt, const unsigned char* ksc, const unsigned char* vsc, int rows_streams,
@@ -353,6 +353,10 @@ hipError_t launch_dec_cross_attn_beams(int dtype, const void* q, const FusedQ& f
 hipError_t launch_dec_cross_attn_kv8_rows(int dtype, const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H,
                                           int T, int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
                                           const unsigned char* ksc, const unsigned char* vsc, int rows_streams, hipStream_t st);
+// its beams mode for the fp8 caches, float16 activations (k_decode_kv8_beams.hip): likewise
+hipError_t launch_dec_cross_attn_kv8_beams(const void* q, const FusedQ& fq, const void* ck, const void* cv, void* out, int B, int H, int T,
+                                           int Tp, const int* align_slot_for_head, float* align, int Ha, int P, const DecState* stt,
+                                           const unsigned char* ksc, const unsigned char* vsc, int n_clips, hipStream_t st);
 // load-time composition for "cross query ahead": out[n][k] = sum_j A[n][j] Bm[j][k] (row-major, T), c0[n] = sum_j A[n][j] bvec[j]
 hipError_t launch_compose(int dtype, const void* A, const void* Bm, const void* bvec, void* out, float* c0, int N, int J, int K,
                           hipStream_t st);

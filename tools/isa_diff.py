@@ -24,7 +24,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Tuple
 
-DEFAULT_FILES = ["k_decode.hip", "k_decode_kv8_rows.hip", "k_decode_beam_cross.hip"]
+DEFAULT_FILES = ["k_decode.hip", "k_decode_kv8_rows.hip", "k_decode_kv8_beams.hip", "k_decode_beam_cross.hip"]
 _LABEL = re.compile(r"\.L[A-Za-z_]+\d+(?:_\d+)?\b")
 
 

@@ -41,7 +41,7 @@ enum { TW_F32 = 0, TW_BF16 = 1, TW_F16 = 2,
        TW_BF16_W8A16 = 4, /* context dtype only: the same MXFP8 weights and fp8 cross K / V caches, but the weight fragments are
                             widened to bf16 in registers and contracted with the UNQUANTISED bf16 activations on the bf16 MFMA
                             ("W8A16": same bytes from HBM, no activation-quantisation error); up to 64 streams */
-       TW_F16_W8A16 = 5   /* context dtype only: TW_BF16_W8A16 on a float16 base.  Activations, the encoder, the cross-K/V
+       TW_F16_W8A16 = 5,  /* context dtype only: TW_BF16_W8A16 on a float16 base.  Activations, the encoder, the cross-K/V
                             projection GEMM and the self-attention caches are those of a TW_F16 context (saturating at 65504); the
                             decoder projections and the logits projection are MXFP8 with the block structure, scale rule
                             (sb = max(E - 7, 1)) and fragment layout of TW_BF16_W8A16; the cross K / V^T caches are e4m3 of the
@@ -52,8 +52,18 @@ enum { TW_F32 = 0, TW_BF16 = 1, TW_F16 = 2,
                             RNE_f16(e4m3 x 2^(sb-127)), a pure function of the stored bytes.  That product is exact whenever the
                             block's largest magnitude is >= 2^-8; in a block of smaller weights an element below the float16
                             normal range (2^-14) is rounded to the subnormal grid (|error| <= 2^-25) and one below 2^-25 becomes
-                            zero.  Up to 64 streams; d_model and ffn multiples of 128.  The one fp8 context with beam search
-                            (tw_generate_beam) */ };
+                            zero.  Up to 64 streams; d_model and ffn multiples of 128.  An fp8 context with beam search
+                            (tw_generate_beam) */
+       TW_F16_W8A16_FULL = 6 /* context dtype only: TW_F16_W8A16 whose ENCODER linears (every layer's fused QKV, out-projection, fc1,
+                            fc2) and per-layer cross k_proj / v_proj weights are MXFP8 as well, each with one scale byte per output
+                            row and block of 32 along K; conv1, conv2, the positions, LayerNorm vectors and biases stay float16, and
+                            no 16-bit copy of a quantised matrix is kept after tw_finalize_weights.  The quantiser is the decoder's:
+                            W' = f16(g * W) where a LayerNorm is folded (gw and cb from W' as in every context), magnitudes clamped to
+                            63488, sb = max(E - 7, 1) per block, elements RNE_e4m3(W' / 2^(sb-127)), and a row sees
+                            w = RNE_f16(e4m3 x 2^(sb-127)).  Activations are not quantised ("W8A16"): the encoder IS the TW_F16
+                            encoder over the de-quantised weights w, bit for bit, whatever the batch (one summation order: a K tile
+                            of 64 in ascending k into one float32 accumulator per output tile).  The decoder side - projections,
+                            logits, e4m3 cross K / V^T, rows launches, drafts, beams, limits - is TW_F16_W8A16's, launch for launch */ };
 
 /* error codes */
 enum {
@@ -88,7 +98,8 @@ typedef struct tw_config {
   int32_t dtype;                 /* TW_BF16 (production), TW_F16 (the reference's streaming default dtype,
                                     R:thestage_speechkit/streaming/streaming_pipeline.py:369-370: same MFMA rate, 10 mantissa bits,
                                     activations saturate at 65504 as HF clamps its float16 hidden states), TW_F32 (strict-parity
-                                    mode), TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 (fp8 decoder weights) */
+                                    mode), TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 (fp8 decoder weights), TW_F16_W8A16_FULL
+                                    (fp8 encoder and cross-K/V projection weights too) */
   int32_t n_align_heads;         /* alignment heads for word timestamps (generation_config.alignment_heads) */
   int32_t align_heads[2 * TW_MAX_ALIGN_HEADS]; /* (layer, head) pairs */
   int32_t device;                /* HIP device ordinal */
@@ -210,7 +221,8 @@ int tw_encode_tapped(tw_ctx* ctx, const void* mel_dev, int32_t mel_dtype, int32_
 /* Host only, no GPU and no context needed: which kernel the encoder's launches take for a shape, so that a test can prove which
  * code it reached.  tw_gemm_plan: dtype = TW_F32 / TW_BF16 / TW_F16, mode = 0 for a row-major output, 2 for the encoder's fused
  * QKV projection, 3 for the cross K/V projection; C[M, N] = A[M, K] W[N, K]^T; *kernel = 1 (both operands through LDS, bm x 64
- * tiles) or 2 (weights straight to registers, bm x 256 tiles), *bm = the tile height.  tw_enc_attention_plan: B streams of H
+ * tiles) or 2 (weights straight to registers, bm x 256 tiles), *bm = the tile height; dtype = TW_F16_W8A16_FULL (N, K multiples of
+ * 128): *kernel = 3 (MXFP8 weights widened in registers), *bm = 64 (64 x 128 tiles) or 80 (80 x 256).  tw_enc_attention_plan: B streams of H
  * heads and T frames; *queries_per_block = 64 or 128, *xcd = 1 when heads are pinned to XCDs.  Any output pointer may be NULL. */
 int tw_gemm_plan(int32_t dtype, int32_t mode, int32_t M, int32_t N, int32_t K, int32_t* kernel, int32_t* bm);
 int tw_enc_attention_plan(int32_t dtype, int32_t B, int32_t H, int32_t T, int32_t* queries_per_block, int32_t* xcd);

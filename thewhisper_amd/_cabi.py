@@ -16,6 +16,7 @@ TW_F32, TW_BF16, TW_F16 = 0, 1, 2
 TW_BF16_MXFP8 = 3  # context dtype only: bf16 activations, MXFP8 decoder projection weights, activations quantised in registers (W8A8)
 TW_BF16_W8A16 = 4  # context dtype only: MXFP8 decoder projection weights widened to bf16 in registers, bf16 activations
 TW_F16_W8A16 = 5  # context dtype only: the same on a float16 base (float16 activations, encoder and caches; weights widened to float16)
+TW_F16_W8A16_FULL = 6  # context dtype only: TW_F16_W8A16 with the encoder's linears and the cross-K/V projection weights in MXFP8 too
 TW_MAX_ALIGN_HEADS = 32
 TW_PCM_F32, TW_PCM_S16 = 0, 1   # tw_resample input formats
 TW_EPI_ROWMAJOR, TW_EPI_QKV_ENC, TW_EPI_KV_CROSS = 0, 2, 3   # tw_gemm_plan epilogue modes

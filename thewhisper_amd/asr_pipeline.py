@@ -47,6 +47,7 @@ class ASRPipeline(AutomaticSpeechRecognitionPipeline):
             device = os.environ["THEWHISPER_DEVICE"]
         engine_factory: Optional[Callable] = kwargs.pop("engine_factory", None)  # test seam only
         decoder_weights: Optional[str] = kwargs.pop("decoder_weights", None)     # MI355X-only option: "fp8" = MXFP8 decoder weights
+        encoder_weights: Optional[str] = kwargs.pop("encoder_weights", None)     # MI355X-only option: "fp8" with decoder_weights="fp8" and float16
         shared_engine = kwargs.pop("engine", None)  # MI355X-only option: an already loaded WhisperEngine (shared context)
         if model_size not in (None, "S", "M", "L", "XL"):
             raise ValueError(f"Invalid model_size: {model_size}")
@@ -104,6 +105,6 @@ class ASRPipeline(AutomaticSpeechRecognitionPipeline):
             return
         engine = self.model.build_engine(
             chunk_length_s=chunk_length_s, max_batch=max(1, min(64, batch_size)), dtype=torch_dtype,
-            engine_factory=engine_factory, decoder_weights=decoder_weights,
+            engine_factory=engine_factory, decoder_weights=decoder_weights, encoder_weights=encoder_weights,
         )
         self.feature_extractor.attach_engine(engine)

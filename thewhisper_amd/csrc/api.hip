@@ -25,6 +25,9 @@ struct LayerW {
   void *wqkv = nullptr, *bqkv = nullptr;    // [3d, d], [3d] (q rows pre-scaled by 1/8, k bias = 0)
   // MXFP8 contexts: block scales of the six decoder projections (inside the weight buffers, behind the fp8 fragments)
   unsigned char *s_qkv = nullptr, *s_o = nullptr, *s_qc = nullptr, *s_oc = nullptr, *s_1 = nullptr, *s_2 = nullptr;
+  // TW_F16_W8A16_FULL: an ENCODER layer's wqkv / wo / w1 / w2 and a decoder layer's wkv_c are e4m3 fragments too (k_gemm_w8.hip), with
+  // their block scales in s_qkv / s_o / s_1 / s_2 and s_kv (behind the fragments, in buffers of their own size: the 16-bit ones are freed)
+  unsigned char* s_kv = nullptr;
   void *wo = nullptr, *bo = nullptr;
   void *lnx_g = nullptr, *lnx_b = nullptr;  // encoder_attn_layer_norm (decoder)
   void *wq_c = nullptr, *bq_c = nullptr;    // cross q (pre-scaled)
@@ -64,7 +67,8 @@ struct tw_ctx {
   tw_config cfg{};
   int dtype = 1;
   bool w8 = false;   // decoder projection weights in MXFP8 (TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 contexts)
-  int a16 = 0;       // ... contracted as bf16 (float16) after widening in registers (TW_BF16_W8A16, TW_F16_W8A16)
+  int a16 = 0;       // ... contracted as bf16 (float16) after widening in registers (TW_BF16_W8A16, TW_F16_W8A16, TW_F16_W8A16_FULL)
+  bool enc8 = false; // TW_F16_W8A16_FULL: the encoder's linears and the cross-K/V projection weights are MXFP8 as well (launch_gemm_w8)
   // "cross query ahead" (decode_core): the decoder's cross-attention query projection is folded into the two launches before
   // it, which saves one dependent launch per layer and step.  du = float32 [Bmax][d] pre-activation of that projection.
   bool fuse_cq = false;
@@ -341,11 +345,12 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   if (cfg->heads <= 0 || cfg->d_model != cfg->heads * 64)
     return fail(nullptr, TW_EINVAL, "head_dim must be 64 (d_model=%d heads=%d)", cfg->d_model, cfg->heads);
   if (cfg->dtype != TW_BF16 && cfg->dtype != TW_F32 && cfg->dtype != TW_F16 && cfg->dtype != TW_BF16_MXFP8 && cfg->dtype != TW_BF16_W8A16 &&
-      cfg->dtype != TW_F16_W8A16)
-    return fail(nullptr, TW_EINVAL, "dtype must be TW_BF16, TW_F16, TW_F32, TW_BF16_MXFP8, TW_BF16_W8A16 or TW_F16_W8A16");
-  const bool cfg_w8 = cfg->dtype == TW_BF16_MXFP8 || cfg->dtype == TW_BF16_W8A16 || cfg->dtype == TW_F16_W8A16;
+      cfg->dtype != TW_F16_W8A16 && cfg->dtype != TW_F16_W8A16_FULL)
+    return fail(nullptr, TW_EINVAL, "dtype must be TW_BF16, TW_F16, TW_F32, TW_BF16_MXFP8, TW_BF16_W8A16, TW_F16_W8A16 or TW_F16_W8A16_FULL");
+  const bool cfg_f16w8 = cfg->dtype == TW_F16_W8A16 || cfg->dtype == TW_F16_W8A16_FULL;   // the float16-based fp8 contexts: one decoder
+  const bool cfg_w8 = cfg->dtype == TW_BF16_MXFP8 || cfg->dtype == TW_BF16_W8A16 || cfg_f16w8;
   if (cfg_w8 && (cfg->d_model % 128 || cfg->ffn % 128))
-    return fail(nullptr, TW_EINVAL, "TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 need d_model and ffn to be multiples of 128");
+    return fail(nullptr, TW_EINVAL, "TW_BF16_MXFP8 / TW_BF16_W8A16 / TW_F16_W8A16 / TW_F16_W8A16_FULL need d_model and ffn to be multiples of 128");
   if (cfg->d_model % 64 || cfg->ffn % 64 || cfg->d_model > 1280)
     return fail(nullptr, TW_EINVAL, "d_model/ffn must be multiples of 64 and d_model <= 1280");
   if (cfg->max_batch < 1 || cfg->max_batch > 64) return fail(nullptr, TW_EINVAL, "max_batch must be in [1,64]");
@@ -366,10 +371,11 @@ static int create_ctx(const tw_config* cfg, const tw_ctx* share, tw_ctx** out) {
   tw_ctx* c = new tw_ctx();
   c->cfg = *cfg;
   c->w8 = cfg_w8;
-  c->a16 = cfg->dtype == TW_BF16_W8A16 || cfg->dtype == TW_F16_W8A16;
+  c->a16 = cfg->dtype == TW_BF16_W8A16 || cfg_f16w8;
+  c->enc8 = cfg->dtype == TW_F16_W8A16_FULL;
   // the 16-bit type everything but the quantised operands is kept and computed in: a TW_F16_W8A16 context issues the launches of
   // a TW_F16 context for the encoder, the cross-K/V GEMM, the self-attention and the weight fold
-  c->dtype = c->w8 ? (cfg->dtype == TW_F16_W8A16 ? (int)TW_F16 : (int)TW_BF16) : cfg->dtype;
+  c->dtype = c->w8 ? (cfg_f16w8 ? (int)TW_F16 : (int)TW_BF16) : cfg->dtype;
   c->esz = c->dtype == TW_F32 ? 4 : 2;
   c->d = cfg->d_model; c->H = cfg->heads; c->ffn = cfg->ffn; c->V = cfg->vocab;
   c->T = cfg->source_positions; c->Tp = (c->T + 63) / 64 * 64; c->P = cfg->target_positions;
@@ -743,18 +749,42 @@ int tw_finalize_weights(tw_ctx* c, void* stream) {
       HIPCHK(c, hipMemcpyAsync(w, scratch, (size_t)N * K * e, hipMemcpyDeviceToDevice, st));
       return TW_OK;
     };
+    // TW_F16_W8A16_FULL: those of the encoder layers and the cross K|V projection are quantised instead (the decoder's quantiser with
+    // 16-row tiles: its fragments are what gemm_w8reg_kernel requests; the scales are re-laid for it) into a buffer of N K (1 + 1/32)
+    // bytes that replaces the 16-bit one, which is freed behind the stream
+    std::vector<void*> stale;
+    auto quant_gemm = [&](void** w, unsigned char** scales, int N, int K) -> int {
+      const size_t nk = (size_t)N * K;
+      unsigned char* sc = reinterpret_cast<unsigned char*>(scratch);
+      unsigned char* q = nullptr;
+      ALLOC(c, q, nk + nk / 32, false);
+      HIPCHK(c, launch_quant_mx8(c->dtype, *w, sc, sc + nk, N, K, 16, st));
+      HIPCHK(c, hipMemcpyAsync(q, sc, nk, hipMemcpyDeviceToDevice, st));
+      HIPCHK(c, launch_w8_scales(sc + nk, q + nk, N, K, st));
+      stale.push_back(*w);
+      *w = q;
+      *scales = q + nk;
+      return TW_OK;
+    };
+    auto prep_gemm = [&](void** w, unsigned char** scales, int N, int K) -> int {
+      return c->enc8 ? quant_gemm(w, scales, N, K) : retile_gemm(*w, N, K);
+    };
     if (r == TW_OK) r = retile_gemm(c->conv1_w, c->d, 3 * c->C);
     if (r == TW_OK) r = retile_gemm(c->conv2_w, c->d, 3 * c->d);
     for (int l = 0; l < c->Le && r == TW_OK; ++l) {
       LayerW& L = c->enc[l];
-      if ((r = retile_gemm(L.wqkv, 3 * c->d, c->d)) != TW_OK) break;
-      if ((r = retile_gemm(L.wo, c->d, c->d)) != TW_OK) break;
-      if ((r = retile_gemm(L.w1, c->ffn, c->d)) != TW_OK) break;
-      if ((r = retile_gemm(L.w2, c->d, c->ffn)) != TW_OK) break;
+      if ((r = prep_gemm(&L.wqkv, &L.s_qkv, 3 * c->d, c->d)) != TW_OK) break;
+      if ((r = prep_gemm(&L.wo, &L.s_o, c->d, c->d)) != TW_OK) break;
+      if ((r = prep_gemm(&L.w1, &L.s_1, c->ffn, c->d)) != TW_OK) break;
+      if ((r = prep_gemm(&L.w2, &L.s_2, c->d, c->ffn)) != TW_OK) break;
     }
-    for (int l = 0; l < c->Ld && r == TW_OK; ++l) r = retile_gemm(c->dec[l].wkv_c, 2 * c->d, c->d);
+    for (int l = 0; l < c->Ld && r == TW_OK; ++l) r = prep_gemm(&c->dec[l].wkv_c, &c->dec[l].s_kv, 2 * c->d, c->d);
     hipError_t he = hipStreamSynchronize(st);
     hipFree(scratch);
+    for (void* p : stale) {
+      c->allocs.erase(std::find(c->allocs.begin(), c->allocs.end(), p));
+      (void)hipFree(p);
+    }
     if (r != TW_OK) return r;
     HIPCHK(c, he);
   }
@@ -794,6 +824,12 @@ int tw_logmel(tw_ctx* c, const float* pcm, int64_t pcm_stride, const int32_t* n_
 }  // extern "C"
 
 namespace {
+
+// a GEMM over a layer's weight matrix, A row-major [M][K]: `scales` non-null (TW_F16_W8A16_FULL) = W is MXFP8, the launch is k_gemm_w8.hip's
+hipError_t layer_gemm(const tw_ctx* c, const void* A, const void* W, const unsigned char* scales, int M, int N, int K, const GemmEpilogue& ep,
+                      hipStream_t st) {
+  return scales ? launch_gemm_w8(A, plain_rows(K), W, scales, M, N, K, ep, st) : launch_gemm(c->dtype, A, plain_rows(K), W, M, N, K, ep, st);
+}
 
 // encoder for B clips whose output goes to slots slot0 .. slot0+B-1 of enc_out (all other buffers are scratch from row 0)
 // `taps` (tw_encode_tapped, a test instrument): copies of whole workspace buffers right after the launch that wrote them; null on
@@ -853,7 +889,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.bias = L.bqkv; ep.mode = EPI_QKV_ENC; ep.T = T; ep.Tp = c->Tp; ep.H = H;
       ep.out = c->qbuf; ep.out2 = c->kbuf; ep.out3 = c->vtbuf;
       if (fold) { ep.bias = nullptr; ep.stats_in = c->ln_stats_a; ep.stats_in_parts = d / 32; ep.ln_gw = L.qkv_gw; ep.ln_cb = L.qkv_cb; }
-      HIPCHK(c, launch_gemm(dt, fold ? c->xa : c->lnbuf, plain_rows(d), L.wqkv, M, 3 * d, d, ep, st));
+      HIPCHK(c, layer_gemm(c, fold ? c->xa : c->lnbuf, L.wqkv, L.s_qkv, M, 3 * d, d, ep, st));
       if (tp) {
         HIPCHK(c, tap(tp->q, c->qbuf, rows_max * d * e));
         HIPCHK(c, tap(tp->k, c->kbuf, rows_max * d * e));
@@ -867,7 +903,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.bias = L.bo; ep.mode = EPI_ROWMAJOR; ep.res = c->xa; ep.res_map = plain_rows(d); ep.c_map = plain_rows(d);
       ep.out = c->xb;
       if (fold) ep.stats_out = c->ln_stats_b;
-      HIPCHK(c, launch_gemm(dt, c->attn, plain_rows(d), L.wo, M, d, d, ep, st));
+      HIPCHK(c, layer_gemm(c, c->attn, L.wo, L.s_o, M, d, d, ep, st));
       if (tp) {
         HIPCHK(c, tap(tp->xb, c->xb, rows_max * d * e));
         HIPCHK(c, tap(tp->ln_stats_b, c->ln_stats_b, rows_max * (d / 32) * 8));
@@ -878,7 +914,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       GemmEpilogue ep{};
       ep.bias = L.b1; ep.gelu = 1; ep.mode = EPI_ROWMAJOR; ep.c_map = plain_rows(F); ep.out = c->ffnh;
       if (fold) { ep.bias = nullptr; ep.stats_in = c->ln_stats_b; ep.stats_in_parts = d / 32; ep.ln_gw = L.fc1_gw; ep.ln_cb = L.fc1_cb; }
-      HIPCHK(c, launch_gemm(dt, fold ? c->xb : c->lnbuf, plain_rows(d), L.w1, M, F, d, ep, st));
+      HIPCHK(c, layer_gemm(c, fold ? c->xb : c->lnbuf, L.w1, L.s_1, M, F, d, ep, st));
       if (tp) HIPCHK(c, tap(tp->ffnh, c->ffnh, rows_max * F * e));
     }
     {
@@ -886,7 +922,7 @@ int encode_core(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, int32_
       ep.bias = L.b2; ep.mode = EPI_ROWMAJOR; ep.res = c->xb; ep.res_map = plain_rows(d); ep.c_map = plain_rows(d);
       ep.out = c->xa;
       if (fold && l + 1 < c->Le) ep.stats_out = c->ln_stats_a;
-      HIPCHK(c, launch_gemm(dt, c->ffnh, plain_rows(F), L.w2, M, d, F, ep, st));
+      HIPCHK(c, layer_gemm(c, c->ffnh, L.w2, L.s_2, M, d, F, ep, st));
       if (tp) HIPCHK(c, tap(tp->xa_out, c->xa, rows_max * d * e));
     }
   }
@@ -924,7 +960,7 @@ int cross_kv_core(tw_ctx* c, int32_t B, int32_t slot0, void* stream) {
       ep.out3 = c->cross_ksc + (size_t)c->Bmax * c->H * c->Tp * l + sc_off;
       ep.out4 = c->cross_vsc + (size_t)c->Bmax * c->H * c->Tp * l + sc_off;
     }
-    HIPCHK(c, launch_gemm(c->dtype, at(c->enc_out, (size_t)slot0 * T * d, c->esz), plain_rows(d), L.wkv_c, B * T, 2 * d, d, ep, st));
+    HIPCHK(c, layer_gemm(c, at(c->enc_out, (size_t)slot0 * T * d, c->esz), L.wkv_c, L.s_kv, B * T, 2 * d, d, ep, st));
   }
   toc(c, 2, st);
   c->cross_B = slot0 + B;
@@ -947,11 +983,14 @@ int tw_encode_tapped(tw_ctx* c, const void* mel, int32_t mel_dtype, int32_t B, v
 }
 
 int tw_gemm_plan(int32_t dtype, int32_t mode, int32_t M, int32_t N, int32_t K, int32_t* kernel, int32_t* bm) {
-  if (dtype != TW_F32 && dtype != TW_BF16 && dtype != TW_F16) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: dtype %d is not TW_F32 / TW_BF16 / TW_F16", dtype);
+  const bool w8 = dtype == TW_F16_W8A16_FULL;   // its MXFP8 GEMMs (k_gemm_w8.hip): kernel 3
+  if (dtype != TW_F32 && dtype != TW_BF16 && dtype != TW_F16 && !w8)
+    return fail(nullptr, TW_EINVAL, "tw_gemm_plan: dtype %d is not TW_F32 / TW_BF16 / TW_F16 / TW_F16_W8A16_FULL", dtype);
   if (mode != EPI_ROWMAJOR && mode != EPI_QKV_ENC && mode != EPI_KV_CROSS) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: mode %d", mode);
-  const int kt = dtype == TW_F32 ? 32 : 64;   // elements per K tile (k_gemm.hip)
-  if (M < 1 || N < 64 || N % 64 != 0 || K < kt || K % kt != 0) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: no GEMM for M=%d N=%d K=%d", M, N, K);
-  const GemmPlan p = gemm_plan(mode, M, N);
+  const int kt = dtype == TW_F32 ? 32 : w8 ? 128 : 64;   // K granule (k_gemm.hip: one K tile; k_gemm_w8.hip: a pair)
+  const int nt = w8 ? 128 : 64;
+  if (M < 1 || N < nt || N % nt != 0 || K < kt || K % kt != 0) return fail(nullptr, TW_EINVAL, "tw_gemm_plan: no GEMM for M=%d N=%d K=%d", M, N, K);
+  const GemmPlan p = w8 ? gemm_w8_plan(M, N) : gemm_plan(mode, M, N);
   if (kernel) *kernel = p.kernel;
   if (bm) *bm = p.bm;
   return TW_OK;

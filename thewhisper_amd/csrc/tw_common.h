@@ -208,6 +208,13 @@ hipError_t launch_gemm(int dtype, const void* A, RowMap amap, const void* W, int
 // picks for an epilogue mode and shape: pure host arithmetic, no device needed
 struct GemmPlan { int kernel, bm; };
 GemmPlan gemm_plan(int mode, int M, int N);
+// The same product over MXFP8 weights (k_gemm_w8.hip; TW_F16_W8A16_FULL): float16 A, W8 = e4m3 fragments as launch_quant_mx8 leaves them
+// for 16-row tiles, WS = their block scales re-laid by launch_w8_scales; each weight widened to float16 in registers.  K % 128 == 0,
+// N % 128 == 0.  Every epilogue mode of launch_gemm.  gemm_w8_plan: kernel = 3, bm = 64 (64 x 128 tiles) or 80 (80 x 256)
+hipError_t launch_gemm_w8(const void* A, RowMap amap, const void* W8, const void* WS, int M, int N, int K, const GemmEpilogue& ep,
+                          hipStream_t st);
+GemmPlan gemm_w8_plan(int M, int N);
+hipError_t launch_w8_scales(const void* src, void* dst, int N, int K, hipStream_t st);   // N * K / 32 bytes each
 
 hipError_t launch_layernorm(int dtype, const void* x, const void* g, const void* b, void* y, int rows, int d,
                             hipStream_t st);

@@ -264,10 +264,11 @@ class WhisperEngine:
         self.dtype_name = dtype
         # "f16" = float16 context (round 4): the reference's streaming default dtype; same kernels instantiated for _Float16
         # "fp8f16" = "fp8a16" on a float16 base (TW_F16_W8A16): float16 activations, encoder and caches, the same fp8 bytes
+        # "fp8f16full" = "fp8f16" whose encoder linears and cross-K/V projection weights are fp8 as well (TW_F16_W8A16_FULL)
         self.tw_dtype = {"bf16": _cabi.TW_BF16, "f16": _cabi.TW_F16, "f32": _cabi.TW_F32, "fp8a8": _cabi.TW_BF16_MXFP8,
-                         "fp8a16": _cabi.TW_BF16_W8A16, "fp8f16": _cabi.TW_F16_W8A16}[dtype]
+                         "fp8a16": _cabi.TW_BF16_W8A16, "fp8f16": _cabi.TW_F16_W8A16, "fp8f16full": _cabi.TW_F16_W8A16_FULL}[dtype]
         self.torch_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "fp8a8": torch.bfloat16,
-                            "fp8a16": torch.bfloat16, "fp8f16": torch.float16}[dtype]
+                            "fp8a16": torch.bfloat16, "fp8f16": torch.float16, "fp8f16full": torch.float16}[dtype]
         self.alignment_heads = [tuple(map(int, x)) for x in (alignment_heads or [])]
         cfg = _cabi.tw_config()
         cfg.d_model = dims["d_model"]

@@ -339,7 +339,7 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
     # -- engine lifetime ---------------------------------------------------------------------------
     def build_engine(self, chunk_length_s: int = 30, max_batch: int = 1, dtype: Optional[torch.dtype] = None,
                      engine_factory: Optional[Callable] = None, release_torch_weights: bool = True,
-                     decoder_weights: Optional[str] = None):
+                     decoder_weights: Optional[str] = None, encoder_weights: Optional[str] = None):
         """Create the context for T = 50*chunk_length_s encoder frames and upload the weights (A0 is applied by
         the library: tw_finalize_weights interpolates the positional table like patch_hf_model)."""
         if chunk_length_s > 30 or chunk_length_s < 1:
@@ -361,6 +361,13 @@ class AMDWhisperForConditionalGeneration(WhisperForConditionalGeneration, _Engin
             # a float16 request keeps its float16 activations, encoder and caches (TW_F16_W8A16); bf16 - and float16 under
             # THEWHISPER_FP16_AS_BF16=1 - the bf16-based flavour
             eng_dtype = "fp8f16" if eng_dtype == "f16" else "fp8"
+        # encoder_weights="fp8": the encoder's linears and the cross-K/V projection weights in fp8 too (TW_F16_W8A16_FULL, float16 base only)
+        if encoder_weights not in (None, "fp8"):
+            raise ValueError(f"Invalid encoder_weights: {encoder_weights}")
+        if encoder_weights == "fp8":
+            if eng_dtype != "fp8f16":
+                raise ValueError("encoder_weights='fp8' is valid only together with decoder_weights='fp8' and a float16 torch_dtype")
+            eng_dtype = "fp8f16full"
         heads = getattr(self.generation_config, "alignment_heads", None) or []
         factory = engine_factory or type(self)._engine_factory
         dev_index = p0.device.index if p0.device.type == "cuda" and p0.device.index is not None else 0

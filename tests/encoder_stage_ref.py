@@ -10,9 +10,13 @@ round - the LayerNorm-folded weight ``W g`` rounded to T, the attention probabil
 contexts), the stored output rounded to T; in ``"f32"`` the whole stage is evaluated in float32, the matrix products with the
 MFMA's one accumulator per output rounded after every 4-wide k-step (``_matmul_t``).  The LayerNorm-folded stages are emulated in the
 kernels' algebra, rstd (x W'^T - mean gw) + cb (``_ln_linear``).  The emulated variant only sets tolerances (how far honest arithmetic in that format lands from the exact value); it is never the expected value.
+
+The weight format ``"fp8f16full"`` (``StageWeights``) is the MXFP8 encoder of TW_F16_W8A16_FULL: float16 activations (``emul="f16"``) over
+de-quantised weights; for its two folded stages the algebra above IS the exact reference (``_ln_linear_w8``).
 """
 from __future__ import annotations
 
+import copy
 import math
 from typing import Dict, Optional, Tuple
 
@@ -42,10 +46,17 @@ class StageWeights:
     """The encoder's weights of one layer as the engine holds them after ``tw_load_weight``: every tensor rounded to the context
     dtype (``dtype="f64"``: not rounded - the float64 oracle's weights), the 1/8 query scale folded into q_proj (exact: a power of
     two), q | k | v stacked into one [3d, d] matrix whose k rows have no bias, the conv kernels as [d, 3 * C] matrices over windows
-    of three consecutive token rows, and the positional table interpolated to T frames."""
+    of three consecutive token rows, and the positional table interpolated to T frames.
+
+    ``dtype="fp8f16full"`` (TW_F16_W8A16_FULL; api.hip: tw_finalize_weights): every tensor rounded to float16 as loaded, then the four
+    linears as a row of the MXFP8 GEMM sees them - ``wo`` and ``w2`` are f16(mx8_quant_dequant(f16(W))); of the two LayerNorm-folded
+    matrices ``wqkv`` / ``w1`` stay the float16 W (cb = W beta + b is formed from them) and ``wqkv_q`` / ``w1_q`` are
+    f16(mx8_quant_dequant(W')), W' = f16(W g), next to ``wqkv_gw`` / ``w1_gw``, the row sums of the UNQUANTISED W'.  The conv stem,
+    the positions, the biases and the LayerNorm parameters are float16 and not quantised.  ``emul`` of its stages is "f16"."""
 
     def __init__(self, weights: Dict[str, np.ndarray], dims: wo.WhisperDims, T: int, dtype: str, layer: int = 0):
-        r = lambda a: round_to(_t(a), dtype)   # noqa: E731
+        fp8 = dtype == "fp8f16full"
+        r = lambda a: round_to(_t(a), "f16" if fp8 else dtype)   # noqa: E731
         e, p = "model.encoder", f"model.encoder.layers.{layer}"
         self.dims, self.T, self.dtype = dims, T, dtype
         self.d, self.H, self.F = dims.d_model, dims.heads, dims.ffn
@@ -68,6 +79,48 @@ class StageWeights:
         self.w1, self.b1 = r(weights[p + ".fc1.weight"]), r(weights[p + ".fc1.bias"])
         self.w2, self.b2 = r(weights[p + ".fc2.weight"]), r(weights[p + ".fc2.bias"])
         self.lnf_g, self.lnf_b = r(weights[e + ".layer_norm.weight"]), r(weights[e + ".layer_norm.bias"])
+        self._pos_table, self._round = np.asarray(weights[e + ".embed_positions.weight"], dtype=np.float32), r
+        self.wqkv_q = self.wqkv_gw = self.w1_q = self.w1_gw = None
+        if fp8:
+            quant = lambda m: round_to(_t(wo.mx8_quant_dequant(m.numpy().astype(np.float32))), "f16")   # noqa: E731  (float16 in float32: exact)
+            self.wo, self.w2 = quant(self.wo), quant(self.w2)
+            for name, w, g in (("wqkv", self.wqkv, self.ln1_g), ("w1", self.w1, self.ln2_g)):
+                wf = round_to(w * g[None, :], "f16")
+                setattr(self, name + "_q", quant(wf))
+                setattr(self, name + "_gw", wf.sum(-1))
+
+
+    def at_frames(self, T: int) -> "StageWeights":
+        """The same weights for clips of T frames (a shallow copy: only the interpolated positional table depends on T; quantising
+        the matrices of "fp8f16full" at large-v3 width takes seconds)."""
+        W = copy.copy(self)
+        W.T, W.Tp, W.pos = T, (T + 63) // 64 * 64, self._round(wo.interpolate_positions(self._pos_table, T))
+        return W
+
+
+def mx8_scale_exponents(w: np.ndarray) -> np.ndarray:
+    """[N, K/128, 2, 2]: the biased scale exponent sb of block (128-k step, K-tile half h, lane-group pair u) of every row, as
+    wo.mx8_quant_dequant (and the context's quantiser) picks it."""
+    N, K = w.shape
+    amax = np.abs(np.asarray(w, dtype=np.float32).reshape(N, K // 128, 2, 2, 2, 2, 8)).max(axis=(3, 5, 6))
+    return np.maximum(np.floor(np.log2(np.maximum(amax, 2.0 ** -126))).astype(np.int64) + 127 - 7, 1)
+
+
+def spread_block_scales(weights: Dict[str, np.ndarray], dims: wo.WhisperDims, seed: int = 11) -> Dict[str, np.ndarray]:
+    """A copy of ``weights`` in which every quantiser block of the encoder's six linear matrices is multiplied by 2^-1, 2^0 or 2^1,
+    drawn per (row, block).  wo.make_weights draws a matrix uniformly in +-1.7 / sqrt(K): at K = 1280 and 5120 the largest of a block's 32
+    values lies in ONE binade for every block, so all scale bytes of a matrix are equal and a kernel that fetches the scale of another
+    block, K tile or row computes the same numbers.  Spread, neighbouring blocks differ in two cases of three.  The values stay off the
+    fp8 grid, and a matrix' variance grows by 1.75."""
+    out = dict(weights)
+    rng = np.random.default_rng(seed)
+    for i in range(dims.enc_layers):
+        for m in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "fc1", "fc2"):
+            name = f"model.encoder.layers.{i}.{m}.weight"
+            N, K = weights[name].shape
+            f = np.ldexp(np.float32(1.0), rng.integers(-1, 2, (N, K // 128, 2, 1, 2, 1, 1))).astype(np.float32)
+            out[name] = (np.asarray(weights[name], dtype=np.float32).reshape(N, K // 128, 2, 2, 2, 2, 8) * f).reshape(N, K)
+    return out
 
 
 # ---- arithmetic shared by the stages -----------------------------------------------------------------------------------------
@@ -123,6 +176,17 @@ def _ln_linear(x, g, beta, w, b, emul):
     return rstd * (_matmul_t(x, wf, emul) - mu * wf.sum(-1)[None, :]) + cb
 
 
+def _ln_linear_w8(x, beta, w, b, wq, gw):
+    """The folded stage of the "fp8f16full" weight format, exact AND emulated (the caller rounds the stored value): the context's defined
+    algebra rstd (x Wq^T - mean gw) + cb in float64, Wq the de-quantised fold, gw the row sums of the UNQUANTISED fold, cb = W beta + b.
+    It is not LayerNorm followed by a linear - gw does not belong to Wq - and that difference is the context's specification, not
+    kernel error.  Every weight is a float16 value already, so the emulation has nothing to round in here."""
+    x = x.to(F64)
+    mu = x.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
+    return rstd * (x @ wq.T - mu * gw[None, :]) + (w @ beta + (b if b is not None else 0.0))
+
+
 def _store(y, emul):
     return round_to(y, emul).to(F64)
 
@@ -162,6 +226,8 @@ def block_stats(x: torch.Tensor, emul: Optional[str] = None) -> torch.Tensor:
 
 def ln_qkv_rows(xa: torch.Tensor, W: StageWeights, emul: Optional[str] = None) -> torch.Tensor:
     """xa [M, d] -> [M, 3d] = q | k | v of LayerNorm(xa), q scaled by 1/8, k without bias, rounded as stored."""
+    if W.wqkv_q is not None:
+        return _store(_ln_linear_w8(xa, W.ln1_b, W.wqkv, W.bqkv, W.wqkv_q, W.wqkv_gw), emul)
     return _store(_ln_linear(xa.to(F64), W.ln1_g, W.ln1_b, W.wqkv, W.bqkv, emul), emul)
 
 
@@ -198,6 +264,8 @@ def out_proj_residual(attn: torch.Tensor, xa: torch.Tensor, W: StageWeights, emu
 
 def ln_fc1_gelu(xb: torch.Tensor, W: StageWeights, emul: Optional[str] = None) -> torch.Tensor:
     """xb [M, d] -> GELU(LayerNorm(xb) W1^T + b1) [M, F]."""
+    if W.w1_q is not None:
+        return _store(gelu(_ln_linear_w8(xb, W.ln2_b, W.w1, W.b1, W.w1_q, W.w1_gw)), emul)
     return _store(gelu(_ln_linear(xb.to(F64), W.ln2_g, W.ln2_b, W.w1, W.b1, emul)), emul)
 
 

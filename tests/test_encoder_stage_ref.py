@@ -39,6 +39,58 @@ def test_composed_stages_are_the_float64_oracle(preset, T):
         assert lo < rel < hi, (emul, rel)
 
 
+@pytest.mark.parametrize("d_model", [128, 256])
+@pytest.mark.parametrize("T", [50, 100])
+def test_composed_fp8_stages_are_the_fp8_context_reference(d_model, T):
+    """The weight format "fp8f16full": composed, the stages are tests/test_gpu_fp8_encoder.RefFull, the float64 model the fp8 GPU tests
+    measure against - two references written independently, tied together before a GPU run trusts either.  (The first run of this
+    test found RefFull 1.4e-7 - 3.9e-7 away: it applied the query's 1/8 to the projection's result where the context rounds W / 8 to
+    float16 at load, and interpolated a float16 positional table where the context rounds the interpolated one.  RefFull was fixed.)"""
+    from tests.test_gpu_fp8_encoder import RefFull
+
+    dims = dims_variant("micro", d_model=d_model, heads=d_model // 64, ffn=512, enc_layers=2, dec_layers=1)
+    w = wo.make_weights(dims, 2)
+    B = 2
+    mel = R.round_to(torch.from_numpy(wo.log_mel(clips(T * 320, B), dims.n_mels)).double(), "f16").numpy()   # as mel_transpose leaves it
+    ref = RefFull(dims, w, T=T).encode(mel)
+    got = _compose(mel, w, dims, T, B, None, "fp8f16full")
+    assert np.linalg.norm(got - ref) / np.linalg.norm(ref) < 1e-12
+    assert np.abs(got - ref).max() < 1e-12 * np.abs(ref).max() * 100
+    # it is a different model from the float16 one over the same tensors (the quantiser moves it by ~2^-4 per weight) ...
+    plain = _compose(mel, w, dims, T, B, None, "f16")
+    assert 1e-3 < np.linalg.norm(got - plain) / np.linalg.norm(plain) < 1e-1
+    # ... and its emulation is float16's: one rounding of every stored value
+    e = _compose(mel, w, dims, T, B, "f16", "fp8f16full")
+    assert 1e-5 < np.linalg.norm(e - ref) / np.linalg.norm(ref) < 4e-3
+    # the stages of the existing formats do not see the new fields
+    W = R.StageWeights(w, dims, T, "f16")
+    assert W.wqkv_q is None and W.w1_q is None
+
+
+def test_spread_block_scales_gives_neighbouring_blocks_different_scale_bytes():
+    """What makes the per-launch fp8 GPU test see a wrong scale byte: at large-v3 width make_weights alone gives every block of a
+    matrix the same one (a library that fetched the scale pair of the previous two K tiles passed that test with unchanged figures)."""
+    dims = dims_variant("large-v3", enc_layers=1, dec_layers=0)
+    w = wo.make_weights(dims, 1)
+    s = R.spread_block_scales(w, dims)
+    assert set(s) == set(w)
+    W = R.StageWeights(s, dims, 500, "f16")
+    for name, folded in (("self_attn.q_proj", W.wqkv[:1280] * W.ln1_g), ("self_attn.out_proj", W.wo), ("fc1", W.w1 * W.ln2_g), ("fc2", W.w2)):
+        key = f"model.encoder.layers.0.{name}.weight"
+        drawn = R.mx8_scale_exponents(w[key])
+        assert (drawn == np.median(drawn)).mean() > 0.9999, name    # as drawn: one scale byte (a block's largest of 32 misses its binade at 1.5e-6)
+        sb = R.mx8_scale_exponents(R.round_to(folded, "f16").numpy())                      # as the context quantises it
+        assert len(np.unique(sb)) >= 3, name
+        pair = sb.reshape(sb.shape[0], -1, 4)                                             # [row, 128-k step = pair of K tiles, (h, u)]
+        assert (pair[:, 1:] != pair[:, :-1]).mean() > 0.6 and (pair[1:] != pair[:-1]).mean() > 0.6, name
+        assert (sb[:, :, 0] != sb[:, :, 1]).mean() > 0.6 and (sb[..., 0] != sb[..., 1]).mean() > 0.6, name
+        ratio = s[key] / w[key]
+        assert set(np.unique(ratio[np.isfinite(ratio)])) == {0.5, 1.0, 2.0}
+        assert not np.array_equal(wo.mx8_quant_dequant(s[key]), s[key])                     # off the grid
+    untouched = [k for k in w if ".layers." not in k]
+    assert untouched and all(s[k] is w[k] for k in untouched)
+
+
 def test_rows_argument_selects_rows_of_the_full_result():
     dims = dims_variant("micro", dec_layers=0)
     w = wo.make_weights(dims, 1)
@@ -156,3 +208,26 @@ def test_plan_query_agrees_with_the_dispatch_table(built_library):
         assert cabi.enc_attention_plan(cabi.TW_F32, B, H, T) == (64, want[1])
     with pytest.raises(RuntimeError):
         cabi.gemm_plan(cabi.TW_BF16, 0, 100, 100, 1280)      # N is no multiple of 64: launch_gemm refuses the shape too
+
+
+PLAN_SWEEP_M = list(range(1, 2200, 7)) + list(range(2200, 26000, 61)) + [1000, 1001, 2000, 2500, 3000, 3200, 7000, 8000, 8750, 10000, 12000]
+
+
+def test_plan_query_of_the_fp8_context(built_library):
+    """TW_F16_W8A16_FULL (k_gemm_w8.hip: gemm_w8_plan): kernel 3; 80 x 256 tiles exactly where the 16-bit weights get kernel 2, 64 x 128
+    tiles elsewhere, whatever the epilogue."""
+    from thewhisper_amd import _cabi as cabi
+
+    dt = cabi.TW_F16_W8A16_FULL
+    # the thresholds at d = 1280, by hand: kernel 2 from 512 tiles of 128 x 128 on = ceil(M / 128) >= 512 / (N / 128)
+    first80 = {5120: 1537, 3840: 2177, 2560: 3201, 1280: 6529}
+    for N, M0 in first80.items():
+        assert M0 == 128 * (-(-512 // (N // 128)) - 1) + 1
+        for mode in (cabi.TW_EPI_ROWMAJOR, cabi.TW_EPI_QKV_ENC, cabi.TW_EPI_KV_CROSS):
+            assert cabi.gemm_plan(dt, mode, M0 - 1, N, 1280) == (3, 64) and cabi.gemm_plan(dt, mode, M0, N, 1280) == (3, 80), (N, mode)
+    for M in PLAN_SWEEP_M + [m + e for m in first80.values() for e in (-1, 0)]:
+        for N in (128, 1280, 2560, 3840, 5120):
+            want = (3, 80 if _plan_by_hand(M, N)[0] == 2 else 64)
+            assert cabi.gemm_plan(dt, cabi.TW_EPI_ROWMAJOR, M, N, 1280) == want, (M, N)
+            assert want[1] == (80 if N in first80 and M >= first80[N] else 64), (M, N)
+    assert cabi.gemm_plan(dt, cabi.TW_EPI_ROWMAJOR, 8000, 1280, 5120) == (3, 80)     # fc2: the plan does not depend on K

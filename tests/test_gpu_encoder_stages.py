@@ -98,15 +98,20 @@ def _need_gpu():
     _cache.clear()
 
 
-def _weights():
-    if "w" not in _cache:
-        _cache["w"] = wo.make_weights(DIMS, 1)
-    return _cache["w"]
+def _weights(dtype=None):
+    """make_weights tensors; for the weight format "fp8f16full" with the block scales of the quantised matrices spread
+    (encoder_stage_ref.spread_block_scales: as drawn, every block of a matrix of this width has the same scale byte)."""
+    key = "w8" if dtype == "fp8f16full" else "w"
+    if key not in _cache:
+        w = wo.make_weights(DIMS, 1)
+        _cache[key] = R.spread_block_scales(w, DIMS) if key == "w8" else w
+    return _cache[key]
 
 
 def _stage_weights(T, dtype):
     if ("W", T, dtype) not in _cache:
-        _cache[("W", T, dtype)] = R.StageWeights(_weights(), DIMS, T, dtype)
+        other = next((v for k, v in _cache.items() if isinstance(k, tuple) and k[0] == "W" and k[2] == dtype), None)     # (only the positions depend on T)
+        _cache[("W", T, dtype)] = other.at_frames(T) if other is not None else R.StageWeights(_weights(dtype), DIMS, T, dtype)
     return _cache[("W", T, dtype)]
 
 
@@ -135,8 +140,10 @@ def _sample(n_rows, n=640):
 
 def check_stages(taps, mel, T, B, dtype):
     """taps: CPU float64 tensors in the layouts of encode_tapped (Bm >= B clips).  Returns {stage: (kernel error, E_emul)} over every
-    launch, every element; raises on the conditions that are not measurements."""
+    launch, every element; raises on the conditions that are not measurements.  ``dtype`` is the weight format of the references
+    (encoder_stage_ref.StageWeights); the activations of "fp8f16full" are float16."""
     W = _stage_weights(T, dtype)
+    dtype = "f16" if dtype == "fp8f16full" else dtype     # from here on: the format the kernels round activations to
     M, Tp = B * T, W.Tp
     out = {}
 
@@ -205,7 +212,12 @@ def _tapped(eng, mel):
 @pytest.mark.parametrize("T,B,dtype,want", CASES, ids=[f"{T}x{B}-{dt}" for T, B, dt, _ in CASES])
 def test_every_launch_against_its_float64_reference(T, B, dtype, want):
     assert plans(T, B, dtype) == want      # the launches of this case reach the kernels and tile heights it is here for
-    eng = make_engine(DIMS, _weights(), T=T, max_batch=B, dtype=dtype)
+    check_every_launch(T, B, dtype)
+
+
+def check_every_launch(T, B, dtype):
+    """One tapped encode of B clips in a ``dtype`` context: the STAGE lines, and every stage within 4 x its E_emul."""
+    eng = make_engine(DIMS, _weights(dtype), T=T, max_batch=B, dtype=dtype)
     mel = _mel(T, B)
     hidden, taps = _tapped(eng, mel)
     plain = eng.encode(torch.from_numpy(mel).cuda(), return_hidden=True)
@@ -220,13 +232,18 @@ def test_every_launch_against_its_float64_reference(T, B, dtype, want):
         if not err <= 4.0 * e_emul:
             bad.append((name, err, e_emul))
     assert not bad, f"stages over 4 x E_emul: {bad}"
+    return res
 
 
 @pytest.mark.parametrize("T,B,dtype", OVERRUN_CASES)
 def test_no_launch_writes_past_its_rows(T, B, dtype):
+    check_no_launch_writes_past_its_rows(T, B, dtype)
+
+
+def check_no_launch_writes_past_its_rows(T, B, dtype):
     """A context for B + 1 clips: encode B + 1 clips, then B other clips; what the first run left in the rows of clip B must survive
     the second bit for bit, in every tapped buffer (a ragged last tile that writes past M would not leave it)."""
-    eng = make_engine(DIMS, _weights(), T=T, max_batch=B + 1, dtype=dtype)
+    eng = make_engine(DIMS, _weights(dtype), T=T, max_batch=B + 1, dtype=dtype)
     _, first = _tapped(eng, _mel(T, B + 1))
     _, second = _tapped(eng, _mel(T, B, seed0=100))
     eng.close()

@@ -28,31 +28,44 @@ def quantised(dims):
     return mats, [f"{p}.{n}.weight" for p in enc for n in ("self_attn_layer_norm", "final_layer_norm")]
 
 
+def put_on_grid(dims, w, seed=5, elem_exp=(-4, 5)):
+    """`w` with every matrix the context quantises ON the fp8 grid (in place; returns w): per block e4m3 normals (8 + r) 2^j x 2^s,
+    j in [elem_exp), with one magnitude in [128, 240], so sb reproduces s and quantisation is the identity; three distinct block scales
+    s per matrix; the folded LayerNorms' gains 1.0: the fold changes nothing"""
+    rng = np.random.default_rng(seed)
+    mats, gains = quantised(dims)
+    for name in gains:
+        w[name] = np.ones_like(w[name])
+    for name in mats:
+        N, K = w[name].shape
+        shp = (N, K // 128, 2, 2, 2, 2, 8)                                   # [n, step, h, mm, u, kk, e]: block (step, h, u) = (mm, kk, e)
+        v = (8 + rng.integers(0, 8, shp)) * np.ldexp(1.0, rng.integers(elem_exp[0], elem_exp[1], shp)) * rng.choice([-1.0, 0.0, 1.0], shp)
+        v[:, :, :, 0, :, 0, 0] = (8 + rng.integers(0, 8, shp[:3] + shp[4:5])) * 16.0
+        s = rng.integers(-12, -9, (N, K // 128, 2, 1, 2, 1, 1))
+        w[name] = (v * np.ldexp(1.0, s)).reshape(N, K).astype(np.float32)
+        assert np.array_equal(wo.mx8_quant_dequant(w[name]), w[name]) and np.array_equal(f16(w[name]), w[name])
+    return w
+
+
 @functools.lru_cache(maxsize=None)
 def model(d_model, ffn, grid):
     dims = dims_variant("micro", d_model=d_model, heads=d_model // 64, ffn=ffn, enc_layers=2, dec_layers=1)
     w = wo.make_weights(dims, 2)
-    if grid:   # every quantised matrix ON the fp8 grid: per block e4m3 normals (8 + r) 2^j x 2^s with one magnitude in [128, 240], so sb
-        rng = np.random.default_rng(5)   # reproduces s and quantisation is the identity; gains 1.0: the fold changes nothing
-        mats, gains = quantised(dims)
-        for name in gains:
-            w[name] = np.ones_like(w[name])
-        for name in mats:
-            N, K = w[name].shape
-            shp = (N, K // 128, 2, 2, 2, 2, 8)                                   # [n, step, h, mm, u, kk, e]: block (step, h, u) = (mm, kk, e)
-            v = (8 + rng.integers(0, 8, shp)) * np.ldexp(1.0, rng.integers(-4, 5, shp)) * rng.choice([-1.0, 0.0, 1.0], shp)
-            v[:, :, :, 0, :, 0, 0] = (8 + rng.integers(0, 8, shp[:3] + shp[4:5])) * 16.0
-            s = rng.integers(-12, -9, (N, K // 128, 2, 1, 2, 1, 1))
-            w[name] = (v * np.ldexp(1.0, s)).reshape(N, K).astype(np.float32)
-            assert np.array_equal(wo.mx8_quant_dequant(w[name]), w[name]) and np.array_equal(f16(w[name]), w[name])
-    return dims, w
+    return dims, put_on_grid(dims, w) if grid else w
 
 
 class RefFull(Ref):
-    """Ref(fp8=True) whose encoder linears and cross k_proj / v_proj are f16(mx8_quant_dequant(f16(g W))), gw / cb from the unquantised W'"""
+    """Ref(fp8=True) whose encoder linears and cross k_proj / v_proj are f16(mx8_quant_dequant(f16(g W))), gw / cb from the unquantised W'.
+    The encoder's q_proj carries its 1/8 as the context holds it, f16(W / 8) rounded at load and folded after that: scaling the
+    projection's result instead keeps the bits that float16 drops where W / 8 is subnormal (2e-7 of the encoder states at d_model 128,
+    found when tests/test_encoder_stage_ref.py composed the per-launch references against this class)."""
 
-    def __init__(self, dims, w):
-        super().__init__(dims, w, True)
+    def __init__(self, dims, w, T=T):
+        super().__init__(dims, w, True, T=T)
+        for i in range(dims.enc_layers):
+            for t in ("weight", "bias"):
+                key = f"model.encoder.layers.{i}.self_attn.q_proj.{t}"
+                self.w[key] = f16(np.asarray(w[key], dtype=np.float32) * np.float32(0.125))
         for i in range(dims.dec_layers):
             for m in ("k_proj", "v_proj"):
                 key = f"model.decoder.layers.{i}.encoder_attn.{m}.weight"
@@ -61,7 +74,7 @@ class RefFull(Ref):
     def encoder_layer(self, x, i):
         p = f"model.encoder.layers.{i}"
         ln1, ln2 = p + ".self_attn_layer_norm", p + ".final_layer_norm"
-        q = self._heads(self._dec_proj(x, ln1, p + ".self_attn.q_proj") * 0.125)
+        q = self._heads(self._dec_proj(x, ln1, p + ".self_attn.q_proj"))
         k = self._heads(self._dec_proj(x, ln1, p + ".self_attn.k_proj", bias=False))
         v = self._heads(self._dec_proj(x, ln1, p + ".self_attn.v_proj"))
         x = x + self._dec_lin(self._merge(wo.softmax(q @ k.transpose(0, 1, 3, 2)) @ v), p + ".self_attn.out_proj")

@@ -27,8 +27,10 @@ def kv8_f16(x):   # oracle.kv8_quant_dequant on float16: per (key, head) sb = ma
 
 
 class Ref(wo.OracleWhisper):
-    def __init__(self, dims, w, fp8):
+    def __init__(self, dims, w, fp8, T=T):
         super().__init__(dims, {k: f16(v) for k, v in w.items()}, T=T, dtype=np.float64)
+        # (the context interpolates the float32 table as loaded and rounds the result: tw_finalize_weights, launch_interp_positions)
+        self.enc_pos = f16(wo.interpolate_positions(np.asarray(w["model.encoder.embed_positions.weight"], dtype=np.float32), self.T))
         self.fp8, self.memo = fp8, {}
 
     def _q(self, key, make):   # the weight a row sees

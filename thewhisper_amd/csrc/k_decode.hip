@@ -846,6 +846,18 @@ __global__ __launch_bounds__(256) void compose_kernel(const T* __restrict__ A, c
 // type for the P.V product as the reference does (HF casts attn_weights to the value dtype).
 // ---------------------------------------------------------------------------------------------
 
+// element [i >> 2][i & 3] of sixteen register values for an index that differs from lane to lane: a tree of selects
+__device__ __forceinline__ float attn_pick16(const f32x4_t (&v)[4], int i) {
+  float s[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float lo = (i & 1) ? v[a][1] : v[a][0], hi = (i & 1) ? v[a][3] : v[a][2];
+    s[a] = (i & 2) ? hi : lo;
+  }
+  const float lo = (i & 4) ? s[1] : s[0], hi = (i & 4) ? s[3] : s[2];
+  return (i & 8) ? hi : lo;
+}
+
 // SINGLE: n_bound <= NW*64, so every K and V^T fragment of the head is requested before anything is waited for
 // (one memory round trip per head); otherwise two passes over chunks of NW*64 keys.
 // n_keys = valid keys (rest masked), n_bound = keys addressable (multiple of 64, <= rows allocated per head).
@@ -896,8 +908,11 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
     for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const u32x4_t*>(qrow + ds * 4 * E + kq * E);
   }
 
-  // ---- scores: D[i = key (lane>>4)*4 + r][j] identical in every column j; column 0 lanes publish them ----
+  // ---- scores: D[i = key (lane>>4)*4 + r][j] identical in every column j.  SINGLE: they stay in the accumulators (sreg), lane
+  // (kq, fr) owning keys a * 16 + kq * 4 + r of its wavefront's 64; two passes: column 0 lanes publish them in LDS ----
+  const int own = (fr >> 2) * 16 + kq * 4 + (fr & 3);   // SINGLE: the key (of 64) whose score lane (kq, fr) picks from sreg
   float m = -1.0e30f;
+  f32x4_t sreg[4];
   for (int c = 0; c < n_chunks; ++c) {
     const int g64 = c * NW + wave;
     if (c > 0) load_k(g64);
@@ -911,7 +926,8 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
         const int t = g64 * 64 + a * 16 + kq * 4 + r;
         const float sv = (t < n_keys) ? acc[r] : -1.0e30f;
         m = fmaxf(m, sv);
-        if (fr == 0 && t < n_bound) sc[t] = sv;
+        if constexpr (SINGLE) sreg[a][r] = sv;
+        else if (fr == 0 && t < n_bound) sc[t] = sv;
       }
     }
   }
@@ -922,7 +938,7 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
 #pragma unroll
   for (int w = 1; w < NW; ++w) M = fmaxf(M, red[w]);
 
-  // ---- probabilities of this wavefront's own keys (written back to LDS for the B operand and the alignment rows) and P.V
+  // ---- probabilities of this wavefront's own keys (written to LDS in key order for the B operand and the alignment rows) and P.V
   f32x4_t o[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -930,9 +946,16 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
   for (int c = 0; c < n_chunks; ++c) {
     const int g64 = c * NW + wave;
     if (!SINGLE) load_v(g64);
-    const int t0 = g64 * 64 + lane;  // one key per lane
+    const bool in = g64 * 64 < n_bound;   // n_bound is a multiple of 64: the wavefront's 64 keys are addressable or none is
+    const int t0 = g64 * 64 + lane;       // one key per lane
     float pr = 0.f;
-    if (t0 < n_bound) {
+    if constexpr (SINGLE) {
+      const int t1 = g64 * 64 + own;      // the exponential of key `own`; the sum below still takes key `lane`
+      if (in) {
+        sc[t1] = (t1 < n_keys) ? expf(attn_pick16(sreg, fr) - M) : 0.f;
+        pr = sc[t0];                      // same wavefront wrote it: LDS operations of a wavefront stay in order
+      }
+    } else if (in) {
       pr = (t0 < n_keys) ? expf(sc[t0] - M) : 0.f;
       sc[t0] = pr;
     }
@@ -940,10 +963,13 @@ __device__ __forceinline__ float attn_mfma_block(const T* __restrict__ q, const 
 #pragma unroll
     for (int ks = 0; ks < DS; ++ks) {
       float pv[E];
+      // the lane's E consecutive keys as 16-byte reads (same wavefront wrote them)
 #pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int t = g64 * 64 + ks * 4 * E + kq * E + e;
-        pv[e] = (t < n_bound) ? sc[t] : 0.f;  // same wavefront wrote these: LDS operations of a wavefront stay in order
+      for (int i = 0; i < E / 4; ++i) {
+        f32x4_t v4 = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        if (in) v4 = *reinterpret_cast<const f32x4_t*>(sc + g64 * 64 + ks * 4 * E + kq * E + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pv[4 * i + e] = v4[e];
       }
       const u32x4_t pf = pack16<T>(pv);
 #pragma unroll
@@ -1135,7 +1161,7 @@ __global__ __launch_bounds__(NW * 64) void dec_self_attn_kernel(const T* __restr
                                                                  T* __restrict__ out, const DecState* __restrict__ stt,
                                                                  typename MAP::Arg map_arg) {
   // argument order: what the K / V^T / q request addresses need comes first (kernarg preload, see skinny_mfma_kernel)
-  __shared__ float sc[512];
+  __shared__ __attribute__((aligned(16))) float sc[512];   // read back in 16-byte vectors
   __shared__ float red[2 * 4 + 4 * 64];
   asm volatile("" ::"s"(q), "s"(kc), "s"(vc), "s"(rows), "s"(H), "s"(key_bound));
   const int h = blockIdx.x, b = blockIdx.y;
